@@ -32,6 +32,12 @@ reports the process group's own world size, the RCCL version and each rank's til
 staged one): frame k runs on slot k % F (its own context, stream and output buffers), so the next frames' waves
 fill the GPU while a frame's slowest waves finish; every frame is traced in full.
 
+A plain run sets up, pre-warms, runs the W warmup and the K timed steps and prints the headline line (value,
+ms_per_step = the wall time of one timed step, config).  --full adds, all untimed: the counted frame (work counters),
+the check of the last frame (oracle digests; N > 1: rank 0's single-process trace of the image), the gather
+alone, the per-kernel timing pass with the roofline block, and the CPU baseline (--cpu-baseline, --cpu-runs,
+--cpu-sample-stride).  --dump-outputs DIR writes what the last timed frame delivered (dump_outputs below).
+
 Prints ONE JSON line on rank 0; fields are described in DESIGN.md (d).
 """
 from __future__ import annotations
@@ -141,11 +147,21 @@ def parse():
                         "for the staged one (scripts/inflight_sweep.sh)")
     p.add_argument("--mode", default="parity", choices=["parity", "fast"],
                    help="fast = BZR_MODE_FAST Newton stage (contracted FMA, approximate div/sqrt; not bit-exact)")
-    p.add_argument("--cpu-baseline", default="on", choices=["on", "off"])
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure (untimed): the counted frame (work counters), "
+                        "the check of the last frame against the oracle digests / the single-process trace, the "
+                        "gather-alone timing, the per-kernel timing pass with the roofline block, and the CPU baseline")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed frame delivered as DIR/<name>.npy "
+                        "(float32 / float64; a fixed seeded sample of the primaries when the frame is larger)")
+    p.add_argument("--cpu-baseline", default="on", choices=["on", "off"], help="with --full only")
     p.add_argument("--cpu-sample-stride", type=int, default=0,
                    help="oracle sample: every k-th row and column (0 = per-config default)")
     p.add_argument("--cpu-runs", type=int, default=5)
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def cpu_model() -> str:
@@ -276,6 +292,39 @@ def oracle_digests(cfg, side, rays_img, status_img, seg_img):
     match = int((got == g["digests"]).all(axis=1).sum())
     return {"tiles_matching": match, "tiles": int(len(g["tiles"])), "ok": match == len(g["tiles"]),
             "source": str(path.relative_to(REPO))}
+
+
+DUMP_MAX_PRIMARIES = 1 << 19  # --dump-outputs: 48 B (chain) / 68 B (intersect) per primary, index included: at most 36 MB
+DUMP_SEED = 20240607
+
+
+def dump_outputs(directory, chain, out, rank, world):
+    """--dump-outputs: this rank's outputs of the last timed frame (the device tensors a caller of trace_chain /
+    intersect receives) as .npy files.  Float rows stay float32; the uint32 words (status, segments; the hit's
+    `what` and `patch` bit patterns) become float64, which holds them exactly.  A frame of more than
+    DUMP_MAX_PRIMARIES primaries is sampled: that many distinct primaries drawn with a fixed seed, in ascending
+    order, their indices into the rank's ray order in `index`."""
+    import torch
+
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    n = int((out[0] if chain else out).shape[1])
+    if n > DUMP_MAX_PRIMARIES:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_PRIMARIES, replace=False))
+    else:
+        idx = np.arange(n)
+    dev_idx = torch.from_numpy(idx).to((out[0] if chain else out).device)
+    words = lambda t: t.index_select(0, dev_idx).cpu().numpy().view(np.uint32).astype(np.float64)  # noqa: E731
+    if chain:
+        arrays = {"rays": out[0].index_select(1, dev_idx).cpu().numpy(), "status": words(out[1]), "segments": words(out[2])}
+    else:
+        h = out.index_select(1, dev_idx).cpu().numpy()
+        arrays = {"hits": np.ascontiguousarray(h[:11]), "what": h[11].view(np.uint32).astype(np.float64),
+                  "patch": h[12].view(np.uint32).astype(np.float64)}
+    arrays["index"] = idx.astype(np.float64)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, arr in arrays.items():
+        np.save(d / f"{name}{suffix}.npy", arr)
 
 
 def verify_frame(a, cfg, chain, world, rank, side, height, ctx, meshes, ris, mode, dev, gather, loop, last, own_out, cap):
@@ -459,14 +508,18 @@ def main():
         else:
             bzr_amd.intersect(ctxs[f], meshes[0], rays, outs[f], mode=mode)
 
-    # work counters of one frame (device-side; measured here, outside the timed region)
-    ctx.counters(True)
-    ctx.counters_report()
+    # one frame outside the timed region: its segment count is the headline figure's numerator; with --full it
+    # also runs with the device-side work counters on
+    work_cnt = None
+    if a.full:
+        ctx.counters(True)
+        ctx.counters_report()
     with torch.cuda.stream(streams[0]):
         trace(0, 0)
     torch.cuda.synchronize()
-    work_cnt = ctx.counters_report()
-    ctx.counters(False)
+    if a.full:
+        work_cnt = ctx.counters_report()
+        ctx.counters(False)
     seg_local = int(out_seg.sum().item()) if chain else n
     seg_total = torch.tensor([seg_local], dtype=torch.int64, device=dev)
     if world > 1:
@@ -550,20 +603,25 @@ def main():
     elapsed = time.perf_counter() - t_start
     chain_ms = events[0].elapsed_time(events[1]) / a.steps
     last_slot = (loop.frames - 1) % F  # the slot of the last timed frame (its outputs are still in place)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, chain, outs[last_slot], rank, world)
     # What the timed frames delivered (untimed): rank 0 checks the last gathered frame
     # against the same frame traced in one process, and (cfg4 4096^2) that frame against the committed oracle
     # digests; at N = 1 the last frame's own outputs against the digests.  Then the gather alone, timed.
-    verify = verify_frame(a, cfg, chain, world, rank, side, height, ctx, meshes, ris, mode, dev, gather, loop,
-                          last_gathered, outs[last_slot], cap)
-    # per-kernel HIP-event timing on the kernels' stream, in a separate untimed pass of the same
-    # K steps (the per-launch events would otherwise sit inside the timed region)
-    ctx.timing(True)
-    ctx.timing_report()  # reset
-    for k in range(a.steps):
-        step(inflight=1)  # slot 0's context only: kernel durations without a neighbouring frame
-    drain()
-    kernels = ctx.timing_report()
-    ctx.timing(False)
+    # All of it with --full only; a plain run stops at the timed steps.
+    verify, kernels = {"gather": {}, "frame": None}, None
+    if a.full:
+        verify = verify_frame(a, cfg, chain, world, rank, side, height, ctx, meshes, ris, mode, dev, gather, loop,
+                              last_gathered, outs[last_slot], cap)
+        # per-kernel HIP-event timing on the kernels' stream, in a separate untimed pass of the same
+        # K steps (the per-launch events would otherwise sit inside the timed region)
+        ctx.timing(True)
+        ctx.timing_report()  # reset
+        for k in range(a.steps):
+            step(inflight=1)  # slot 0's context only: kernel durations without a neighbouring frame
+        drain()
+        kernels = ctx.timing_report()
+        ctx.timing(False)
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -572,6 +630,58 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / a.steps * 1e3
         value = seg_total * a.steps / elapsed / 1e6
+        line = {
+            "metric": "Mrays/sec (primary+refracted) at 1/2/4/8 MI355X; % of HBM-read roofline",
+            "value": round(value, 3),
+            "unit": "Mrays/s",
+            "n_gpus": pg_world,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "prewarm_s": a.prewarm_s,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True,
+            "scaling": a.scaling,
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic (deterministic ray grid; lenses built by the reference's preprocessing recipe)",
+            "full": a.full,
+            "config": {
+                "workload": f"{cfg.name}: {cfg.note}" + (f" (side {side})" if side != cfg.side else ""),
+                "image": f"{side}x{height}",
+                "primaries_per_gpu": n,
+                "ranks": {"world_size": pg_world, "backend": dist.get_backend() if world > 1 else None,
+                          "rccl_version": rccl, "launcher": os.environ.get(launch.LAUNCHED_BY) or
+                          ("external (WORLD_SIZE set)" if world > 1 else "single process"),
+                          "tiles_per_rank": tiles_per_rank, "tile": f"{frame.TILE}x{frame.TILE}"},
+                "segments_per_step": seg_total,
+                "patches": n_patch,
+                "parallelism": f"64x64 image tiles round-robin over {world} rank(s), {a.scaling} scaling"
+                               + (f", RCCL gather of every frame to rank 0 (overlapped with the next frames): "
+                                  f"{loop.bytes_per_rank / npad:.2f} B per primary ({a.gather})" if gather else ""),
+                "gather": ({"layout": a.gather, "bytes_per_rank_per_frame": loop.bytes_per_rank,
+                            "bytes_per_primary": round(loop.bytes_per_rank / npad, 3), "compact_capacity": cap or None,
+                            **verify["gather"],
+                            # the gather's rate against the frame's: below 1 it never stalls the tracing
+                            **({"gather_only_over_ms_per_step":
+                                (round(verify["gather"]["gather_only_ms_per_frame"] / ms_per_step, 4)
+                                 if verify["gather"].get("gather_only_ms_per_frame") else None)} if a.full else {})}
+                           if gather else None),
+                **({"frame_verified": verify["frame"]} if a.full else {}),
+                "pipeline": a.pipeline,
+                "frames_in_flight": F,
+                **({"slot_priority": {"mode": slot_prio, "slot0": top_prio}} if slot_prio else {}),
+                "hw_queues": {"GPU_MAX_HW_QUEUES_requested": hwq, "source": hwq_source,
+                              "streams": len(streams) + (1 if gather else 0),
+                              "ok": hwq >= len(streams) + (1 if gather else 0)},
+                "scan": "BVH-culled (bit-identical to brute force)" if a.accel == "bvh" else "brute force",
+                "numerics": "parity: bit-identical to the CPU oracle" if a.mode == "parity" else
+                            "fast: exact planar gate, Newton stage with FMA + approximate div/sqrt (SURVEY 8c fast gates)",
+                "preprocess_s": round(prep_s, 3),
+                "upload_and_bvh_s": round(upload_s, 3),
+                **({"outputs_dumped": str(a.dump_outputs)} if a.dump_outputs else {}),
+            },
+        }
+    if rank == 0 and a.full:
         base, cnt = (None, None)
         if a.cpu_baseline == "on" and world == 1:
             stride = a.cpu_sample_stride or {"cfg2": 4, "cfg3": 32, "cfg4": 8, "cfg5": 256}[cfg.name]
@@ -641,53 +751,7 @@ def main():
                 "frac": round(iss_all["valu_insts"] * launches * 2.0 / (SIMDS * PEAK_CLOCK_GHZ * 1e9 * ms_per_step * 1e-3), 4),
                 "valu_insts_per_step": round(iss_all["valu_insts"] * launches), "source": iss_all["source"],
                 "note": "VALU instructions per step (PMC) x 2 cycles / (1024 SIMDs x 2.4 GHz x ms_per_step)"}
-        line = {
-            "metric": "Mrays/sec (primary+refracted) at 1/2/4/8 MI355X; % of HBM-read roofline",
-            "value": round(value, 3),
-            "unit": "Mrays/s",
-            "n_gpus": pg_world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "prewarm_s": a.prewarm_s,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": a.scaling,
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic (deterministic ray grid; lenses built by the reference's preprocessing recipe)",
-            "config": {
-                "workload": f"{cfg.name}: {cfg.note}" + (f" (side {side})" if side != cfg.side else ""),
-                "image": f"{side}x{height}",
-                "primaries_per_gpu": n,
-                "ranks": {"world_size": pg_world, "backend": dist.get_backend() if world > 1 else None,
-                          "rccl_version": rccl, "launcher": os.environ.get(launch.LAUNCHED_BY) or
-                          ("external (WORLD_SIZE set)" if world > 1 else "single process"),
-                          "tiles_per_rank": tiles_per_rank, "tile": f"{frame.TILE}x{frame.TILE}"},
-                "segments_per_step": seg_total,
-                "patches": n_patch,
-                "parallelism": f"64x64 image tiles round-robin over {world} rank(s), {a.scaling} scaling"
-                               + (f", RCCL gather of every frame to rank 0 (overlapped with the next frames): "
-                                  f"{loop.bytes_per_rank / npad:.2f} B per primary ({a.gather})" if gather else ""),
-                "gather": ({"layout": a.gather, "bytes_per_rank_per_frame": loop.bytes_per_rank,
-                            "bytes_per_primary": round(loop.bytes_per_rank / npad, 3), "compact_capacity": cap or None,
-                            **verify["gather"],
-                            # the gather's rate against the frame's: below 1 it never stalls the tracing
-                            "gather_only_over_ms_per_step": (round(verify["gather"]["gather_only_ms_per_frame"] / ms_per_step, 4)
-                                                             if verify["gather"].get("gather_only_ms_per_frame") else None)}
-                           if gather else None),
-                "frame_verified": verify["frame"],
-                "pipeline": a.pipeline,
-                "frames_in_flight": F,
-                **({"slot_priority": {"mode": slot_prio, "slot0": top_prio}} if slot_prio else {}),
-                "hw_queues": {"GPU_MAX_HW_QUEUES_requested": hwq, "source": hwq_source,
-                              "streams": len(streams) + (1 if gather else 0),
-                              "ok": hwq >= len(streams) + (1 if gather else 0)},
-                "scan": "BVH-culled (bit-identical to brute force)" if a.accel == "bvh" else "brute force",
-                "numerics": "parity: bit-identical to the CPU oracle" if a.mode == "parity" else
-                            "fast: exact planar gate, Newton stage with FMA + approximate div/sqrt (SURVEY 8c fast gates)",
-                "preprocess_s": round(prep_s, 3),
-                "upload_and_bvh_s": round(upload_s, 3),
-            },
+        line.update({
             "roofline": {
                 **roof,
                 "traffic": traffic,
@@ -734,7 +798,8 @@ def main():
                 },
             },
             "cpu_baseline": base,
-        }
+        })
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

@@ -8,7 +8,7 @@ OUT=gpurun_out/config_sweep.jsonl
 for spec in "cfg2 fused" "cfg2 staged" "cfg3 fused" "cfg3 staged" "cfg4 fused" "cfg4 staged" "cfg5 fused" "cfg5 staged"; do
   set -- $spec
   for f in ${INFLIGHTS:-1 2 3}; do
-    timeout -k 10 240 python bench.py --config "$1" --pipeline "$2" --inflight "$f" --steps ${STEPS:-10} --warmup 2 \
+    timeout -k 10 240 python bench.py --full --config "$1" --pipeline "$2" --inflight "$f" --steps ${STEPS:-10} --warmup 2 \
       --cpu-baseline off > gpurun_out/sweep_one.log 2>&1
     rc=$?
     if [ $rc -ne 0 ]; then echo "{\"config\": \"$1\", \"pipeline\": \"$2\", \"inflight\": $f, \"rc\": $rc}" >> "$OUT"; [ $rc -ge 124 ] && exit $rc; continue; fi

@@ -30,11 +30,11 @@ for s in $STEPS; do
     pytest) step pytest_gpu 900 python -u -m pytest tests -x -v -m gpu -p no:cacheprovider --timeout 120 \
               --timeout-method thread ${PYTEST_K:+-k "$PYTEST_K"} ${PYTEST_ARGS:-} ;;
     smoke)  step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)  step bench 600 python bench.py ${BENCH_ARGS:-} ;;
+    bench)  step bench 600 python bench.py --full ${BENCH_ARGS:-} ;;
     # 2 ranks on the box's one GPU, launched by bench.py itself (no torch.distributed.run): gloo, every rank
     # on device 0 (RCCL refuses two ranks on one device).  Exercises the launcher, the tile deal and the
     # per-frame gather; not a scaling measurement.
-    rehearse2) step rehearse2 300 env BZR_BENCH_BACKEND=gloo BZR_BENCH_DEVICE=0 python bench.py --gpus 2 --steps 5 \
+    rehearse2) step rehearse2 300 env BZR_BENCH_BACKEND=gloo BZR_BENCH_DEVICE=0 python bench.py --full --gpus 2 --steps 5 \
               --warmup 2 --cpu-baseline off ${BENCH_ARGS:-} ;;
     prof)   step prof 1500 env TAG="${PROF_TAG:-prof}" BENCH="${PROF_BENCH:-}" WORKLOAD="${PROF_WORKLOAD:-}" \
               bash scripts/prof_run.sh ;;
@@ -48,7 +48,7 @@ for s in $STEPS; do
               grep -h '^{' "$OUT/cppbench.log" >> "$OUT/cppbench.jsonl" ;;
     # bench lines of the other configs on both pipelines (bench defaults, 100 timed steps): configs.jsonl
     configs) for c in cfg5 cfg3 cfg2; do for p in staged fused; do
-               step "configs_${c}_$p" 300 python bench.py --config $c --pipeline $p --steps 100 --cpu-baseline off &&
+               step "configs_${c}_$p" 300 python bench.py --full --config $c --pipeline $p --steps 100 --cpu-baseline off &&
                grep -h '^{' "$OUT/configs_${c}_$p.log" >> "$OUT/configs.jsonl"
              done; done ;;
     ab)     step ab 900 python scripts/ab.py ${AB_ARGS:-} ;;

@@ -11,7 +11,7 @@ for r in $(seq ${REPS:-2}); do
   for f in ${INFLIGHTS:-2}; do
     for g in ${GRIDS:-1:1024 2:1024}; do
       ng=${g%%:*}; rg=${g##*:}
-      BZR_NEWTON_GRIDX=$ng BZR_RESOLVE_BLOCKS=$rg timeout -k 10 240 python bench.py --config "${CONFIG:-cfg5}" \
+      BZR_NEWTON_GRIDX=$ng BZR_RESOLVE_BLOCKS=$rg timeout -k 10 240 python bench.py --full --config "${CONFIG:-cfg5}" \
         --pipeline "${PIPE:-staged}" --inflight "$f" --cpu-baseline off ${BENCH_ARGS:-} > gpurun_out/gridx_one.log 2>&1 || exit $?
       grep '^{' gpurun_out/gridx_one.log | tail -1 | python3 -c "
 import json, sys

@@ -138,3 +138,39 @@ def test_default_frames_in_flight_follow_the_rank_frame_size():
     assert slots(["--scaling", "weak"], 8) == 3               # weak: every rank keeps 4096²
     assert slots(["--config", "cfg5", "--pipeline", "staged"], 1) == 2
     assert slots(["--config", "cfg4", "--side", "2048", "--pipeline", "staged"], 1) == 6
+
+
+def test_dump_outputs_is_a_fixed_sample_in_float_arrays(tmp_path, monkeypatch):
+    """--dump-outputs: .npy files in float32 / float64, a seeded sample (the same from call to call) of a frame
+    larger than DUMP_MAX_PRIMARIES, the uint32 words exact in float64, the whole frame below the limit."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, str(REPO))
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_MAX_PRIMARIES", 100)
+    rng = np.random.default_rng(3)
+    n = 1000
+    rays = torch.from_numpy(rng.standard_normal((6, n)).astype(np.float32))
+    status = torch.from_numpy(rng.integers(0, 3, n).astype(np.int32))
+    seg = torch.from_numpy(np.full(n, -1, np.int32))  # the word 0xffffffff
+    got = []
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, True, (rays, status, seg), 0, 1)
+        got.append({p.stem: np.load(p) for p in sorted((tmp_path / d).glob("*.npy"))})
+    a, b = got
+    assert sorted(a) == ["index", "rays", "segments", "status"]
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    idx = a["index"].astype(np.int64)
+    assert a["index"].dtype == np.float64 and len(idx) == 100 and (np.diff(idx) > 0).all() and idx.max() < n
+    assert a["rays"].dtype == np.float32 and np.array_equal(a["rays"], rays.numpy()[:, idx])
+    assert a["status"].dtype == np.float64 and np.array_equal(a["status"], status.numpy()[idx])
+    assert (a["segments"] == 4294967295.0).all()
+
+    hits = torch.from_numpy(rng.standard_normal((13, 50)).astype(np.float32))
+    hits[11] = torch.from_numpy(np.full(50, 4, np.uint32).view(np.float32))
+    bench.dump_outputs(tmp_path / "c", False, hits, 1, 2)
+    c = {p.stem: np.load(p) for p in (tmp_path / "c").glob("*.npy")}
+    assert sorted(c) == ["hits_rank1", "index_rank1", "patch_rank1", "what_rank1"]
+    assert c["hits_rank1"].shape == (11, 50) and (c["what_rank1"] == 4.0).all() and len(c["index_rank1"]) == 50
