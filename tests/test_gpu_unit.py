@@ -78,6 +78,26 @@ def _heights(torch, n, gen, kind):
         c = torch.exp2(torch.empty(1, n, device="cuda").uniform_(-16.6, 0.0, generator=gen))
         c = c * (torch.randint(0, 2, (1, n), device="cuda", generator=gen).float() * 2 - 1)
         return torch.cat([h, c]).contiguous()
+    if kind == "edge":  # the whole proven range and its edges, every lane inside it (see _in_fast_range)
+        pick = torch.randint(0, 4, (3, n), device="cuda", generator=gen)
+        m = torch.empty(3, n, device="cuda").uniform_(1.0, 2.0, generator=gen).clamp_(max=2.0 - 2.0 ** -23)
+        m = torch.where(pick == 0, torch.ones_like(m), m)
+        m = torch.where(pick == 1, torch.full_like(m, 1.0 + 2.0 ** -23), m)
+        m = torch.where(pick == 2, torch.full_like(m, 2.0 - 2.0 ** -23), m)
+        e = torch.cat([torch.randint(-40, 41, (2, n), device="cuda", generator=gen),
+                       torch.randint(-20, 21, (1, n), device="cuda", generator=gen)])
+        m[2] = torch.where(e[2] == 20, torch.ones_like(m[2]), m[2])  # |cos| <= 2^20: that exponent holds 2^20 alone
+        s = torch.randint(0, 2, (3, n), device="cuda", generator=gen).float() * 2 - 1
+        v = torch.ldexp(s * m, e).float()
+        # a fixed block pairs the extremes: |h| just below 2^41 over 2^-20, and 2^-40 over 2^20 (both signs)
+        big, tiny = (2.0 - 2.0 ** -23) * 2.0 ** 40, 2.0 ** -40
+        sign = torch.tensor([1.0, -1.0], device="cuda").repeat(64)
+        sign2 = torch.tensor([1.0, 1.0, -1.0, -1.0], device="cuda").repeat(32)
+        v[0, 0:128], v[1, 0:128], v[2, 0:128] = big * sign, -big, 2.0 ** -20 * sign2
+        v[0, 128:256], v[1, 128:256], v[2, 128:256] = tiny * sign, -tiny, 2.0 ** 20 * sign2
+        v[0, 256:384], v[1, 256:384], v[2, 256:384] = big * sign, tiny, -(2.0 ** -20)
+        v[0, 384:512], v[1, 384:512], v[2, 384:512] = tiny, big * sign, 2.0 ** 20
+        return v.contiguous()
     # every exponent (the guard's fallback), zeros of both signs
     e = torch.randint(-150, 128, (3, n), device="cuda", generator=gen).float()
     m = torch.empty(3, n, device="cuda").uniform_(1.0, 2.0, generator=gen)
@@ -88,10 +108,22 @@ def _heights(torch, n, gen, kind):
     return v.contiguous()
 
 
-@pytest.mark.parametrize("kind", ["lens", "wide"])
+def _in_fast_range(torch, a):
+    """div_heights' test for the shared-reciprocal chain, per element, as patch_math.hpp states it: both heights'
+    biased exponents in 87..167 (2^-40 <= |h| < 2^41) and 2^-20 <= |cos| <= 2^20."""
+    e = (a[:2].view(torch.int32) >> 23) & 0xFF
+    c = a[2].abs()
+    return ((e - (127 - 40) >= 0) & (e - (127 - 40) <= 80)).all(dim=0) & (c >= 2.0 ** -20) & (c <= 2.0 ** 20)
+
+
+@pytest.mark.parametrize("kind", ["lens", "wide", "edge"])
 def test_shared_reciprocal_heights_are_bit_exact(bzr, ctx, kind):
     """newton_tail's din = hIn / cos, dout = hOut / cos (reference/bezierTriangle.cpp:132-133) with one shared
-    reciprocal (patch_math.hpp div_heights) == one correctly rounded division each == numpy float32."""
+    reciprocal (patch_math.hpp div_heights) == one correctly rounded division each == numpy float32.  The chain
+    runs only when a whole wave is in its proven range: "wide" almost never gives such a wave and "lens" stays far
+    from the range's edges, so "edge" puts every lane inside it (asserted before the launch: every wave takes the
+    chain), exponents uniform over the whole range, the mantissas 1, 1 + 2^-23, 2 - 2^-23 and random, the exact
+    bounds 2^-20 and 2^20 of |cos| and a block of lanes with the extreme quotients."""
     torch = pytest.importorskip("torch")
     gen = torch.Generator(device="cuda")
     gen.manual_seed(4321 + len(kind))
@@ -100,6 +132,10 @@ def test_shared_reciprocal_heights_are_bit_exact(bzr, ctx, kind):
     ctx.use_torch_stream()
     for rep in range(4):
         a = _heights(torch, n, gen, kind)
+        if kind == "edge":
+            assert bool(_in_fast_range(torch, a).all()) and not bool((a == 0).any())
+            assert bool((a[2].abs() == 2.0 ** -20).any()) and bool((a[2].abs() == 2.0 ** 20).any())
+            assert bool((a < 0).any(dim=1).all()) and bool((a > 0).any(dim=1).all())
         out = torch.empty(4, n, device="cuda")
         assert L.bzr_debug_div_heights(ctx.handle, ctypes.c_void_p(a.data_ptr()), n, ctypes.c_void_p(out.data_ptr())) == 0
         torch.cuda.synchronize()

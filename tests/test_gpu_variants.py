@@ -20,6 +20,10 @@ the default takes two) and with k_trace's per-lane walk (-DBZR_TRACE_BUNDLE=0, r
 checks, fused == staged == brute force (== the oracle on cfg2), including the incoherent cfg5 rays whose wide
 bundles take the per-lane node tests.
 
+Every variant also runs tests/test_gpu_stacked.py's "dup" mesh (cfg1's lens 20.5 times over: exact ties, 40 / 41 / 42
+gate passes beside 0 and 80..168), intersect and chain against the oracle: the staged overflow list is exactly the rays
+past 40 gate passes (stack4: at least those), so listed and overflowed rays share waves, chunks and pooled passes.
+
 The variant runs in a child process (BZR_LIBRARY selects the library; one process = one libbzr).
 """
 import json
@@ -57,6 +61,26 @@ for name, mode in (("fused", bzr.PIPELINE_FUSED), ("staged", bzr.PIPELINE_STAGED
     c = ctx.counters_report(); ctx.counters(False)
     out[f"cfg2_{name}_equal"] = all(np.array_equal(bits(g), bits(w)) for g, w in zip(got, want))
     out[f"cfg2_{name}_overflow_rays"] = c["overflow_rays"]
+# stacked cfg1 lens (tests/test_gpu_stacked.py's "dup"): 20 copies and the first half of a 21st, every hit an exact tie
+# the first copy wins; 40, 41 and 42 gate passes beside 0 and 80..168, so listed and overflowed rays share waves
+base = build_lens(orc.OMesh, CONFIGS["cfg1"].lenses[0]).bezier_patches()
+def moved(p, k):
+    q = p.copy()
+    q.view(np.uint32)[:, 16:19] += np.uint32(k * len(p))  # the neighbour words stay inside copy k
+    return q
+stk = np.ascontiguousarray(np.concatenate([moved(base, k) for k in range(20)] + [base[:len(base) // 2]]))
+dms = bzr.DeviceMesh(ctx, stk)
+rs = grid_rays(CONFIGS["cfg1"], side=32)
+want_hit, want_chain = bits(orc.intersect(stk, rs)), orc.trace_chain([stk], [1.3], rs)
+out["stack_gate_over_40"] = int((orc.planar_gate(stk, rs).sum(axis=1) > 40).sum())
+for name, mode in (("fused", bzr.PIPELINE_FUSED), ("staged", bzr.PIPELINE_STAGED), ("brute", bzr.ACCEL_NONE)):
+    ctx.counters(True); ctx.counters_report()
+    got = bits(bzr.intersect(ctx, dms, rs, mode=mode))
+    c = ctx.counters_report(); ctx.counters(False)
+    out[f"stack_{name}_equal"] = bool(np.array_equal(got, want_hit))
+    out[f"stack_{name}_overflow_rays"] = c["overflow_rays"]
+    got = bzr.trace_chain(ctx, [dms], [1.3], rs, mode=mode)
+    out[f"stack_{name}_chain_equal"] = all(np.array_equal(bits(g), bits(w)) for g, w in zip(got, want_chain))
 # cfg5: 301 056 patches, BezierMesh::intersect on 65 536 grid rays from the lens's middle rows
 cfg = CONFIGS["cfg5"]
 p5 = build_lens(bzr.TriMesh, cfg.lenses[0]).bezier_patches()
@@ -126,6 +150,8 @@ def test_tiny_stack_overflow_path_is_exact():
     # the tiny stack really overflowed on both pipelines (the brute-force scan has no stack)
     for k in ("cfg2_fused", "cfg2_staged", "cfg5_fused", "cfg5_staged"):
         assert out[f"{k}_overflow_rays"] > 0, (k, out)
+    # the stacked lens: the walk runs out of stack while the candidate list overflows too
+    assert out["stack_fused_overflow_rays"] > 0 and out["stack_staged_overflow_rays"] >= out["stack_gate_over_40"] > 0, out
     assert out["cfg5_hits"] > 10000
 
 
@@ -149,6 +175,12 @@ def test_trace_bundle_walk_is_exact(variant):
             assert v, (k, out)
     assert out["far_overflow_rays"] == out["far_count"]
     assert out["cfg2_fused_overflow_rays"] == 0
+    # the stacked lens: k_traverse's walk is the default one; k_trace's one-level-per-batch bundle walk (tracebundle)
+    # runs out of its 64-entry stack on two waves of the 21 coincident boxes (128 overflow rays measured), which take
+    # the in-order scan -- the same bits, checked above; the per-lane walk does not
+    assert out["stack_staged_overflow_rays"] == out["stack_gate_over_40"] > 0, out
+    if variant == "traceperlane":
+        assert out["stack_fused_overflow_rays"] == 0, out
     assert out["cfg5_hits"] > 10000
 
 
@@ -169,6 +201,7 @@ def test_pooled_passes_are_exact(variant):
         if k.endswith("_equal"):
             assert v, (k, out)
     assert out["cfg2_fused_overflow_rays"] == 0 and out["cfg5_fused_overflow_rays"] == 0
+    assert out["stack_fused_overflow_rays"] == 0 and out["stack_staged_overflow_rays"] == out["stack_gate_over_40"] > 0, out
     assert out["far_overflow_rays"] == out["far_count"]
 
 
@@ -188,6 +221,7 @@ def test_staged_pair_layout_extremes_are_exact(variant):
     for k, v in out.items():
         if k.endswith("_equal"):
             assert v, (k, out)
+    assert out["stack_fused_overflow_rays"] == 0 and out["stack_staged_overflow_rays"] == out["stack_gate_over_40"] > 0, out
     if variant == "dense1":
         assert out["cfg5_staged_lane_chunks"] == 0, out
     else:
