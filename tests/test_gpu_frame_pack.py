@@ -10,10 +10,10 @@ from bzr_amd import frame
 pytestmark = pytest.mark.gpu
 
 
-def frame_outputs(n, seed, p_survive=0.65):
-    """Synthetic chain outputs: status 0..2, segments 0..4 (survivors: segments >= 2 or status != 0)."""
+def frame_outputs(n, seed, p_survive=0.65, max_seg=4):
+    """Synthetic chain outputs: status 0..2, segments 0..max_seg (survivors: segments >= 2 or status != 0)."""
     g = np.random.default_rng(seed)
-    seg = g.integers(0, 5, n).astype(np.int32)
+    seg = g.integers(0, max_seg + 1, n).astype(np.int32)
     st = np.where(g.random(n) < p_survive, g.integers(1, 3, n), 0).astype(np.int32)
     st[seg == 0] = 0
     rays = g.standard_normal((6, n)).astype(np.float32)
@@ -63,6 +63,43 @@ def test_pack_compact_matches_torch(bzr, ctx, n, npad, cap_delta):
         assert np.array_equal(r[:, alive], rays.cpu().numpy()[:, alive])
         assert np.array_equal(s, (st.cpu().numpy() & 3).astype(np.uint32))
         assert np.array_equal(g, sg.cpu().numpy().astype(np.uint32))
+
+
+@pytest.mark.parametrize("layout", ["image", "rays", "compact"])
+def test_pack_segments_of_an_eight_lens_chain(bzr, ctx, layout):
+    """Segments 0..16 (a chain of eight lenses, the most bzr_trace_chain takes): the compact byte is
+    (status & 3) | segments << 2, up to 66, and the word layouts' bits 8..15 hold 16."""
+    n, npad = 5000, 8192
+    rays, st, sg = frame_outputs(n, 99, max_seg=16)
+    assert int(sg.max()) == 16 and len(torch.unique(sg)) == 17 and int((sg[st != 0] == 16).sum()) > 50
+    if layout == "compact":
+        count = int(frame.survivors(st, sg).sum())
+        cap = count + 3
+        want = torch.zeros(frame.compact_size(npad, cap), dtype=torch.float32, device="cuda")
+        got = torch.zeros_like(want)
+        frame.pack_compact(st, sg, rays, want, npad, cap)
+        bzr.pack_frame(ctx, "compact", rays, st, sg, got, npad, cap)
+        torch.cuda.synchronize()
+        nw = frame.compact_words(npad)
+        assert torch.equal(got[:nw].view(torch.uint8)[:n], want[:nw].view(torch.uint8)[:n])
+        assert int(got[:nw].view(torch.uint8)[:n].max()) == (16 << 2 | 2)
+        assert int(got[nw:nw + 1].view(torch.int32)) == count
+        r, s, g = frame.unpack_compact(got.cpu(), n, npad, cap, np.zeros((6, n), np.float32))
+        alive = frame.survivors(st, sg).cpu().numpy()
+        assert np.array_equal(r[:, alive], rays.cpu().numpy()[:, alive])
+        assert np.array_equal(s, st.cpu().numpy().astype(np.uint32))
+        assert np.array_equal(g, sg.cpu().numpy().astype(np.uint32))
+    else:
+        rows = frame.IMAGE_ROWS if layout == "image" else frame.PACKED_ROWS
+        want = torch.zeros((rows, npad), dtype=torch.float32, device="cuda")
+        got = torch.full((rows, npad), 7.0, dtype=torch.float32, device="cuda")
+        frame.pack(rays if layout == "rays" else None, st, sg, want)
+        bzr.pack_frame(ctx, layout, rays if layout == "rays" else None, st, sg, got, npad)
+        torch.cuda.synchronize()
+        assert torch.equal(got[:, :n].view(torch.int32), want[:, :n].view(torch.int32))
+        word = got[-1, :n].view(torch.int32)
+        assert torch.equal((word >> 8) & 0xFF, sg) and torch.equal(word & 0xFF, st)
+        assert bool((got[:, n:] == 7.0).all())
 
 
 def test_pack_compact_empty_frame(bzr, ctx):

@@ -24,6 +24,11 @@ Every variant also runs tests/test_gpu_stacked.py's "dup" mesh (cfg1's lens 20.5
 gate passes beside 0 and 80..168), intersect and chain against the oracle: the staged overflow list is exactly the rays
 past 40 gate passes (stack4: at least those), so listed and overflowed rays share waves, chunks and pooled passes.
 
+Every variant also runs tests/test_gpu_long_chains.py's eight-lens chain and, from tests/test_gpu_ray_edges.py, the batch
+with an origin of each tier-boundary class in every wave and the batch with NaN, infinite and scaled rays in every third
+lane, against the oracle on all three modes: the 4-entry stack overflows mid-walk beside a NaN lane, and the per-lane
+walk, the one-level walk and both staged pair layouts see those inputs.
+
 The variant runs in a child process (BZR_LIBRARY selects the library; one process = one libbzr).
 """
 import json
@@ -81,6 +86,32 @@ for name, mode in (("fused", bzr.PIPELINE_FUSED), ("staged", bzr.PIPELINE_STAGED
     out[f"stack_{name}_overflow_rays"] = c["overflow_rays"]
     got = bzr.trace_chain(ctx, [dms], [1.3], rs, mode=mode)
     out[f"stack_{name}_chain_equal"] = all(np.array_equal(bits(g), bits(w)) for g, w in zip(got, want_chain))
+# tests/test_gpu_long_chains.py's eight-lens chain, and tests/test_gpu_ray_edges.py's seven tier-boundary classes in every
+# wave and its garbage in every third lane (intersect and the one-lens chain on lens 0): the recipes are the tests' own
+sys.path.append(sys.argv[2] + "/tests")
+import test_gpu_long_chains as tl
+import test_gpu_ray_edges as te
+l8 = [tl.lens_patches(orc, k) for k in range(tl.N_LENS)]
+d8 = [bzr.DeviceMesh(ctx, p) for p in l8]
+s_near, s_max = te.tier_radii(bzr, l8[0])
+_, tier_mix, _ = te.tier_batches(l8[0], te.tier_classes(s_near, s_max))
+third, third_mask = te.poisoned(te.clean_batch(l8[0], s_near), "third")
+out["edges_beyond_s_max"] = int((np.abs(tier_mix[:3]).max(axis=0) > s_max).sum())
+out["edges_poisoned"] = int(third_mask.sum())
+jobs = [("long8", tl.chain_rays(), "chain8"), ("tiers", tier_mix, "intersect"), ("tiers", tier_mix, "chain1"),
+        ("third", third, "intersect"), ("third", third, "chain1")]
+for label, rr, op in jobs:
+    if op == "chain8":
+        want_e = [bits(a) for a in orc.trace_chain(l8, [1.3] * tl.N_LENS, rr)]
+        out["long8_full_length_rays"] = int((want_e[2] == 16).sum())
+    else:
+        want_e = te.run_orc(orc, l8, op, rr)[0]
+    for name, mode in (("fused", bzr.PIPELINE_FUSED), ("staged", bzr.PIPELINE_STAGED), ("brute", bzr.ACCEL_NONE)):
+        if op == "chain8":
+            got_e = [bits(a) for a in bzr.trace_chain(ctx, d8, [1.3] * tl.N_LENS, rr, mode=mode)]
+        else:
+            got_e = te.run_gpu(bzr, ctx, d8, op, rr, mode)
+        out[f"{label}_{op}_{name}_equal"] = not bool(te.differing(got_e, want_e).any())
 # cfg5: 301 056 patches, BezierMesh::intersect on 65 536 grid rays from the lens's middle rows
 cfg = CONFIGS["cfg5"]
 p5 = build_lens(bzr.TriMesh, cfg.lenses[0]).bezier_patches()
@@ -134,6 +165,14 @@ print(json.dumps(out))
 """
 
 
+def assert_edge_inputs_ran(out):
+    """The long chain, the tier boundaries and the garbage lanes were traced on all three modes, over the populations
+    tests/test_gpu_long_chains.py and tests/test_gpu_ray_edges.py assert."""
+    keys = [k for k in out if k.endswith("_equal") and k.split("_")[0] in ("long8", "tiers", "third")]
+    assert len(keys) == 15, keys
+    assert out["long8_full_length_rays"] >= 2000 and out["edges_beyond_s_max"] > 1000 and out["edges_poisoned"] > 2000, out
+
+
 @pytest.mark.gpu
 def test_tiny_stack_overflow_path_is_exact():
     lib = PKG / "lib" / "stack4" / "libbzr.so"
@@ -147,6 +186,7 @@ def test_tiny_stack_overflow_path_is_exact():
     for k, v in out.items():
         if k.endswith("_equal"):
             assert v, (k, out)
+    assert_edge_inputs_ran(out)
     # the tiny stack really overflowed on both pipelines (the brute-force scan has no stack)
     for k in ("cfg2_fused", "cfg2_staged", "cfg5_fused", "cfg5_staged"):
         assert out[f"{k}_overflow_rays"] > 0, (k, out)
@@ -173,6 +213,7 @@ def test_trace_bundle_walk_is_exact(variant):
     for k, v in out.items():
         if k.endswith("_equal"):
             assert v, (k, out)
+    assert_edge_inputs_ran(out)
     assert out["far_overflow_rays"] == out["far_count"]
     assert out["cfg2_fused_overflow_rays"] == 0
     # the stacked lens: k_traverse's walk is the default one; k_trace's one-level-per-batch bundle walk (tracebundle)
@@ -200,6 +241,7 @@ def test_pooled_passes_are_exact(variant):
     for k, v in out.items():
         if k.endswith("_equal"):
             assert v, (k, out)
+    assert_edge_inputs_ran(out)
     assert out["cfg2_fused_overflow_rays"] == 0 and out["cfg5_fused_overflow_rays"] == 0
     assert out["stack_fused_overflow_rays"] == 0 and out["stack_staged_overflow_rays"] == out["stack_gate_over_40"] > 0, out
     assert out["far_overflow_rays"] == out["far_count"]
@@ -221,6 +263,7 @@ def test_staged_pair_layout_extremes_are_exact(variant):
     for k, v in out.items():
         if k.endswith("_equal"):
             assert v, (k, out)
+    assert_edge_inputs_ran(out)
     assert out["stack_fused_overflow_rays"] == 0 and out["stack_staged_overflow_rays"] == out["stack_gate_over_40"] > 0, out
     if variant == "dense1":
         assert out["cfg5_staged_lane_chunks"] == 0, out
