@@ -141,16 +141,13 @@ __device__ __forceinline__ uint32_t deal_blocks(uint32_t b, uint32_t nblocks) {
 // meshes whose always list takes more than one 64-patch round (kAblockMin < n_always <= kAblockMax; others keep
 // the one-wave kernel).  Before the walk every wave's bundle is in LDS; the block's union bundle tests the
 // always-listed patches, one per thread, and keeps a mask in LDS.  1 (default): each wave gate-tests the
-// block-kept patches per lane; 2: each wave first re-tests the block-kept patches against its own bundle in
-// one (compacted) round; 0: off.  A dropped patch is one no ray of the block (so of the wave) can pass: the
-// candidates are unchanged.  cfg5 (131 always-listed patches): k_traverse 4.01 -> 3.84 ms per frame with 1,
-// 4.05 with 2 (profiles/r05_ab_traverse_ablock.jsonl).
-// 3 (A/B): the pre-test in a kernel of its own before k_traverse (k_always_mask: the same union bundle per 256 rays
-// and the same ballots, to a global mask), and k_traverse in one-wave blocks reading its 256-ray block's mask -- no
-// barriers in the walk kernel.
+// block-kept patches per lane; 0: off.  A dropped patch is one no ray of the block (so of the wave) can pass: the
+// candidates are unchanged.  cfg5 (131 always-listed patches): k_traverse 4.01 -> 3.84 ms per frame
+// (profiles/r05_ab_traverse_ablock.jsonl).
 #ifndef BZR_TRAV_ABLOCK
 #define BZR_TRAV_ABLOCK 1
 #endif
+static_assert(BZR_TRAV_ABLOCK == 0 || BZR_TRAV_ABLOCK == 1, "BZR_TRAV_ABLOCK: 0 or 1");
 #ifndef BZR_TRAV_BLOCK
 #define BZR_TRAV_BLOCK 64
 #endif
@@ -158,17 +155,6 @@ __device__ __forceinline__ uint32_t deal_blocks(uint32_t b, uint32_t nblocks) {
 #define BZR_ABLOCK_BLOCK 256
 #endif
 constexpr uint32_t kAblockMin = 64, kAblockMax = 1024, kAblockBlock = BZR_ABLOCK_BLOCK;  // threads per pre-testing block
-constexpr uint32_t kAmaskWords = kAblockMax / 64u;  // mask words per pre-testing block (BZR_TRAV_ABLOCK 3)
-// BZR_TRAV_ALDS (A/B knob, default 0): with the block pre-test (BZR_TRAV_ABLOCK 1), the block copies its kept
-// always-listed records (the 96 bytes the per-lane gate reads) into LDS once, so the waves' per-lane gates read
-// them there instead of waiting on one scalar load each (when at most kAldsMax are kept; else as before).
-// Same 64 VGPRs and 8 waves, 18 KB of LDS per block; cfg5 k_traverse 3.85 -> 3.93 ms per lone frame, bench lines
-// -0.8 % (profiles/r05_ab_traverse_alds.jsonl): the scalar loads hit the scalar cache; the copy and the records as
-// VGPR operands cost more.  Not kept.
-#ifndef BZR_TRAV_ALDS
-#define BZR_TRAV_ALDS 0
-#endif
-constexpr uint32_t kAldsMax = 128, kAldsQuads = 6;
 constexpr int kTravBlock = BZR_TRAV_BLOCK;
 // BZR_SLAB_FMA (default 1): the traversal slab test as fma(lo, inv, -s*inv) (mirrored by bvh.cpp slab_h).
 #ifndef BZR_SLAB_FMA
@@ -207,12 +193,6 @@ constexpr int kTravBlock = BZR_TRAV_BLOCK;
 constexpr uint32_t kWideSlots = BZR_TRAV_WIDE == 2 ? 64u : 16u;  // slots per node of the wide records
 // k_traverse's stack: a three-level batch (BZR_TRAV_WIDE 2) can push 64 entries at once
 constexpr int kTravStack = BZR_TRAV_WIDE == 2 ? 4 * kStack : kStack;
-// BZR_TRACE_BLEAF_PAIRS (A/B knob, default 0): k_trace's bundle walk gate-tests its queued leaves two at a time.
-// Measured at bench level: cfg4 -4.1 %, cfg2 -2.7 %, cfg5 fused -3.4 % (80 VGPRs with 5 spilled to scratch,
-// 49 SGPR spills; profiles/r04_bench_ab_trace_leaf_pairs.jsonl) -- unlike k_traverse, where pairs pay.
-#ifndef BZR_TRACE_BLEAF_PAIRS
-#define BZR_TRACE_BLEAF_PAIRS 0
-#endif
 // BZR_TRACE_WIDE (default 1, with BZR_TRACE_BUNDLE): k_trace's bundle walk over the same two-level records.
 #ifndef BZR_TRACE_WIDE
 #define BZR_TRACE_WIDE 1
@@ -233,21 +213,9 @@ constexpr int kTravStack = BZR_TRAV_WIDE == 2 ? 4 * kStack : kStack;
 #ifndef BZR_OVERFLOW_BLOCKS
 #define BZR_OVERFLOW_BLOCKS 2048u
 #endif
-// BZR_NEWTON_QUEUE (A/B knob, default 0): k_newton's waves take their dense chunks from a work counter (w.ctr[5],
-// one atomic per chunk and wave) instead of the static stride q, q + W, ...: a wave that drew cheap chunks takes
-// more, so the kernel ends when the work does, not when its most loaded wave does.
-#ifndef BZR_NEWTON_QUEUE
-#define BZR_NEWTON_QUEUE 0
-#endif
 // BZR_NEWTON_GATED (default 1): k_newton skips the planar gate its pairs already passed in k_traverse.
 #ifndef BZR_NEWTON_GATED
 #define BZR_NEWTON_GATED 1
-#endif
-// BZR_STAGED_AOS (default 0): k_traverse also writes each ray of the chunk as a 32-byte AoS record (ox oy oz dx
-// | dy dz), and the Newton / resolve kernels read a pair's ray from it -- one 32-byte sector instead of six
-// SoA rows whose 128-byte lines serve few of a bucket's rays.
-#ifndef BZR_STAGED_AOS
-#define BZR_STAGED_AOS 0
 #endif
 // BZR_DENSE_MIN (default 16): the staged pair layout.  A patch bucket's pairs fill whole 64-pair chunks of
 // that one patch (dense chunks: patch-uniform Newton passes, every lane busy); its last, partial chunk is
@@ -415,21 +383,6 @@ __device__ __forceinline__ void load_ray(const float *__restrict__ r, uint32_t n
   s = mk(r[i], r[(size_t)n + i], r[(size_t)2 * n + i]);
   d = mk(r[(size_t)3 * n + i], r[(size_t)4 * n + i], r[(size_t)5 * n + i]);
 }
-// A pair's ray in the staged path: the chunk's 32-byte AoS copy (BZR_STAGED_AOS) or the SoA rows.
-__device__ __forceinline__ void load_pair_ray(const float4 *__restrict__ aos, const float *__restrict__ r, uint32_t ld,
-                                              uint32_t off, uint32_t i, f3 &s, f3 &d) {
-#if BZR_STAGED_AOS
-  (void)r;
-  (void)ld;
-  (void)off;
-  const float4 a = aos[2u * i], b = aos[2u * i + 1u];
-  s = mk(a.x, a.y, a.z);
-  d = mk(a.w, b.x, b.y);
-#else
-  (void)aos;
-  load_ray(r, ld, off + i, s, d);
-#endif
-}
 __device__ __forceinline__ void store_ray(float *__restrict__ r, uint32_t n, uint32_t i, f3 s, f3 d) {
   r[i] = s.x;
   r[(size_t)n + i] = s.y;
@@ -437,13 +390,6 @@ __device__ __forceinline__ void store_ray(float *__restrict__ r, uint32_t n, uin
   r[(size_t)3 * n + i] = d.x;
   r[(size_t)4 * n + i] = d.y;
   r[(size_t)5 * n + i] = d.z;
-}
-
-// Diagnostic builds (BZR_DIAG_WALK2 / BZR_DIAG_NEWTON2): a copy of a value the compiler cannot see through,
-// so a phase evaluated twice is not folded -- the marginal cost of its arithmetic, with identical results.
-__device__ __forceinline__ f3 opaque(f3 v) {
-  asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z));
-  return v;
 }
 
 // ------------------------------------------------------------ culled path
@@ -531,9 +477,6 @@ __device__ __forceinline__ void node_children(const bzr_host::Bvh4Node *nodes, c
     const float4 hi = make_float4(__uint_as_float(na[12 + c]), __uint_as_float(nb[c]), __uint_as_float(nb[4 + c]), 0.0f);
     ch[c] = nb[8 + c];
     hit[c] = act & (ch[c] != bzr_host::kEmptyChild) & slab(lo, hi, s, sinv, inv);
-#if BZR_DIAG_WALK2
-    hit[c] &= slab(lo, hi, s, opaque(sinv), opaque(inv));
-#endif
   }
 }
 
@@ -557,17 +500,8 @@ __device__ __forceinline__ void node_children(const bzr_host::Bvh4Node *nodes, c
 //   k_finish    winner -> BezierIntersection / refraction (overflow rays: their winner re-evaluated)
 // For one ray (t order, patch, slot) orders like (t, scanned patch index): the atomicMin winner is the
 // reference's strict-< in-order winner (record()).
-// BZR_ROWS_DIRECT: where the Newton stage writes an intersect segment's hits (RowOut::rows non-null: the caller's
-// hit rows, see record_row) instead of the list slots.
-struct RowOut {
-  float *rows = nullptr;        // [13][ld] hit rows, ray i at off + i
-  uint32_t ld = 0, off = 0;
-  uint32_t *count = nullptr;    // Work::count (kDirty)
-  uint32_t *dirty = nullptr;    // [chunk] rays whose row two improving pairs may have written in either order
-  uint32_t *ndirty = nullptr;   // Work::ctr + 4
-};
 struct Work {
-  uint32_t *ctr;     // [0] follow count, [1] overflow count, [2] rays traced, [3] pairs listed, [4] dirty rows
+  uint32_t *ctr;     // [0] follow count, [1] overflow count, [2] rays traced, [3] pairs listed
   uint32_t *hist;    // [nb + 1] pair counts per patch (hist[nb] = 0); 256 bytes after ctr
   unsigned long long *offs;  // [nb + 1] exclusive prefix of bucket_split(hist); offs[nb] = the totals
   uint32_t *cand;    // [kMaxCand][n]
@@ -579,15 +513,9 @@ struct Work {
                      // region; a follow request adds its side << 30 to the patch word
   uint32_t *fol;     // [cap] follow requests: pair indices
   uint32_t *ovf;     // [n]
-  uint32_t *dirty;   // [n] BZR_ROWS_DIRECT: rays whose hit row k_finish_ovf evaluates again
-  unsigned long long *amask;  // BZR_TRAV_ABLOCK 3: [n / 256][kAmaskWords] always-listed patches kept per 256 rays
-  RowOut ro;         // BZR_ROWS_DIRECT (intersect segments): the Newton stage's direct row writes
-  float4 *aos;       // [2 * chunk] the chunk's rays as 32-byte records (BZR_STAGED_AOS)
   void *cub;
   size_t cub_bytes;
   uint32_t cap;      // kMaxCand * chunk
-  uint32_t hbase;    // BZR_TRAV_HYBRID: pair index of the in-wave follow requests' records (j * n + ray past it)
-  uint32_t hyb_t;    // BZR_TRAV_HYBRID: lanes a leaf's gate must pass for its Newton pass to run in the walking wave
 };
 constexpr uint32_t kSlotWords = 12;  // t, point, cos, bary, normal, source patch
 
@@ -672,55 +600,6 @@ __device__ __forceinline__ void record(float *__restrict__ slot, uint32_t n, uin
 #endif
 }
 
-// BZR_ROWS_DIRECT (A/B knob, default 0): an intersect segment's Newton stage writes a pair's hit straight into the caller's
-// hit rows instead of its 48-byte list slot, and k_finish only writes the misses' rows -- it no longer reads a slot
-// and rewrites every hit row (cfg5: k_finish 822 -> ~260 MB per 8 M-ray chunk).  Ordering: a pair whose key improves
-// the ray's (the returning atomicMin) writes its 13 words write-through (sc1: the line leaves the XCD's L2 for the
-// memory side, MI355X_MICROARCH.md visibility table), waits for them (vmcnt(0)) and reads the key again at the
-// coherence point (a second atomicMin).  Still its own key: any later improvement's atomic comes after that read, so
-// its stores land after these and its row is the final one.  Changed: another pair improved meanwhile and the two
-// writes may have landed in either order, so the ray is marked dirty (kDirty in its count, once, and listed) and
-// k_finish_ovf evaluates its final winner again from the key (patch b, cThis, then the follow side's neighbour with
-// cNone: the sequence that produced the key, same bits).  Misses are written by k_finish, overflow rays by
-// k_finish_ovf, as before.  Measured (profiles/r06_ab_rows_direct.jsonl; all GPU tests bit-identical with it on):
-// 0.43 % of cfg5's rays dirty; lone frames cfg5 -0.3 % (k_finish 1.17 -> 0.64 ms per frame, but k_newton +0.25 and
-// k_resolve +0.13: the drain stalls the VALU-bound waves), cfg3 +3 %; at bench level, frames in flight, cfg5 6 758 ->
-// 6 517 Mrays/s and cfg3 9 695 -> 9 433 -- the write-through stores cost more than k_finish's HBM bytes save.  Checking
-// a row at the lane's next step instead (its stores long done): 3.4x the dirty rows and slower.  Not kept.
-#ifndef BZR_ROWS_DIRECT
-#define BZR_ROWS_DIRECT 0
-#endif
-constexpr uint32_t kDirty = 0x10000u;  // count flag (above kOverflow): the hit row is evaluated again
-__device__ __forceinline__ void store_wt(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// Record a lane's hit (wr) -- ray `ray`'s list slot j, candidate patch b, from patch src -- into its row.
-__device__ __forceinline__ void row_step(const RowOut &ro, unsigned long long *key, bool wr, uint32_t ray, uint32_t j,
-                                         uint32_t b, const Hit &h, uint32_t src) {
-  wr = wr && h.t < FLT_MAX;
-  const unsigned long long kn = ((unsigned long long)t_order(h.t) << 32) | (b << 6) | j;
-  if (wr) wr = kn < atomicMin(&key[ray], kn);
-  if (!__any(wr)) return;
-  if (wr) {
-    const size_t ld = ro.ld, i = (size_t)ro.off + ray;
-    float *r = ro.rows;
-    store_wt(r + i, h.t);
-    store_wt(r + ld + i, h.point.x);
-    store_wt(r + 2 * ld + i, h.point.y);
-    store_wt(r + 3 * ld + i, h.point.z);
-    store_wt(r + 4 * ld + i, h.cs);
-    store_wt(r + 5 * ld + i, h.bary.x);
-    store_wt(r + 6 * ld + i, h.bary.y);
-    store_wt(r + 7 * ld + i, h.bary.z);
-    store_wt(r + 8 * ld + i, h.normal.x);
-    store_wt(r + 9 * ld + i, h.normal.y);
-    store_wt(r + 10 * ld + i, h.normal.z);
-    store_wt(r + 11 * ld + i, __uint_as_float(kIntersect));
-    store_wt(r + 12 * ld + i, __uint_as_float(src));
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the rows have reached the memory side
-  if (wr && atomicMin(&key[ray], kn) != kn && !(atomicOr(&ro.count[ray], kDirty) & kDirty))
-    ro.dirty[atomicAdd(ro.ndirty, 1u)] = ray;
-}
-
 // Word group g of a 64-byte leaf record (planar record, patch index in the last word): q0..q3 of the gate.
 __device__ __forceinline__ float4 leaf_q(const u32x16 &r, int g) {
   return make_float4(__uint_as_float(r[4 * g]), __uint_as_float(r[4 * g + 1]), __uint_as_float(r[4 * g + 2]),
@@ -761,28 +640,6 @@ __device__ __forceinline__ bool always_gate_rec(const u32x16 &r, const u32x8 &wq
 __device__ __forceinline__ bool always_gate(const float4 *always, uint32_t k, bool act, f3 s, f3 d, uint32_t &patch) {
   const u32x16 r = *((const cu32x16 *)(uintptr_t)(always + (size_t)kAlwaysQuads * k));
   const u32x8 wq = *((const cu32x8 *)(uintptr_t)(always + (size_t)kAlwaysQuads * k + 4));
-  return always_gate_rec(r, wq, act, s, d, patch);
-}
-// The same gate from a record staged in LDS (BZR_TRAV_ALDS): quads 0-3 the leaf record, 4-5 the wedge words.
-__device__ __forceinline__ bool always_gate_lds(const float4 *q, bool act, f3 s, f3 d, uint32_t &patch) {
-  u32x16 r;
-  u32x8 wq;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float4 v = q[k];
-    r[4 * k] = __float_as_uint(v.x);
-    r[4 * k + 1] = __float_as_uint(v.y);
-    r[4 * k + 2] = __float_as_uint(v.z);
-    r[4 * k + 3] = __float_as_uint(v.w);
-  }
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const float4 v = q[4 + k];
-    wq[4 * k] = __float_as_uint(v.x);
-    wq[4 * k + 1] = __float_as_uint(v.y);
-    wq[4 * k + 2] = __float_as_uint(v.z);
-    wq[4 * k + 3] = __float_as_uint(v.w);
-  }
   return always_gate_rec(r, wq, act, s, d, patch);
 }
 
@@ -1118,132 +975,21 @@ __device__ __forceinline__ bool bundle_gate_keep(const float *B, float4 q0, floa
 #else
 #define BZR_PHASE(k)
 #endif
+// BZR_TRAV_PRIO (A/B knob, default 0): the whole k_traverse wave at s_setprio(N), ahead of the other frame's
+// k_newton waves that share its CUs when frames are in flight.
+#ifndef BZR_TRAV_PRIO
+#define BZR_TRAV_PRIO 0
+#endif
 // The lanes whose gate of patch b passed list it as their next candidate (while the list has room; a lane
 // past kMaxCand overflows to the full scan).  (Counting the listing lanes into b's histogram word right here --
 // b is wave-uniform, so one atomic without return per wave -- and ranking the pairs in k_place instead of
 // after the walk: k_traverse -1.6 % on cfg5 and -9 % on cfg3, but k_place's grouped ranking atomics cost more
 // than that, cfg3 frames +7.6 %; profiles/r04_ab_rank_late.jsonl.)
-// BZR_RANK_EARLY (A/B knob, default 0): each listed group (the lanes whose gate of the wave-uniform patch b
-// passed) takes its ranks in b's bucket right away -- one returning atomic by its first lane -- instead of the
-// ranking pass after the walk (the candidates' reload, a ballot loop per list slot grouping the lanes by patch,
-// the atomics' round trip at the end of the wave: 13 % of a cfg5 wave, 22 % of a cfg3 one).  1: the ranks are
-// stored at the next listing (one group pending, its base in a VGPR across the walk); 2: stored at once (the
-// wave waits for each atomic).  A ray that later overflows its list keeps its ranked places; k_place fills them
-// with idle (kNoPair) records.  Both lose: cfg5 k_traverse 3.88 -> 4.45 (1) / 4.20 (2) ms per frame, cfg3 0.173
-// -> 0.201 / 0.187 (profiles/r05_ab_rank_early.jsonl): one atomic round trip per listing instead of one per four
-// list slots, and with 1 the pending base spills VGPRs at the 8-wave budget.
-#ifndef BZR_RANK_EARLY
-#define BZR_RANK_EARLY 0
-#endif
-constexpr uint32_t kRankEntries = 64;  // BZR_RANK_EARLY 3: listings recorded per wave
-struct RankPend {  // the last listed group of the wave (BZR_RANK_EARLY 1); the wave's listings (3)
-  uint32_t base = 0u;           // its first place in the bucket (valid in its first lane)
-  unsigned long long g = 0ull;  // its lanes
-  uint32_t *ent = nullptr;      // 3: LDS [kRankEntries] patch, then [kRankEntries] lane masks (two words each)
-  uint32_t ne = 0u;             // 3: listings so far (uniform; past kRankEntries the wave ranks the old way)
-};
-// Store the pending group's ranks: a lane's slot is its list count - 1 (its count changes only at a listing,
-// after this; the overflow flag keeps the low bits).
-__device__ __forceinline__ void rank_flush(RankPend &pr, const Work &w, uint32_t n, uint32_t i, uint32_t cnt) {
-  if (pr.g) {
-    const uint32_t bs = __builtin_amdgcn_readlane(pr.base, (uint32_t)__builtin_ctzll(pr.g));
-    if (lane_bit64(pr.g, threadIdx.x & 63u))
-      w.rank[(size_t)((cnt & (kOverflow - 1u)) - 1u) * n + i] = bs + lanes_below(pr.g);
-    pr.g = 0ull;
-  }
-}
-// BZR_TRAV_HYBRID (A/B knob, default 0 = round 5's k_traverse): in-wave Newton passes for dense leaves (VERDICT r05
-// item 1).  A leaf whose exact planar gate passes for at least Work::hyb_t of the wave's lanes (runtime threshold,
-// BZR_HYBRID_T; 0 = never) is not listed: its patch and lane mask go to the wave's LDS entries (up to kHybEntries;
-// more are listed as before), and once the walk and the always list are done the wave runs one patch-uniform pass
-// per entry with the record in SGPRs (k_trace's site, k_newton's arithmetic: kGated, the lanes passed this gate).
-// A lane keeps its best in-wave (t order, patch) key; it becomes the ray's initial key, with list slot kHybSlot
-// holding its record, so the staged pairs' atomicMin and k_finish treat it like any listed pair's hit.  A follow-side
-// result becomes a follow request for k_resolve on a list slot of its own (cand word kCandFollow: no pair for the
-// ranking or k_place; its pair record at hbase + j n + ray), or, when the list is full, is retried in the wave.
-// Sparse leaves go to the buckets as before.  Same candidates, same keys: the schedule never changes a bit.
-// Measured (cfg5 8192^2 staged, lone frames, scripts/ab.py; profiles/r06_ab_hybrid.jsonl): the in-wave passes
-// cost what the same pairs cost in k_newton (T = 48 with the walk at priority 3: k_traverse +2.02 ms, k_newton
-// -2.0 ms per frame) -- they do not hide behind the walk, which is issue-bound, not latency-bound -- and the
-// compiled-in code alone costs the walk 7.6 % (3.90 -> 4.19 ms at T = 0: 90 SGPR spills, 3 VGPRs to scratch at the
-// 8-wave budget); T = 32 / 16: 13.5 / 17.1 ms per frame against 11.2.  Not kept; same bits in every variant.
-#ifndef BZR_TRAV_HYBRID
-#define BZR_TRAV_HYBRID 0
-#endif
-// BZR_TRAV_PRIO (A/B knob, default 0): the walk at s_setprio(N) -- with BZR_TRAV_HYBRID the in-wave passes back at 0
-// (as k_trace's BZR_TRACE_PRIO); without it the whole k_traverse wave, ahead of the other frame's k_newton waves
-// that share its CUs when frames are in flight.
-#ifndef BZR_TRAV_PRIO
-#define BZR_TRAV_PRIO 0
-#endif
-#ifndef BZR_HYBRID_T_DEFAULT
-#define BZR_HYBRID_T_DEFAULT 32
-#endif
-static_assert(!BZR_TRAV_HYBRID || BZR_RANK_EARLY == 0, "BZR_TRAV_HYBRID ranks after the walk");
-constexpr uint32_t kHybEntries = 16;
-constexpr uint32_t kListCap = BZR_TRAV_HYBRID ? kMaxCand - 1u : kMaxCand;  // listed slots per ray
-constexpr uint32_t kHybSlot = kMaxCand - 1u;                               // the in-wave winner's list slot
-constexpr uint32_t kCandFollow = 0x80000000u;                             // cand word of an in-wave follow request
-struct HybEntries {  // the wave's dense leaves (LDS)
-  uint32_t *b = nullptr;             // [kHybEntries] patch
-  unsigned long long *g = nullptr;   // [kHybEntries] lanes whose gate passed
-  uint32_t ne = 0u;                  // entries so far (uniform)
-  uint32_t t = 0u;                   // the threshold (Work::hyb_t)
-};
-
 __device__ __forceinline__ void list_candidate(bool pass, uint32_t b, const Work &w, uint32_t n, uint32_t i,
-                                               uint32_t &cnt, RankPend &pr) {
-  const bool lst = pass && cnt < kListCap;
-#if BZR_RANK_EARLY == 1
-  rank_flush(pr, w, n, i, cnt);
-#endif
-#if BZR_RANK_EARLY == 3
-  const unsigned long long g = __ballot(lst);
-  if (g) {  // record the listing (patch, lanes) in the wave's LDS; ranked after the walk
-    if (pr.ne < kRankEntries && (threadIdx.x & 63u) == 0u) {
-      pr.ent[pr.ne] = b;
-      reinterpret_cast<unsigned long long *>(pr.ent + kRankEntries)[pr.ne] = g;
-    }
-    ++pr.ne;
-  }
-#elif BZR_RANK_EARLY
-  const unsigned long long g = __ballot(lst);
-  if (g) {
-    const uint32_t leader = (uint32_t)__builtin_ctzll(g);
-    uint32_t base = 0u;
-    if ((threadIdx.x & 63u) == leader) base = atomicAdd(&w.hist[b], (uint32_t)__popcll(g));
-#if BZR_RANK_EARLY == 1
-    pr.base = base;
-    pr.g = g;
-#elif BZR_RANK_EARLY == 3
-    (void)base;
-#else  // 2: wait for the atomic right here (no state across the walk)
-    const uint32_t bs = __builtin_amdgcn_readlane(base, leader);
-    if (lst) w.rank[(size_t)cnt * n + i] = bs + lanes_below(g);
-#endif
-  }
-#endif
+                                               uint32_t &cnt) {
+  const bool lst = pass && cnt < kMaxCand;
   if (lst) w.cand[(size_t)cnt * n + i] = b;
-  if (pass) cnt = cnt < kListCap ? cnt + 1 : (cnt | kOverflow);
-}
-// A leaf's gate result: a dense leaf (BZR_TRAV_HYBRID) becomes one of the wave's entries, any other is listed.
-__device__ __forceinline__ void take_leaf(bool pass, uint32_t b, const Work &w, uint32_t n, uint32_t i, uint32_t &cnt,
-                                          RankPend &pr, HybEntries &hy) {
-#if BZR_TRAV_HYBRID
-  const unsigned long long g = __ballot(pass);
-  if (g == 0ull) return;
-  if (hy.ne < kHybEntries && (uint32_t)__popcll(g) >= hy.t && hy.t != 0u) {
-    if ((threadIdx.x & 63u) == 0u) {
-      hy.b[hy.ne] = b;
-      hy.g[hy.ne] = g;
-    }
-    ++hy.ne;
-    return;
-  }
-#else
-  (void)hy;
-#endif
-  list_candidate(pass, b, w, n, i, cnt, pr);
+  if (pass) cnt = cnt < kMaxCand ? cnt + 1 : (cnt | kOverflow);
 }
 // Candidate search.  `alive` (optional): a ray is traced iff alive[off + i] != BZR_RR_NONE.
 // One wave's 64 rays i (lane l of the wave holds ray i); `stk` is the wave's LDS stack.
@@ -1251,9 +997,8 @@ template <int kBlk, int kAblock, bool kFast>
 __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__restrict__ rays, uint32_t ld,
                                               uint32_t off, const uint32_t *__restrict__ alive, uint32_t n,
                                               const Work &w, unsigned long long *counters, uint32_t i, uint32_t *stk,
-                                              float *bl, uint32_t *pend, uint32_t *raw, HybEntries hy,
-                                              float *ubl = nullptr, unsigned long long *akeep = nullptr,
-                                              uint32_t *rk = nullptr, float4 *arec = nullptr) {
+                                              float *bl, uint32_t *pend, uint32_t *raw, float *ubl = nullptr,
+                                              unsigned long long *akeep = nullptr) {
 #if BZR_TRAV_PHASES
   unsigned long long ph_acc[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull}, ph_t = __builtin_amdgcn_s_memtime();
   uint32_t ph_cur = 0;
@@ -1265,15 +1010,7 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
   bool active = i < n && (alive == nullptr || alive[off + i] != BZR_RR_NONE);
   f3 s = mk(0.0f, 0.0f, 0.0f), d = s;
   if (i < n) load_ray(rays, ld, off + i, s, d);
-#if BZR_STAGED_AOS
-  if (i < n) {
-    w.aos[2u * i] = make_float4(s.x, s.y, s.z, d.x);
-    w.aos[2u * i + 1u] = make_float4(d.y, d.z, 0.0f, 0.0f);
-  }
-#endif
   uint32_t cnt = 0;
-  RankPend rpend;  // BZR_RANK_EARLY: the last listed group's ranks, stored at the next listing (1); listings (3)
-  rpend.ent = rk;
   // gate-region boxes hold for ray origins within s_max (bvh.cpp); farther rays take the full scan
   if (active && !(fmaxf(fmaxf(fabsf(s.x), fabsf(s.y)), fabsf(s.z)) <= m.s_max)) {
     cnt |= kOverflow;
@@ -1315,9 +1052,8 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
 #if BZR_TRAV_PRETEST
   uint32_t nraw = 0;  // leaves queued in raw, not yet pre-tested
 #endif
-  // the always list's block pre-test (every thread of the block gets here: no early exit above); with
-  // BZR_TRAV_ABLOCK 3 k_always_mask did it and akeep points at this ray block's mask
-  if constexpr (kAblock == 1 || kAblock == 2) {
+  // the always list's block pre-test (every thread of the block gets here: no early exit above)
+  if constexpr (kAblock != 0) {
     if (!walk) bundle_setup_dpp(active, s, d, bl, threadIdx.x & 63u);  // (an empty wave's bundle is the identity)
     __syncthreads();
     if (threadIdx.x < 13u) {  // the union over the block's waves with rays (bl - wave * kBundleWords: wave 0's)
@@ -1340,24 +1076,6 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
       if ((threadIdx.x & 63u) == 0u) akeep[(base + threadIdx.x) >> 6] = km;
     }
     __syncthreads();
-#if BZR_TRAV_ALDS
-    if constexpr (kAblock == 1) {  // the kept records into LDS, in list order (word, then bit)
-      const uint32_t words = (m.n_always + 63u) / 64u;
-      uint32_t total = 0;
-      for (uint32_t q = 0; q < words; ++q) total += (uint32_t)__popcll(akeep[q]);
-      if (total <= kAldsMax) {
-        for (uint32_t e = threadIdx.x; e < total * kAldsQuads; e += kBlk) {
-          const uint32_t j = e / kAldsQuads, qd = e - j * kAldsQuads;
-          uint32_t q = 0, before = 0;
-          while (before + (uint32_t)__popcll(akeep[q]) <= j) before += (uint32_t)__popcll(akeep[q++]);
-          unsigned long long bits = akeep[q];
-          for (uint32_t k = before; k < j; ++k) bits &= bits - 1ull;  // drop the kept patches before j
-          arec[e] = m.always[(size_t)kAlwaysQuads * (q * 64u + (uint32_t)__builtin_ctzll(bits)) + qd];
-        }
-      }
-      __syncthreads();
-    }
-#endif
   }
   while (bwalk) {
     if (pi < npend) {
@@ -1376,11 +1094,11 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
         c_leaves += two ? 2u : 1u;
         c_gates += (two ? 2u : 1u) * (uint32_t)__popcll(__ballot(active));
       }
-      take_leaf(active & planar_gate(leaf_q(r0, 0), leaf_q(r0, 1), leaf_q(r0, 2), leaf_q(r0, 3), s, d), r0[15], w,
-                     n, i, cnt, rpend, hy);
+      list_candidate(active & planar_gate(leaf_q(r0, 0), leaf_q(r0, 1), leaf_q(r0, 2), leaf_q(r0, 3), s, d),
+                     r0[15], w, n, i, cnt);
       if (two)
-        take_leaf(active & planar_gate(leaf_q(r1, 0), leaf_q(r1, 1), leaf_q(r1, 2), leaf_q(r1, 3), s, d), r1[15],
-                       w, n, i, cnt, rpend, hy);
+        list_candidate(active & planar_gate(leaf_q(r1, 0), leaf_q(r1, 1), leaf_q(r1, 2), leaf_q(r1, 3), s, d),
+                       r1[15], w, n, i, cnt);
 #else
       const uint32_t slot = __builtin_amdgcn_readfirstlane(pend[pi]);
       ++pi;
@@ -1389,8 +1107,8 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
         ++c_leaves;
         c_gates += (uint32_t)__popcll(__ballot(active));
       }
-      take_leaf(active & planar_gate(leaf_q(r, 0), leaf_q(r, 1), leaf_q(r, 2), leaf_q(r, 3), s, d), r[15], w, n,
-                     i, cnt, rpend, hy);
+      list_candidate(active & planar_gate(leaf_q(r, 0), leaf_q(r, 1), leaf_q(r, 2), leaf_q(r, 3), s, d),
+                     r[15], w, n, i, cnt);
 #endif
       continue;
     }
@@ -1482,7 +1200,7 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
           ++c_leaves;
           c_gates += (uint32_t)__popcll(hm);
         }
-        take_leaf(hit[c] & planar_gate(q0, q1, q2, q3, s, d), r[15], w, n, i, cnt, rpend, hy);
+        list_candidate(hit[c] & planar_gate(q0, q1, q2, q3, s, d), r[15], w, n, i, cnt);
       } else {
         if (next != 0xFFFFFFFFu) {
           if (sp < kTravStack) stk[sp++] = next;
@@ -1501,47 +1219,7 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
 #endif
       bundle_to_lds(active, s, d, bl, threadIdx.x & 63u);
     if constexpr (kAblock != 0) {
-      const uint32_t lane = threadIdx.x & 63u, words = (m.n_always + 63u) / 64u;
-      if constexpr (kAblock == 2) {
-      // the block-kept patches compacted into the wave's (now idle) pend buffer, re-tested with its own bundle
-      uint32_t total = 0;
-      for (uint32_t q = 0; q < words; ++q) {
-        const unsigned long long kq = akeep[q];
-        if (lane_bit64(kq, lane)) pend[total + lanes_below(kq)] = q * 64u + lane;
-        total += (uint32_t)__popcll(kq);
-      }
-      __builtin_amdgcn_wave_barrier();
-      for (uint32_t r0 = 0; r0 < total; r0 += 64u) {
-        const uint32_t k = r0 + lane;
-        const uint32_t id = k < total ? pend[k] : 0u;
-        unsigned long long am = __ballot(k < total && always_bundle_keep(m.always, id, m.n_always, bl));
-        for (; am; am &= am - 1ull) {
-          uint32_t b;
-          if (counters) {
-            ++c_leaves;
-            c_gates += (uint32_t)__popcll(__ballot(active));
-          }
-          const uint32_t patch = __builtin_amdgcn_readfirstlane(pend[r0 + __builtin_ctzll(am)]);
-          const bool pass = always_gate(m.always, patch, active, s, d, b);
-          take_leaf(pass, b, w, n, i, cnt, rpend, hy);
-        }
-      }
-      } else {
-#if BZR_TRAV_ALDS
-      uint32_t total = 0;
-      for (uint32_t q = 0; q < words; ++q) total += (uint32_t)__popcll(akeep[q]);
-      if (total <= kAldsMax) {
-        for (uint32_t j = 0; j < total; ++j) {
-          uint32_t b;
-          if (counters) {
-            ++c_leaves;
-            c_gates += (uint32_t)__popcll(__ballot(active));
-          }
-          const bool pass = always_gate_lds(arec + (size_t)kAldsQuads * j, active, s, d, b);
-          take_leaf(pass, b, w, n, i, cnt, rpend, hy);
-        }
-      } else
-#endif
+      const uint32_t words = (m.n_always + 63u) / 64u;
       for (uint32_t q = 0; q < words; ++q) {
         for (unsigned long long am = akeep[q]; am; am &= am - 1ull) {
           uint32_t b;
@@ -1550,9 +1228,8 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
             c_gates += (uint32_t)__popcll(__ballot(active));
           }
           const bool pass = always_gate(m.always, q * 64u + __builtin_ctzll(am), active, s, d, b);
-          take_leaf(pass, b, w, n, i, cnt, rpend, hy);
+          list_candidate(pass, b, w, n, i, cnt);
         }
-      }
       }
     } else
     for (uint32_t ab = 0; ab * 64u < m.n_always; ++ab) {
@@ -1564,142 +1241,24 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
           c_gates += (uint32_t)__popcll(__ballot(active));
         }
         const bool pass = always_gate(m.always, ab * 64u + __builtin_ctzll(am), active, s, d, b);
-        take_leaf(pass, b, w, n, i, cnt, rpend, hy);
+        list_candidate(pass, b, w, n, i, cnt);
       }
     }
 
   }
-  // BZR_TRAV_HYBRID: the wave's dense leaves, one patch-uniform Newton pass each (k_trace's site).  A lane's best
-  // (t order, patch) key becomes the ray's initial key (list slot kHybSlot holds its record); a follow-side result
-  // becomes a follow request on a list slot of its own, or is retried here when the list is full.
-  unsigned long long hbest = ~0ull;
-  uint32_t h_pairs = 0u, h_rounds = 0u;  // work counters (uniform)
-#if BZR_TRAV_HYBRID
-  if (hy.ne) {
-    BZR_PHASE(3)
-#if BZR_TRAV_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint32_t e = 0; e < hy.ne; ++e) {
-      const uint32_t b = __builtin_amdgcn_readfirstlane(hy.b[e]);
-      const unsigned long long g0 = hy.g[e];
-      const unsigned long long g = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(g0 >> 32)) << 32) |
-                                   (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)g0);
-      const bool run = lane_bit64(g, lane) && !(cnt & kOverflow);  // (an overflowed lane takes the full scan)
-      if (counters) {
-        h_pairs += (uint32_t)__popcll(__ballot(run));
-        ++h_rounds;
-      }
-      const auto pa = uniform_patch(m.full, b);
-      uint32_t what = kNone;
-      if (run) {
-        const Hit h = patch_intersect<BZR_NEWTON_GATED != 0, kFast>(pa, s, d, false);
-        what = h.what;
-        if (h.what == kIntersect && h.t < FLT_MAX) {
-          const unsigned long long k = ((unsigned long long)t_order(h.t) << 32) | (b << 6) | kHybSlot;
-          if (k < hbest) {
-            hbest = k;
-            write_slot(w.slot, n, i, kHybSlot, h, b);
-          }
-        }
-      }
-      const bool fol = run && what <= kFollow2;
-      if (!__any(fol)) continue;
-      const bool room = fol && cnt < kListCap;
-      const unsigned long long rm = __ballot(room);
-      if (rm) {  // follow requests for k_resolve: pair record (ray | j << 26, b | side << 30) at hbase + j n + ray
-        uint32_t base = 0u;
-        if (lane == 0u) base = atomicAdd(&w.ctr[0], (uint32_t)__popcll(rm));
-        base = __builtin_amdgcn_readfirstlane(base);
-        if (room) {
-          const uint32_t p = w.hbase + cnt * n + i;
-          w.pairs[p] = make_uint2(i | (cnt << 26), b | (what << 30));
-          w.cand[(size_t)cnt * n + i] = kCandFollow;
-          w.fol[base + lanes_below(rm)] = p;
-          ++cnt;
-        }
-      }
-      for (uint32_t side = 0; side < 3u; ++side) {  // list full: the retry runs here (cNone, ranked at b)
-        const bool fl = fol && !room && what == side;
-        if (!__any(fl)) continue;
-        const uint32_t nb = __float_as_uint(pa.r[rec::kNeigh + side]);
-        const auto pn = uniform_patch(m.full, nb);
-        if (counters) {
-          h_pairs += (uint32_t)__popcll(__ballot(fl));
-          ++h_rounds;
-        }
-        if (fl) {
-          const Hit h = patch_intersect<false, kFast>(pn, s, d, true);
-          if (h.what == kIntersect && h.t < FLT_MAX) {
-            const unsigned long long k = ((unsigned long long)t_order(h.t) << 32) | (b << 6) | kHybSlot;
-            if (k < hbest) {
-              hbest = k;
-              write_slot(w.slot, n, i, kHybSlot, h, nb);
-            }
-          }
-        }
-      }
-    }
-  }
-#endif
   if (counters) {  // rays traced (one atomic per wave: on one address, so only with counters on)
     const unsigned long long traced = __ballot(i < n && (alive == nullptr || alive[off + i] != BZR_RR_NONE));
     if ((threadIdx.x & 63u) == 0 && traced) atomicAdd(&w.ctr[2], (uint32_t)__popcll(traced));
     // walk work (bzr_ctx_counters node_visits / leaf_fetches / gate_tests), spread over the replicas
     const uint32_t lane = threadIdx.x & 63u, rep = (i >> 6) % kCounterReplicas;
-#if BZR_TRAV_HYBRID  // and the in-wave Newton passes' pairs and passes
-    const uint32_t v = lane == 0u ? c_nodes : lane == 1u ? c_leaves : lane == 2u ? c_gates : lane == 3u ? h_pairs : h_rounds;
-    const uint32_t which = lane == 0u ? BZR_COUNTER_NODE_VISITS : lane == 1u ? BZR_COUNTER_LEAF_FETCHES
-                           : lane == 2u ? BZR_COUNTER_GATE_TESTS : lane == 3u ? BZR_COUNTER_PAIRS : BZR_COUNTER_NEWTON_ROUNDS;
-    if (!BZR_TRAV_PHASES && lane < 5u && v) atomicAdd(&counters[(size_t)rep * BZR_COUNTER_COUNT + which], (unsigned long long)v);
-#else
-    (void)h_pairs;
-    (void)h_rounds;
     const uint32_t v = lane == 0u ? c_nodes : (lane == 1u ? c_leaves : c_gates);
     const uint32_t which = lane == 0u ? BZR_COUNTER_NODE_VISITS : (lane == 1u ? BZR_COUNTER_LEAF_FETCHES : BZR_COUNTER_GATE_TESTS);
     if (!BZR_TRAV_PHASES && lane < 3u && v) atomicAdd(&counters[(size_t)rep * BZR_COUNTER_COUNT + which], (unsigned long long)v);
-#endif
   }
-#if BZR_RANK_EARLY == 1
-  rank_flush(rpend, w, n, i, cnt);
-#endif
   if (i >= n) return;
   w.count[i] = cnt;
-#if BZR_TRAV_HYBRID
-  w.key[i] = cnt > kMaxCand ? ~0ull : hbest;
-#else
-  (void)hbest;
   w.key[i] = ~0ull;
-#endif
   if (cnt > kMaxCand) w.ovf[atomicAdd(&w.ctr[1], 1u)] = i;
-#if BZR_RANK_EARLY == 3
-  const uint32_t lane = threadIdx.x & 63u;
-  BZR_PHASE(5)
-  if (rpend.ne <= kRankEntries) {
-    // every recorded listing's atomic at once (lane e: listing e, its lanes minus the overflow rays, which rank
-    // nothing: the full scan takes them), one wait, then each listing's lanes store base + their rank in it --
-    // a lane's j-th listing is its list slot j
-    const unsigned long long ovf = __ballot(cnt > kMaxCand);
-    const uint32_t ne = rpend.ne;
-    const unsigned long long *eg = reinterpret_cast<const unsigned long long *>(rk + kRankEntries);
-    uint32_t base = 0u;
-    if (lane < ne) {
-      const unsigned long long g = eg[lane] & ~ovf;
-      if (g) base = atomicAdd(&w.hist[rk[lane]], (uint32_t)__popcll(g));
-    }
-    uint32_t slot = 0u;
-    for (uint32_t e = 0; e < ne; ++e) {
-      const unsigned long long g0 = eg[e];
-      const unsigned long long g = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(g0 >> 32)) << 32) |
-                                   (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)g0);
-      const uint32_t bs = __builtin_amdgcn_readlane(base, e);
-      if (lane_bit64(g & ~ovf, lane)) w.rank[(size_t)slot * n + i] = bs + lanes_below(g & ~ovf);
-      slot += lane_bit64(g, lane) ? 1u : 0u;
-    }
-  } else {
-#endif
-#if !BZR_RANK_EARLY || BZR_RANK_EARLY == 3
   // Rank of each (ray, patch) pair within its patch bucket.  Neighbouring rays mostly share
   // patches: the lanes naming the same patch form a group (found with ballots, no memory traffic),
   // each group's first lane adds the group size -- all groups in one atomic instruction -- and the
@@ -1717,11 +1276,10 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
     uint32_t b[kRankBatch], leader[kRankBatch], below[kRankBatch], base[kRankBatch];
 #pragma unroll
     for (int k = 0; k < kRankBatch; ++k)
-      b[k] = j0 + k < listed ? w.cand[(size_t)(j0 + k) * n + i] : (BZR_TRAV_HYBRID ? kCandFollow : 0u);
+      b[k] = j0 + k < listed ? w.cand[(size_t)(j0 + k) * n + i] : 0u;
 #pragma unroll
     for (int k = 0; k < kRankBatch; ++k) {
-      // (an in-wave follow request is no pair: BZR_TRAV_HYBRID)
-      const bool pend = BZR_TRAV_HYBRID ? !(b[k] & kCandFollow) : j0 + k < listed;
+      const bool pend = j0 + k < listed;
       unsigned long long group = 0ull;
       bool todo = pend;
       for (;;) {
@@ -1743,16 +1301,9 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
 #pragma unroll
     for (int k = 0; k < kRankBatch; ++k) {
       const uint32_t bs = __shfl(base[k], (int)leader[k], 64);
-      if (BZR_TRAV_HYBRID ? !(b[k] & kCandFollow) : j0 + k < listed) w.rank[(size_t)(j0 + k) * n + i] = bs + below[k];
+      if (j0 + k < listed) w.rank[(size_t)(j0 + k) * n + i] = bs + below[k];
     }
   }
-#else
-  const uint32_t lane = threadIdx.x & 63u;
-  (void)lane;
-#endif
-#if BZR_RANK_EARLY == 3
-  }
-#endif
 #if BZR_TRAV_PHASES
   BZR_PHASE(0)
   if (counters && lane < 6u) {
@@ -1809,76 +1360,15 @@ __global__ __launch_bounds__(kBlk) BZR_TRAV_ATTR void k_traverse(MeshView m, con
   uint32_t *wraw = nullptr;
 #endif
   const uint32_t b = deal_blocks<BZR_TRAV_XCD>(blockIdx.x, gridDim.x);
-#if BZR_RANK_EARLY == 3
-  __shared__ __attribute__((aligned(8))) uint32_t rk[kBlk / 64][3 * kRankEntries];  // the wave's listings (patch, lane mask)
-  uint32_t *wrk = rk[threadIdx.x >> 6];
-#else
-  uint32_t *wrk = nullptr;
-#endif
-  HybEntries hy;  // the wave's dense leaves (BZR_TRAV_HYBRID)
-#if BZR_TRAV_HYBRID
-  __shared__ uint32_t hyb_b[kBlk / 64][kHybEntries];
-  __shared__ unsigned long long hyb_g[kBlk / 64][kHybEntries];
-  hy.b = hyb_b[threadIdx.x >> 6];
-  hy.g = hyb_g[threadIdx.x >> 6];
-  hy.t = w.hyb_t;
-#endif
-  if constexpr (kAblock == 3) {  // the mask of this wave's 256-ray block (k_always_mask)
-    traverse_rays<kBlk, 3, kFast>(m, rays, ld, off, alive, n, w, counters, b * kBlk + threadIdx.x, stack[threadIdx.x >> 6],
-                                  bundle[threadIdx.x >> 6], wpend, wraw, hy, nullptr,
-                                  w.amask + (size_t)((b * kBlk) / kAblockBlock) * kAmaskWords, wrk);
-  } else if constexpr (kAblock != 0) {
+  if constexpr (kAblock != 0) {
     static_assert(!kAblock || BZR_TRAV_BUNDLE, "BZR_TRAV_ABLOCK needs the bundle walk");
     __shared__ float ubl[16];                                  // the block's union bundle (words 0..12)
     __shared__ unsigned long long akeep[kAblockMax / 64u];     // block-kept always-listed patches
-#if BZR_TRAV_ALDS
-    __shared__ float4 arec[kAldsMax * kAldsQuads];             // their records (BZR_TRAV_ALDS)
-#else
-    float4 *arec = nullptr;
-#endif
     traverse_rays<kBlk, kAblock, kFast>(m, rays, ld, off, alive, n, w, counters, b * kBlk + threadIdx.x,
-                                        stack[threadIdx.x >> 6], bundle[threadIdx.x >> 6], wpend, wraw, hy, ubl, akeep,
-                                        wrk, arec);
+                                        stack[threadIdx.x >> 6], bundle[threadIdx.x >> 6], wpend, wraw, ubl, akeep);
   } else {
     traverse_rays<kBlk, 0, kFast>(m, rays, ld, off, alive, n, w, counters, b * kBlk + threadIdx.x, stack[threadIdx.x >> 6],
-                                  bundle[threadIdx.x >> 6], wpend, wraw, hy, nullptr, nullptr, wrk);
-  }
-}
-
-
-// BZR_TRAV_ABLOCK 3: the always list's block pre-test as a kernel of its own.  Block b (kAblockBlock rays) forms
-// its waves' ray bundles (bundle_setup_dpp) and their union, ballots always_bundle_keep for every always-listed
-// patch and writes the kept mask to amask[b].  The union is over every ray of the block that is traced (a superset
-// of the walk's active rays: rays beyond s_max take the full scan there), so a dropped patch is one no traced ray of
-// the block can pass -- the candidates are unchanged.
-__global__ __launch_bounds__(kAblockBlock) void k_always_mask(MeshView m, const float *__restrict__ rays, uint32_t ld,
-                                                              uint32_t off, const uint32_t *__restrict__ alive, uint32_t n,
-                                                              unsigned long long *__restrict__ amask) {
-  __shared__ float bundle[kAblockBlock / 64][kBundleWords];
-  __shared__ float ubl[16];
-  const uint32_t i = blockIdx.x * kAblockBlock + threadIdx.x, lane = threadIdx.x & 63u;
-  const bool active = i < n && (alive == nullptr || alive[off + i] != BZR_RR_NONE);
-  f3 s = mk(0.0f, 0.0f, 0.0f), d = s;
-  if (i < n) load_ray(rays, ld, off + i, s, d);
-  bundle_setup_dpp(active, s, d, bundle[threadIdx.x >> 6], lane);
-  __syncthreads();
-  if (threadIdx.x < 13u) {  // the union over the block's waves with rays (as traverse_rays' block pre-test)
-    const uint32_t k = threadIdx.x;
-    float v = k < 12u ? ((k % 6u) < 3u ? __builtin_inff() : -__builtin_inff()) : 1.0f;
-    bool any = false;
-    for (uint32_t q = 0; q < kAblockBlock / 64u; ++q) {
-      const float *bq = bundle[q];
-      if (!(bq[0] <= bq[3])) continue;  // no traced ray in wave q
-      any = true;
-      const float x = bq[k];
-      v = k == 12u ? fminf(v, x) : ((k % 6u) < 3u ? fminf(v, x) : fmaxf(v, x));
-    }
-    ubl[k] = (k == 12u && !any) ? 0.0f : v;
-  }
-  __syncthreads();
-  for (uint32_t base = 0; base < m.n_always; base += kAblockBlock) {
-    const unsigned long long km = __ballot(always_bundle_keep(m.always, base + threadIdx.x, m.n_always, ubl));
-    if (lane == 0u) amask[(size_t)blockIdx.x * kAmaskWords + ((base + threadIdx.x) >> 6)] = km;
+                                  bundle[threadIdx.x >> 6], wpend, wraw);
   }
 }
 
@@ -1918,17 +1408,8 @@ __global__ __launch_bounds__(kBlock) void k_place(uint32_t n, uint32_t nb, Work 
   }
   if (t >= n) return;
   const uint32_t c0 = w.count[t];
-#if BZR_RANK_EARLY == 1 || BZR_RANK_EARLY == 2
-  // an overflow ray (the full scan takes it) had its listed pairs ranked in k_traverse: their places get idle
-  // kNoPair records (its patch in .y, as the dense chunks' padding), and the pair counter drops them
-  const bool idle = c0 > kMaxCand;
-  const uint32_t cnt = c0 & (kOverflow - 1u);
-  if (idle && cnt && pair_count) atomicSub(pair_count, cnt);
-#else
   if (c0 > kMaxCand) return;  // (an overflow ray's list is not ranked: the full scan takes it)
-  const bool idle = false;
   const uint32_t cnt = c0;
-#endif
   if (cnt == 0) return;
   const unsigned long long tot = w.offs[nb];
   const uint32_t sparse0 = static_cast<uint32_t>(tot >> 32) * 64u;  // the sparse region's first pair
@@ -1944,19 +1425,15 @@ __global__ __launch_bounds__(kBlock) void k_place(uint32_t n, uint32_t nb, Work 
     }
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k) {
-      const uint32_t bb = BZR_TRAV_HYBRID ? b[k] & ~kCandFollow : b[k];  // (BZR_TRAV_HYBRID: follow requests place no pair)
-      o0[k] = w.offs[bb];
-      o1[k] = w.offs[bb + 1u];
+      o0[k] = w.offs[b[k]];
+      o1[k] = w.offs[b[k] + 1u];
     }
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k) {
       if (j0 + k >= cnt) break;
-#if BZR_TRAV_HYBRID
-      if (b[k] & kCandFollow) continue;
-#endif
       const uint32_t dbase = static_cast<uint32_t>(o0[k] >> 32), dlen = 64u * (static_cast<uint32_t>(o1[k] >> 32) - dbase);
       const uint32_t p = r[k] < dlen ? dbase * 64u + r[k] : sparse0 + static_cast<uint32_t>(o0[k]) + (r[k] - dlen);
-      w.pairs[p] = make_uint2(idle ? kNoPair : t | ((j0 + k) << 26), b[k]);
+      w.pairs[p] = make_uint2(t | ((j0 + k) << 26), b[k]);
     }
   }
 }
@@ -1984,21 +1461,13 @@ __device__ __forceinline__ void flush_follow(uint32_t *buf, uint32_t &nf, uint32
 #define BZR_NEWTON_WPE 8
 #endif
 #define BZR_NEWTON_ATTR __attribute__((amdgpu_waves_per_eu(BZR_NEWTON_WPE)))
-// BZR_NEWTON_PREFETCH (A/B knob, default 0): k_newton loads a chunk's rays while the previous chunk computes
-// (and the pair records two chunks ahead) instead of at the chunk's start.  61 instead of 54 VGPRs, still 8
-// waves: cfg5 k_newton 4.32 -> 4.26 ms per frame, frames within noise; cfg3 frames -3 % (noisy)
-// (profiles/r05_ab_newton_prefetch.jsonl): the eight waves per SIMD already hide the gathers.  Not kept.
-#ifndef BZR_NEWTON_PREFETCH
-#define BZR_NEWTON_PREFETCH 0
-#endif
 template <bool kFast>
 __global__ __launch_bounds__(kBlock) BZR_NEWTON_ATTR void k_newton(const float *__restrict__ full,
                                                    const unsigned long long *__restrict__ total,
                                                    uint2 *__restrict__ pairs, const float *__restrict__ rays,
                                                    uint32_t ld, uint32_t off, uint32_t n, float *__restrict__ slot,
                                                    unsigned long long *__restrict__ key,
-                                                   uint32_t *__restrict__ fol, uint32_t *__restrict__ nfol,
-                                                   const float4 *__restrict__ aos, RowOut ro) {
+                                                   uint32_t *__restrict__ fol, uint32_t *__restrict__ nfol) {
   __shared__ uint32_t fbuf[kWaves][kFolBuf];
   const uint32_t wv = threadIdx.x >> 6;
   uint32_t nf = 0;  // staged follow requests of this wave (uniform)
@@ -2013,58 +1482,17 @@ __global__ __launch_bounds__(kBlock) BZR_NEWTON_ATTR void k_newton(const float *
   q = __builtin_amdgcn_readfirstlane(q);
   uint2 pr = make_uint2(kNoPair, 0u);
   if (q < D) pr = pairs[q * 64u + lane];
-#if BZR_NEWTON_PREFETCH
-  // two-deep pipeline: this chunk's rays were loaded during the previous chunk, the next chunk's pair records
-  // two chunks ahead
-  f3 ns = mk(0.0f, 0.0f, 0.0f), nd = ns;
-  if (q < D && pr.x != kNoPair) load_pair_ray(aos, rays, ld, off, pr.x & kRayMask, ns, nd);
-  uint2 pr2 = make_uint2(kNoPair, 0u);
-  if (q + W < D) pr2 = pairs[(q + W) * 64u + lane];
-#endif
-#if BZR_NEWTON_QUEUE && !BZR_NEWTON_PREFETCH
-  for (uint32_t qnext = 0; q < D; q = qnext) {
-#else
   for (; q < D; q += W) {
-#endif
     const uint32_t p = q * 64u + lane;
     const bool todo = pr.x != kNoPair;
     const uint32_t ray = pr.x & kRayMask, j = pr.x >> 26;
     const uint32_t b = __builtin_amdgcn_readfirstlane(pr.y);  // the chunk's patch (lane 0 is a real pair)
-#if BZR_NEWTON_PREFETCH
-    const f3 s = ns, d = nd;
-    const uint32_t qn = q + W;
-    pr = pr2;  // the next chunk's pairs (loaded a chunk ago): its rays now, its successor's pairs too
-    if (qn < D && pr.x != kNoPair) load_pair_ray(aos, rays, ld, off, pr.x & kRayMask, ns, nd);
-    if (qn + W < D) pr2 = pairs[(qn + W) * 64u + lane];
-#else
     f3 s = mk(0.0f, 0.0f, 0.0f), d = s;
-    if (todo) load_pair_ray(aos, rays, ld, off, ray, s, d);  // pairs of one patch: mostly neighbouring rays
-#if BZR_NEWTON_QUEUE
-    uint32_t qn = 0;  // the wave's next chunk: the W first chunks went to the waves by id, the rest from the counter
-    if (lane == 0u) qn = atomicAdd(nfol + 5, 1u);
-    qn = __builtin_amdgcn_readfirstlane(qn) + W;
-#else
+    if (todo) load_ray(rays, ld, off + ray, s, d);  // pairs of one patch: mostly neighbouring rays
     const uint32_t qn = q + W;
-#endif
     if (qn < D) pr = pairs[qn * 64u + lane];  // prefetch the next chunk's pair records
-#endif
-#if BZR_NEWTON_QUEUE && !BZR_NEWTON_PREFETCH
-    qnext = qn;
-#endif
     bool is_fol = false;
     const auto pa = uniform_patch(full, b);
-#if BZR_ROWS_DIRECT
-    if (ro.rows) {
-      Hit h = no_hit();
-      // every pair passed this patch's planar gate in k_traverse (same arithmetic, same record values)
-      if (todo) h = patch_intersect<BZR_NEWTON_GATED != 0, kFast>(pa, s, d, false);
-      row_step(ro, key, todo && h.what == kIntersect, ray, j, b, h, b);
-      is_fol = todo && h.what <= kFollow2;
-      if (is_fol) reinterpret_cast<uint32_t *>(pairs)[2u * p + 1u] = b | (h.what << 30);  // the side, for k_resolve
-    } else
-#else
-    (void)ro;
-#endif
     if (todo) {
       const Hit h = patch_intersect<BZR_NEWTON_GATED != 0, kFast>(pa, s, d, false);
       if (h.what == kIntersect) record(slot, n, ray, j, b, h, b, &key[ray]);
@@ -2090,8 +1518,7 @@ __global__ __launch_bounds__(kBlock) void k_newton_lane(const float *__restrict_
                                                         uint2 *__restrict__ pairs, const float *__restrict__ rays,
                                                         uint32_t ld, uint32_t off, uint32_t n, float *__restrict__ slot,
                                                         unsigned long long *__restrict__ key,
-                                                        uint32_t *__restrict__ fol, uint32_t *__restrict__ nfol,
-                                                        const float4 *__restrict__ aos, RowOut ro) {
+                                                        uint32_t *__restrict__ fol, uint32_t *__restrict__ nfol) {
   const unsigned long long tot = *total;
   const uint32_t base = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(tot >> 32)) * 64u;
   const uint32_t S = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(tot));
@@ -2100,35 +1527,16 @@ __global__ __launch_bounds__(kBlock) void k_newton_lane(const float *__restrict_
     const uint32_t p = base + c * 64u + lane;
     bool is_fol = false;
     const uint2 pr = c * 64u + lane < S ? pairs[p] : make_uint2(kNoPair, 0u);
-#if BZR_ROWS_DIRECT
-    const bool todo = pr.x != kNoPair;
-    const uint32_t ray = pr.x & kRayMask, j = pr.x >> 26, b = pr.y;
-    Hit h = no_hit();
-    if (todo) {
-      f3 s, d;
-      load_pair_ray(aos, rays, ld, off, ray, s, d);
-      const Patch pa = load_patch(full + (size_t)rec::kWords * b);
-      h = patch_intersect<BZR_NEWTON_GATED != 0, kFast>(pa, s, d, false);
-    }
-    if (ro.rows) row_step(ro, key, todo && h.what == kIntersect, ray, j, b, h, b);
-    else if (todo && h.what == kIntersect) record(slot, n, ray, j, b, h, b, &key[ray]);
-    if (todo) {
-      is_fol = h.what <= kFollow2;
-      if (is_fol) reinterpret_cast<uint32_t *>(pairs)[2u * p + 1u] = b | (h.what << 30);
-    }
-#else
-    (void)ro;
     if (pr.x != kNoPair) {
       const uint32_t ray = pr.x & kRayMask, j = pr.x >> 26, b = pr.y;
       f3 s, d;
-      load_pair_ray(aos, rays, ld, off, ray, s, d);
+      load_ray(rays, ld, off + ray, s, d);
       const Patch pa = load_patch(full + (size_t)rec::kWords * b);
       const Hit h = patch_intersect<BZR_NEWTON_GATED != 0, kFast>(pa, s, d, false);
       if (h.what == kIntersect) record(slot, n, ray, j, b, h, b, &key[ray]);
       is_fol = h.what <= kFollow2;
       if (is_fol) reinterpret_cast<uint32_t *>(pairs)[2u * p + 1u] = b | (h.what << 30);
     }
-#endif
     const unsigned long long fm = __ballot(is_fol);
     if (fm) {
       uint32_t fb = 0;
@@ -2176,18 +1584,14 @@ template <int kMode, bool kFast>
 __global__ __launch_bounds__(kBlock) BZR_FINISH_ATTR void k_finish(MeshView m, const float *rays, uint32_t ld, uint32_t off, uint32_t n,
                                                    Work w, Out o) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  if (blockIdx.x == 0 && threadIdx.x < 6) w.ctr[threadIdx.x] = 0u;  // last reader of the counters this segment
+  if (blockIdx.x == 0 && threadIdx.x < 4) w.ctr[threadIdx.x] = 0u;  // last reader of the counters this segment
   if (i >= n) return;
   const uint32_t gi = off + i;
   if constexpr (kMode == kModeHits && BZR_FINISH_NORAY) {
     // count and key together (testing the count first would make the key and slot loads wait on it)
     const uint32_t c = w.count[i];
     const unsigned long long k = w.key[i];
-    if (c > kMaxCand) return;  // an overflow ray or a dirty row (BZR_ROWS_DIRECT): k_finish_ovf emitted it
-    if (BZR_ROWS_DIRECT && w.ro.rows) {  // BZR_ROWS_DIRECT: a hit's row is written already; a miss's here
-      if (k == ~0ull) store_hit(o.hits, ld, gi, no_hit(), 0xFFFFFFFFu);
-      return;
-    }
+    if (c > kMaxCand) return;  // an overflow ray: k_finish_ovf emitted it
     Hit h = no_hit();
     uint32_t patch = 0xFFFFFFFFu;
     if (k != ~0ull) {
@@ -2249,19 +1653,6 @@ __global__ __launch_bounds__(kBlock) void k_finish_ovf(MeshView m, const float *
     if (k != ~0ull) h = evaluate_patch<kFast>(m, static_cast<uint32_t>(k), s, d, patch);
     store_hit(o.hits, ld, gi, h, patch);
   }
-#if BZR_ROWS_DIRECT
-  // BZR_ROWS_DIRECT's dirty rows: the final key's pair (candidate b, list slot j) evaluated again -- b with cThis,
-  // then its follow side's neighbour with cNone, as k_newton / k_resolve did
-  const uint32_t D = __builtin_amdgcn_readfirstlane(w.ctr[4]);
-  for (uint32_t q = blockIdx.x * kBlock + threadIdx.x; q < D; q += gridDim.x * kBlock) {
-    const uint32_t i = w.dirty[q], gi = off + i;
-    f3 s, d;
-    load_ray(rays, ld, gi, s, d);
-    uint32_t patch = 0xFFFFFFFFu;
-    const Hit h = evaluate_patch<kFast>(m, static_cast<uint32_t>(w.key[i]) >> 6, s, d, patch);
-    store_hit(o.hits, ld, gi, h, patch);
-  }
-#endif
 }
 
 // The rays k_traverse could not take: the reference's full in-order scan, split into
@@ -2289,40 +1680,16 @@ template <bool kFast>
 __global__ __launch_bounds__(kBlock) BZR_RESOLVE_ATTR void k_resolve(MeshView m, const float *__restrict__ rays, uint32_t ld,
                                                     uint32_t off, uint32_t n, Work w) {
   const uint32_t F = __builtin_amdgcn_readfirstlane(w.ctr[0]);
-#if BZR_ROWS_DIRECT
-  for (uint32_t q0 = blockIdx.x * kBlock; q0 < F; q0 += gridDim.x * kBlock) {  // (whole waves: row_step votes)
-    const uint32_t q = q0 + threadIdx.x;
-    const bool todo = q < F;
-    uint32_t ray = 0u, j = 0u, b = 0u, nbr = 0u;
-    Hit h = no_hit();
-    if (todo) {
-      const uint2 pr = w.pairs[w.fol[q]];
-      ray = pr.x & kRayMask;
-      j = pr.x >> 26;
-      b = pr.y & ~(3u << 30);
-      const uint32_t what = pr.y >> 30;
-      f3 s, d;
-      load_pair_ray(w.aos, rays, ld, off, ray, s, d);
-      nbr = __float_as_uint(m.full[(size_t)rec::kWords * b + rec::kNeigh + what]);
-      Patch pa = load_patch(m.full + (size_t)rec::kWords * nbr);
-      h = patch_intersect<false, kFast>(pa, s, d, true);
-    }
-    // (a follow result ranks at its candidate b)
-    if (w.ro.rows) row_step(w.ro, w.key, todo && h.what == kIntersect, ray, j, b, h, nbr);
-    else if (todo && h.what == kIntersect) record(w.slot, n, ray, j, b, h, nbr, &w.key[ray]);
-  }
-#else
   for (uint32_t q = blockIdx.x * kBlock + threadIdx.x; q < F; q += gridDim.x * kBlock) {
     const uint2 pr = w.pairs[w.fol[q]];
     const uint32_t ray = pr.x & kRayMask, j = pr.x >> 26, b = pr.y & ~(3u << 30), what = pr.y >> 30;
     f3 s, d;
-    load_pair_ray(w.aos, rays, ld, off, ray, s, d);
+    load_ray(rays, ld, off + ray, s, d);
     const uint32_t nbr = __float_as_uint(m.full[(size_t)rec::kWords * b + rec::kNeigh + what]);
     Patch pa = load_patch(m.full + (size_t)rec::kWords * nbr);
     Hit h = patch_intersect<false, kFast>(pa, s, d, true);
     if (h.what == kIntersect) record(w.slot, n, ray, j, b, h, nbr, &w.key[ray]);  // ranks at its candidate
   }
-#endif
   const uint32_t V = __builtin_amdgcn_readfirstlane(w.ctr[1]);
   const uint32_t S = (m.n + kOvfSlice - 1) / kOvfSlice;
   const uint64_t items = (uint64_t)V * S;  // 64-bit: 2^20-ray chunks x slices of meshes above ~8M patches
@@ -2330,7 +1697,7 @@ __global__ __launch_bounds__(kBlock) BZR_RESOLVE_ATTR void k_resolve(MeshView m,
     const uint32_t q = (uint32_t)(item / S), lo = (uint32_t)(item - (uint64_t)q * S) * kOvfSlice, hi = min(m.n, lo + kOvfSlice);
     const uint32_t i = w.ovf[q];
     f3 s, d;
-    load_pair_ray(w.aos, rays, ld, off, i, s, d);
+    load_ray(rays, ld, off + i, s, d);
     float best_t = FLT_MAX;
     uint32_t best_b = 0xFFFFFFFFu;
     // (not unrolled: newton_tail's wave vote in div_heights is a convergent operation)
@@ -2356,7 +1723,6 @@ __global__ void k_count(Work w, uint32_t nb, unsigned long long *__restrict__ co
   counters[BZR_COUNTER_PAIRS] += w.ctr[3];
   counters[BZR_COUNTER_FOLLOWS] += w.ctr[0];
   counters[BZR_COUNTER_OVERFLOW_RAYS] += w.ctr[1];
-  counters[BZR_COUNTER_DIRTY_ROWS] += w.ctr[4];
   // k_newton_lane's chunks; Newton passes = dense chunks + those
   const unsigned long long tot = w.offs[nb];
   const uint32_t sparse_chunks = (static_cast<uint32_t>(tot) + 63u) / 64u;
@@ -2577,8 +1943,7 @@ __device__ __forceinline__ Hit parked(TraceLds<kMode> &L, uint32_t lane) {
 // One BezierMesh::intersect for the wave's active lanes; the winner is left in `best` / L.hit.
 template <int kMode, bool kFast, bool kCount>
 __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, bool act, unsigned long long &best,
-                                              TraceLds<kMode> &L, uint32_t lane, TraceCtr &ctr,
-                                              uint32_t *pflag = nullptr) {
+                                              TraceLds<kMode> &L, uint32_t lane, TraceCtr &ctr) {
   constexpr bool kPark = TraceWords<kMode>::kPark > 0;
   constexpr uint32_t kNo = 0xFFFFFFFFu;
   constexpr int kCap = TraceWords<kMode>::kStackCap;
@@ -2629,60 +1994,14 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
     bwalk = true;
   }
 #endif
-#if BZR_TRACE_PAIRSYNC
-  bool seg_done = false;  // this wave has no batch left in the segment (its partner may)
-#endif
   for (;;) {
     uint32_t ne = 0;  // collected leaves (uniform)
-#if BZR_TRACE_PAIRSYNC
-    // meeting point A: where two-wave lending would swap the waves' entry lists; the loop
-    // ends once both waves are done, and a done wave keeps meeting its partner with empty batches
-    if (lane == 0u) pflag[threadIdx.x >> 6] = seg_done ? 1u : 0u;
-    __syncthreads();
-    if (pflag[0] && pflag[1]) break;
-    if (!seg_done) {
-#endif
 #if BZR_TRACE_PRIO
     __builtin_amdgcn_s_setprio(BZR_TRACE_PRIO);  // the walk is latency-bound: issue it ahead of Newton passes
 #endif
 #if BZR_TRACE_BUNDLE
     while (bwalk && ne < kEntries) {
       if (pi < npend) {  // a queued leaf: every active lane's planar gate
-#if BZR_TRACE_BLEAF_PAIRS
-        // two queued leaves per step when the entry list has room for both: both records in flight, one wait
-        const bool two = pi + 1u < npend && ne + 1u < kEntries;
-        const uint32_t slot0 = __builtin_amdgcn_readfirstlane(L.pend[pi]);
-        const uint32_t slot1 = __builtin_amdgcn_readfirstlane(L.pend[two ? pi + 1u : pi]);
-        pi += two ? 2u : 1u;
-        u32x16 r0, r1;
-        asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx16 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                     : "=&s"(r0), "=&s"(r1)
-                     : "s"(leaf + 4u * slot0), "s"(leaf + 4u * slot1));
-        if (kCount) {
-          ctr.leaves += two ? 2u : 1u;
-          ctr.gate_tests += (two ? 2u : 1u) * popc64(__ballot(act));
-        }
-        const unsigned long long pm0 =
-            __ballot(act & planar_gate(leaf_q(r0, 0), leaf_q(r0, 1), leaf_q(r0, 2), leaf_q(r0, 3), s, d));
-        if (pm0) {
-          if (lane == 0u) {
-            L.eid[ne] = r0[15];
-            L.emask[ne] = pm0;
-          }
-          ++ne;
-        }
-        if (two) {
-          const unsigned long long pm1 =
-              __ballot(act & planar_gate(leaf_q(r1, 0), leaf_q(r1, 1), leaf_q(r1, 2), leaf_q(r1, 3), s, d));
-          if (pm1) {
-            if (lane == 0u) {
-              L.eid[ne] = r1[15];
-              L.emask[ne] = pm1;
-            }
-            ++ne;
-          }
-        }
-#else
         const uint32_t slot = __builtin_amdgcn_readfirstlane(L.pend[pi]);
         ++pi;
         const u32x16 r = *((const cu32x16 *)(uintptr_t)leaf + slot);
@@ -2699,7 +2018,6 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
           }
           ++ne;
         }
-#endif
         continue;
       }
       if (sp == 0) break;
@@ -2759,9 +2077,6 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
           const float4 g2 = make_float4(__uint_as_float(r[8]), __uint_as_float(r[9]), __uint_as_float(r[10]), __uint_as_float(r[11]));
           const float4 g3 = make_float4(__uint_as_float(r[12]), __uint_as_float(r[13]), __uint_as_float(r[14]), 0.0f);
           const bool pass = hit[c] & planar_gate(g0, g1, g2, g3, s, d)
-#if BZR_DIAG_WALK2
-                            & planar_gate(g0, g1, g2, g3, opaque(s), opaque(d))
-#endif
               ;
           if (kCount) {
             ++ctr.leaves;
@@ -2814,15 +2129,7 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
       }
     }
     if (ne == 0u) {  // tree done: the reference's in-order scan for the lanes that could not use it
-#if BZR_TRACE_PAIRSYNC
-#define BZR_SEG_END       \
-  {                       \
-    seg_done = true;      \
-    goto pair_b;          \
-  }
-#else
 #define BZR_SEG_END break;
-#endif
       if (scan == kNo) {
         if (!__any(ovf)) BZR_SEG_END
         scan = 0;
@@ -2844,12 +2151,6 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
       ne = 1;
       ++scan;
     }
-#if BZR_TRACE_PAIRSYNC
-    }  // !seg_done
-  pair_b:
-    __syncthreads();  // meeting point B: where lending would hand the borrowed lanes' results back
-    if (seg_done) ne = 0u;
-#endif
     // the collected leaves' passes, in order
 #if BZR_TRACE_PRIO
     __builtin_amdgcn_s_setprio(0);
@@ -2879,16 +2180,7 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
       }
       uint32_t what = kNone;
       if (run0 || joined || spec) {
-#if BZR_DIAG_NEWTON2
-        // the extra evaluation first, folded to one word, so it adds ~1 live register to the real one
-        const Hit h2 = patch_intersect<false, kFast>(hp, opaque(s), opaque(d), joined || spec);
-        const uint32_t k2 = __float_as_uint(h2.t) ^ h2.what ^ __float_as_uint(h2.normal.x) ^ __float_as_uint(h2.point.y);
-        Hit h = patch_intersect<false, kFast>(hp, s, d, joined || spec);
-        if (k2 != (__float_as_uint(h.t) ^ h.what ^ __float_as_uint(h.normal.x) ^ __float_as_uint(h.point.y)))
-          h.what = kNone;  // never (the same evaluation): keeps h2's whole evaluation
-#else
         const Hit h = patch_intersect<false, kFast>(hp, s, d, joined || spec);
-#endif
         if (spec) {
           park(h, L, lane);
           parked_nb = b;
@@ -2973,15 +2265,8 @@ struct TraceJob {
 #endif
 // Threads per k_trace block (BZR_TRACE_BLOCK): its waves share nothing but the CU, so one-wave blocks let
 // a finished wave be replaced at once (waves run 1-4 segments; 64 vs 256: cfg4 -3 %, cfg5 -7 %).
-// BZR_TRACE_PAIRSYNC (diagnostic A/B, default 0): two-wave k_trace blocks whose waves meet twice per collected
-// batch, as lane lending between them would need, with nothing lent: the measured cost of
-// the pairing alone, against scripts/pair_sim.py's bound on what lending could save.  Same bits
-// and passes; cfg4 -8.4 %, cfg2 -8.6 % (profiles/r05_ab_pairsync.jsonl) against <= ~2 % lending could recover.
-#ifndef BZR_TRACE_PAIRSYNC
-#define BZR_TRACE_PAIRSYNC 0
-#endif
 #ifndef BZR_TRACE_BLOCK
-#define BZR_TRACE_BLOCK (BZR_TRACE_PAIRSYNC ? 128 : 64)
+#define BZR_TRACE_BLOCK 64
 #endif
 constexpr int kTraceBlock = BZR_TRACE_BLOCK, kTraceWaves = kTraceBlock / 64;
 // Which 64-ray tile block b takes (BZR_TRACE_XCD): 0 = the dispatch order itself (XCD x gets every 8th
@@ -3072,12 +2357,6 @@ template <int kMode, bool kFast, bool kCount>
 __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet lenses, TraceJob job,
                                                                       unsigned long long *__restrict__ counters) {
   __shared__ TraceLds<kMode> lds[kTraceWaves];
-#if BZR_TRACE_PAIRSYNC
-  static_assert(kTraceWaves == 2, "BZR_TRACE_PAIRSYNC pairs the two waves of a 128-thread block");
-  __shared__ uint32_t pflag[2];
-#else
-  uint32_t *const pflag = nullptr;
-#endif
   const uint32_t lane = threadIdx.x & 63u;
   TraceLds<kMode> &L = lds[threadIdx.x >> 6];
   const uint32_t tile = job.order ? job.order[blockIdx.x] : trace_tile(blockIdx.x, gridDim.x);
@@ -3094,11 +2373,11 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
   const uint32_t nseg = kMode == kModeStage ? 2u * lenses.count : 1u;
   uint32_t st = BZR_RR_NONE, seg = 0;
   for (uint32_t k = 0; k < nseg; ++k) {
-    if (!BZR_TRACE_PAIRSYNC && !__any(alive)) break;  // (paired waves both run every segment: same meetings)
+    if (!__any(alive)) break;
     const MeshView &m = lenses.lens[k >> 1];
     unsigned long long best;
     const uint32_t r0 = ctr.rounds, w0 = ctr.pairs + ctr.follows;
-    trace_segment<kMode, kFast, kCount>(m, s, d, alive, best, L, lane, ctr, pflag);
+    trace_segment<kMode, kFast, kCount>(m, s, d, alive, best, L, lane, ctr);
     if (kCount) {
       ctr.segments += popc64(__ballot(alive));
       if (k & 1u) {  // per-segment lane utilisation: front (even) vs back (odd) surfaces
@@ -3163,15 +2442,6 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
     if (mine) atomicAdd(&counters[(size_t)rep * BZR_COUNTER_COUNT + which], (unsigned long long)mine);
   }
 }
-
-// BZR_TRACE_RPL (default 1): rays per lane of the fused kernel.  2 or 4: k_trace_r (trace_pool.inc), one wave
-// per 64 R rays with the Newton passes pooled over all of them.
-#ifndef BZR_TRACE_RPL
-#define BZR_TRACE_RPL 1
-#endif
-#if BZR_TRACE_RPL > 1
-#include "trace_pool.inc"
-#endif
 
 // ------------------------------------------------------------ brute-force path
 __global__ __launch_bounds__(kBlock) void k_intersect_scan(MeshView m, const float *__restrict__ rays, uint32_t n,
@@ -3412,18 +2682,6 @@ uint32_t resident_blocks(bzr_ctx *ctx, K kernel) {
   return blocks;
 }
 
-// BZR_TRAV_HYBRID's threshold: lanes a leaf's gate must pass for k_traverse to run its Newton pass in the wave
-// (environment BZR_HYBRID_T, 1..64; 0 = list every leaf, round 5's pipeline; read once per process).
-uint32_t hybrid_threshold() {
-  static const uint32_t t = [] {
-    const char *e = std::getenv("BZR_HYBRID_T");
-    if (!e || !*e) return (uint32_t)BZR_HYBRID_T_DEFAULT;
-    const long v = std::strtol(e, nullptr, 10);
-    return (uint32_t)(v < 0 ? 0 : v > 64 ? 64 : v);
-  }();
-  return BZR_TRAV_HYBRID ? t : 0u;
-}
-
 // Grid of the persistent staged kernels (k_newton, k_resolve) in units of the device's resident capacity
 // (A/B knobs, environment BZR_NEWTON_GRIDX / BZR_RESOLVE_GRIDX, 1..64, read once per process).  A grid
 // of exactly the resident capacity holds every wave slot until the kernel ends, so another frame's kernels (frames
@@ -3468,9 +2726,8 @@ bzr_status ensure_work(bzr_ctx *ctx, uint32_t chunk, uint32_t nb, Work &w) {
   const size_t cap = (size_t)kMaxCand * chunk;
   const size_t bytes = round256(32) + round256((size_t)(hn + 1) * 4) + round256((size_t)(hn + 1) * 8) + 2 * round256(cap * 4) +
                        round256((size_t)chunk * 4) + round256((size_t)chunk * 8) + round256(kSlotWords * cap * 4) +
-                       round256((cap + 64 * ((size_t)nb + 1) + (BZR_TRAV_HYBRID ? cap : 0)) * 8) + round256(cap * 4) +
-                       2 * round256((size_t)chunk * 4) + round256(((size_t)chunk + kAblockBlock - 1) / kAblockBlock * kAmaskWords * 8) +
-                       (BZR_STAGED_AOS ? round256((size_t)chunk * 32) : 0) + round256(cub_bytes);
+                       round256((cap + 64 * ((size_t)nb + 1)) * 8) + round256(cap * 4) +
+                       round256((size_t)chunk * 4) + round256(cub_bytes);
   const size_t had = ctx->work_bytes;
   if (bzr_status s = ensure_buffer(ctx->work, ctx->work_bytes, bytes)) return s;
   if (ctx->work_bytes != had) ctx->zero_ctr = nullptr;  // reallocated (possibly at the same address)
@@ -3483,18 +2740,12 @@ bzr_status ensure_work(bzr_ctx *ctx, uint32_t chunk, uint32_t nb, Work &w) {
   w.count = st.take<uint32_t>(chunk);
   w.key = st.take<unsigned long long>(chunk);
   w.slot = st.take<float>(kSlotWords * cap);
-  // dense chunks (< 64 padding slots per patch) + sparse; then (BZR_TRAV_HYBRID) the in-wave follow requests' records
-  w.pairs = st.take<uint2>(cap + 64 * ((size_t)nb + 1) + (BZR_TRAV_HYBRID ? cap : 0));
+  w.pairs = st.take<uint2>(cap + 64 * ((size_t)nb + 1));  // dense chunks (< 64 padding slots per patch) + sparse
   w.fol = st.take<uint32_t>(cap);
   w.ovf = st.take<uint32_t>(chunk);
-  w.dirty = st.take<uint32_t>(chunk);
-  w.amask = st.take<unsigned long long>(((size_t)chunk + kAblockBlock - 1) / kAblockBlock * kAmaskWords);
-  w.aos = BZR_STAGED_AOS ? st.take<float4>((size_t)2 * chunk) : nullptr;
   w.cub = st.take<char>(cub_bytes ? cub_bytes : 1);
   w.cub_bytes = cub_bytes;
   w.cap = static_cast<uint32_t>(cap);
-  w.hbase = static_cast<uint32_t>(cap + 64 * ((size_t)nb + 1));
-  w.hyb_t = hybrid_threshold();
   return BZR_OK;
 }
 
@@ -3507,9 +2758,10 @@ bzr_status ensure_work(bzr_ctx *ctx, uint32_t chunk, uint32_t nb, Work &w) {
 #define BZR_CHUNK_LOG2 23
 #endif
 constexpr uint32_t kChunk = 1u << BZR_CHUNK_LOG2;
-constexpr size_t kWorkBytesPerRay = (size_t)kMaxCand * (4 + 4 + 48 + 8 + 4 + (BZR_TRAV_HYBRID ? 8 : 0)) + 20 + (BZR_STAGED_AOS ? 32 : 0);
+// what ensure_work takes per ray: per list slot cand, rank, slot, pair and fol; per ray count, key and ovf
+constexpr size_t kWorkBytesPerRay = (size_t)kMaxCand * (4 + 4 + 48 + 8 + 4) + (4 + 8 + 4);
 static_assert(BZR_CHUNK_LOG2 <= 26, "pair records hold a chunk's ray index in 26 bits");
-static_assert((uint64_t)kMaxCand * kChunk * (BZR_TRAV_HYBRID ? 2 : 1) + 64ull * (kStagedPatchLimit + 1) < (1ull << 32),
+static_assert((uint64_t)kMaxCand * kChunk + 64ull * (kStagedPatchLimit + 1) < (1ull << 32),
               "32-bit pair indices");
 static_assert(kMaxCand <= 64, "winner keys hold a list slot in 6 bits");
 uint32_t chunk_for(bzr_ctx *ctx, uint64_t n) {
@@ -3540,18 +2792,8 @@ bzr_status run_culled(bzr_ctx *ctx, const MeshView &mv, const float *rays, uint3
                            ctx->stream));
   ctx->zero_ctr = nullptr;  // valid again only once this segment is fully enqueued
   unsigned long long *const ctr = (ctx->counting && ctx->counters) ? ctx->counters : nullptr;
-  // BZR_ROWS_DIRECT: an intersect segment's Newton stage writes the hit rows itself (record_row)
-  w.ro = RowOut{};
-  if (kMode == kModeHits && BZR_ROWS_DIRECT && BZR_FINISH_NORAY && !BZR_TRAV_HYBRID)
-    w.ro = RowOut{o.hits, ld, off, w.count, w.dirty, w.ctr + 4};
-  if (BZR_TRAV_ABLOCK == 3 && mv.n_always > kAblockMin && mv.n_always <= kAblockMax) {  // pre-test kernel, then the walk
-    Span sp(ctx, BZR_KERNEL_TRAVERSE);
-    hipLaunchKernelGGL(k_always_mask, dim3((n + kAblockBlock - 1) / kAblockBlock), dim3(kAblockBlock), 0, ctx->stream, mv,
-                       rays, ld, off, alive, n, w.amask);
-    hipLaunchKernelGGL((k_traverse<kTravBlock, 3, kFast>), dim3((n + kTravBlock - 1) / kTravBlock), dim3(kTravBlock), 0,
-                       ctx->stream, mv, rays, ld, off, alive, n, w, ctr);
-  } else if (BZR_TRAV_ABLOCK && mv.n_always > kAblockMin && mv.n_always <= kAblockMax)  // block-level always-list pre-test
-    launch_on(ctx, ctx->stream, dim3(kAblockBlock), BZR_KERNEL_TRAVERSE, k_traverse<kAblockBlock, BZR_TRAV_ABLOCK == 3 ? 1 : BZR_TRAV_ABLOCK, kFast>,
+  if (BZR_TRAV_ABLOCK && mv.n_always > kAblockMin && mv.n_always <= kAblockMax)  // block-level always-list pre-test
+    launch_on(ctx, ctx->stream, dim3(kAblockBlock), BZR_KERNEL_TRAVERSE, k_traverse<kAblockBlock, BZR_TRAV_ABLOCK, kFast>,
               dim3((n + kAblockBlock - 1) / kAblockBlock), mv, rays, ld, off, alive, n, w, ctr);
   else
     launch_on(ctx, ctx->stream, dim3(kTravBlock), BZR_KERNEL_TRAVERSE, k_traverse<kTravBlock, 0, kFast>,
@@ -3570,9 +2812,9 @@ bzr_status run_culled(bzr_ctx *ctx, const MeshView &mv, const float *rays, uint3
   const uint32_t gn = std::min<uint32_t>(std::max<uint32_t>((kMaxCand * n + kBlock - 1) / kBlock, 1u),
                                          resident_blocks(ctx, k_newton<kFast>) * newton_gridx(nb));
   launch(ctx, BZR_KERNEL_NEWTON, k_newton<kFast>, dim3(gn), mv.full, w.offs + hn, w.pairs, rays, ld, off, n, w.slot, w.key,
-         w.fol, w.ctr, (const float4 *)w.aos, w.ro);
+         w.fol, w.ctr);
   launch(ctx, BZR_KERNEL_NEWTON_LANE, k_newton_lane<kFast>, dim3(std::min<uint32_t>(std::max<uint32_t>(n / 1024u, 1u), 1024u)),
-         mv.full, w.offs + hn, w.pairs, rays, ld, off, n, w.slot, w.key, w.fol, w.ctr, (const float4 *)w.aos, w.ro);
+         mv.full, w.offs + hn, w.pairs, rays, ld, off, n, w.slot, w.key, w.fol, w.ctr);
   {  // follow retries + overflow rays (whose keys the Newton stage left untouched: their lists are empty)
     const uint64_t items = (uint64_t)n * ((nb + kOvfSlice - 1) / kOvfSlice);
     const uint32_t grid = std::max(std::min<uint32_t>(grid_for(n / 8 + 1), resolve_blocks()),
@@ -3606,7 +2848,7 @@ bzr_status run_fused(bzr_ctx *ctx, const LensSet &set, const TraceJob &job, uint
   j.order = nullptr;
   j.cost = nullptr;
   const uint32_t tiles = grid.x;
-  const bool sched = BZR_TRACE_SCHED && BZR_TRACE_RPL == 1 && tiles >= kSchedMinTiles;
+  const bool sched = BZR_TRACE_SCHED && tiles >= kSchedMinTiles;
   if (sched) {  // this call's tile costs; the order of the last call of the same size, if any
     if (ctx->sched_cap < tiles) {
       if (ctx->sched) BZR_HIP(hipFree(ctx->sched));
@@ -3634,20 +2876,6 @@ bzr_status run_fused(bzr_ctx *ctx, const LensSet &set, const TraceJob &job, uint
     }
   }
   const bool rebuild = sched && ctx->sched_calls % BZR_TRACE_SCHED_REFRESH == 0;
-#if BZR_TRACE_RPL > 1
-  constexpr uint32_t kRays = 64u * BZR_TRACE_RPL;  // rays per one-wave block (k_trace_r)
-  const dim3 rgrid((job.n + kRays - 1) / kRays), rblock(64);
-  auto go = [&](auto kernel) { launch_on(ctx, ctx->stream, rblock, BZR_KERNEL_TRACE, kernel, rgrid, set, j, ctx->counters); };
-  (void)grid;
-  (void)block;
-  if (fast) {
-    if (count) go(k_trace_r<kMode, BZR_TRACE_RPL, true, true>);
-    else go(k_trace_r<kMode, BZR_TRACE_RPL, true, false>);
-  } else {
-    if (count) go(k_trace_r<kMode, BZR_TRACE_RPL, false, true>);
-    else go(k_trace_r<kMode, BZR_TRACE_RPL, false, false>);
-  }
-#else
   auto go = [&](auto kernel) { launch_on(ctx, ctx->stream, block, BZR_KERNEL_TRACE, kernel, grid, set, j, ctx->counters); };
   if (fast) {
     if (count) go(k_trace<kMode, true, true>);
@@ -3656,7 +2884,6 @@ bzr_status run_fused(bzr_ctx *ctx, const LensSet &set, const TraceJob &job, uint
     if (count) go(k_trace<kMode, false, true>);
     else go(k_trace<kMode, false, false>);
   }
-#endif
   BZR_HIP(hipGetLastError());
   if (rebuild) {  // the next calls' order: tiles longest-first (counting sort of the cost bins)
     uint32_t *order = ctx->sched + ctx->sched_cap, *hist = ctx->sched + (size_t)2 * ctx->sched_cap, *offs = hist + kSchedBins;

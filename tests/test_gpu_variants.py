@@ -11,10 +11,6 @@ dense1 / dense64: libbzr with the staged pair layout's two extremes (-DBZR_DENSE
 partial chunk padded, no sparse region; =64: no padding, every remainder in the sparse region): staged ==
 brute force (== the oracle on cfg2 and the cfg4 chain) through only the dense or mostly the sparse kernel.
 
-rpl2 / rpl4: libbzr whose fused kernel is k_trace_r (trace_pool.inc): 2 or 4 rays per lane, the Newton passes
-pooled over a wave's 128 / 256 rays (-DBZR_TRACE_RPL); the same checks plus cfg4's two-lens chain and origins
-beyond s_max (the in-order scan inside the pooled kernel), fused == brute force == the oracle.
-
 tracebundle / traceperlane: libbzr with k_trace's wave-bundle walk one tree level per batch (-DBZR_TRACE_WIDE=0;
 the default takes two) and with k_trace's per-lane walk (-DBZR_TRACE_BUNDLE=0, round 3's default): the same
 checks, fused == staged == brute force (== the oracle on cfg2), including the incoherent cfg5 rays whose wide
@@ -223,28 +219,6 @@ def test_trace_bundle_walk_is_exact(variant):
     if variant == "traceperlane":
         assert out["stack_fused_overflow_rays"] == 0, out
     assert out["cfg5_hits"] > 10000
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("variant", ["rpl2", "rpl4"])
-def test_pooled_passes_are_exact(variant):
-    """k_trace_r (2 / 4 rays per lane, Newton passes pooled over the wave's rays): bit-identical to the
-    brute-force scan and the oracle on cfg2 / cfg4 chains, cfg5 intersect and far origins."""
-    lib = PKG / "lib" / variant / "libbzr.so"
-    if not lib.exists():
-        pytest.fail(f"{lib} missing: build() makes the `variants` target")
-    env = dict(os.environ, BZR_LIBRARY=str(lib))
-    res = subprocess.run([sys.executable, "-c", WORKER, str(PKG), str(REPO), "--more"], env=env,
-                         capture_output=True, text=True, timeout=110)
-    assert res.returncode == 0, res.stderr[-2000:]
-    out = json.loads(res.stdout.strip().splitlines()[-1])
-    for k, v in out.items():
-        if k.endswith("_equal"):
-            assert v, (k, out)
-    assert_edge_inputs_ran(out)
-    assert out["cfg2_fused_overflow_rays"] == 0 and out["cfg5_fused_overflow_rays"] == 0
-    assert out["stack_fused_overflow_rays"] == 0 and out["stack_staged_overflow_rays"] == out["stack_gate_over_40"] > 0, out
-    assert out["far_overflow_rays"] == out["far_count"]
 
 
 @pytest.mark.gpu
