@@ -113,6 +113,7 @@ _SIGS = {
     "bzr_pack_frame": [_P, _I32, _P, _P, _P, _U32, _U32, _U32, _P],
     "bzr_debug_unit": [_P, _P, _U32, _P],
     "bzr_debug_div_heights": [_P, _P, _U32, _P],
+    "bzr_debug_fast_unit": [_P, _P, _U32, _P],
     "bzr_debug_wave_clock": [_P, _P, _U32],
     "bzr_debug_wave_clock_rate": [_P, _P, _U32],
 }
@@ -363,15 +364,16 @@ def intersect_records(ctx: Context, mesh: DeviceMesh, rays, records=None, patch=
     return records, patch
 
 
-def patch_intersect(ctx: Context, mesh: DeviceMesh, patch_index, limit, rays, out=None):
-    """BezierTriangle::intersect for (patch, ray, limit) triples -> hits [13, n]."""
+def patch_intersect(ctx: Context, mesh: DeviceMesh, patch_index, limit, rays, out=None, mode=MODE_PARITY):
+    """BezierTriangle::intersect for (patch, ray, limit) triples -> hits [13, n]; mode MODE_FAST: the Newton stage in
+    fast arithmetic after the exact gate."""
     n = _n_of(rays)
     out = _empty_like(rays, HIT_FIELDS, np.float32) if out is None else out
     i, l_ = _Buf(patch_index, np.uint32), _Buf(limit, np.uint32)
     r, o = _Buf(rays, np.float32), _Buf(out, np.float32, True)
     res = _residency(i, l_, r, o)
     with _stream_for(ctx, res):
-        _check(lib().bzr_patch_intersect(ctx.handle, mesh.handle, i.ptr, l_.ptr, r.ptr, n, o.ptr, res))
+        _check(lib().bzr_patch_intersect(ctx.handle, mesh.handle, i.ptr, l_.ptr, r.ptr, n, o.ptr, res | mode))
     return out
 
 

@@ -3548,7 +3548,30 @@ __global__ __launch_bounds__(kBlock) void k_debug_div_heights(const float *__res
   out[(size_t)2 * n + i] = div_rn(hin, ic);
   out[(size_t)3 * n + i] = div_rn(hout, ic);
 }
+// BZR_MODE_FAST's primitives (patch_math.hpp namespace fast): row 0 div_rn(a0, a1), row 1 sqrt_rn(|a0|), rows 2..4
+// normalized(a).
+__global__ __launch_bounds__(kBlock) void k_debug_fast_unit(const float *__restrict__ a, uint32_t n,
+                                                            float *__restrict__ out) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const f3 v = mk(a[i], a[(size_t)n + i], a[(size_t)2 * n + i]);
+  const f3 u = fast::normalized(v);
+  const float r[5] = {fast::div_rn(v.x, v.y), fast::sqrt_rn(fabsf(v.x)), u.x, u.y, u.z};
+#pragma unroll
+  for (int k = 0; k < 5; ++k) out[(size_t)k * n + i] = r[k];
+}
 }  // namespace
+
+extern "C" bzr_status bzr_debug_fast_unit(void *ctxp, const float *a, uint32_t n, float *out) {
+  bzr_ctx *ctx = static_cast<bzr_ctx *>(ctxp);
+  if (!ctx) return set_error(BZR_ERR_INVALID_ARGUMENT, "null context");
+  if (n == 0) return BZR_OK;
+  if (!a || !out) return set_error(BZR_ERR_INVALID_ARGUMENT, "null buffer");
+  DeviceGuard g(ctx->device);
+  hipLaunchKernelGGL(k_debug_fast_unit, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, a, n, out);
+  BZR_HIP(hipGetLastError());
+  return BZR_OK;
+}
 
 extern "C" bzr_status bzr_debug_div_heights(void *ctxp, const float *a, uint32_t n, float *out) {
   bzr_ctx *ctx = static_cast<bzr_ctx *>(ctxp);

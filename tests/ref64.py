@@ -1,0 +1,266 @@
+"""float64 restatement of BezierTriangle::intersect and BezierMesh::intersect, for judging float32 results.
+
+A plain helper module (no fixtures, no plugin).  It is written from csrc/device/patch_math_body.inc and
+oracle/bzr_oracle.c: the same expressions, evaluated by numpy in binary64 over arrays of (patch, ray, limit)
+triples.  The record's float32 words and the float32 constants 1e-5f (plane_ray's |cos| floor, deviations D1/D2 of
+DESIGN.md included), 1e-6f (the secant's denominator floor) and 0.01f (the acceptance radius) are taken at their
+float32 values; everything computed from them is binary64, so a result here carries about 2^-29 of the float32
+oracle's rounding noise and serves as the truth both the oracle and BZR_MODE_FAST are measured against.
+
+patch_intersect64   per triple: the planar gate, the bracket, the secant start, the 4 Newton steps, the acceptance
+                    and the divider classification; every hit field, `what`, and the conditioning margins
+intersect64         the mesh-level winner over the pairs of an exact gate matrix (oracle.planar_gate): cThis per
+                    pair, the follow-side retry on the named neighbour with cNone under the original scan index,
+                    strict-< minimum over finite t
+well_conditioned    the triples whose class and fields float32 can be expected to reproduce (margins below)
+"""
+from types import SimpleNamespace
+
+import numpy as np
+
+NONE, INTERSECT = 3, 4
+LIMIT_THIS, LIMIT_NONE = 0, 1
+EPS_COS = float(np.float32(0.00001))
+EPS_DEN = float(np.float32(0.000001))
+PERP_MAX = float(np.float32(0.01))
+
+# the conditioning margins (span = the mesh's largest control-point extent)
+PERP_WELL = 0.005       # norm(perp) below half the acceptance radius
+DIVIDER_WELL = 1e-3     # x span: the point's distance from every divider plane
+HEIGHT_WELL = 1e-4      # x span: the gate's two height tests
+BARY_WELL = 1e-4        # cThis: every gate barycentric inside [BARY_WELL, 1 - BARY_WELL]
+COS_WELL = 0.05         # |cos| of incidence
+SEPARATION_WELL = 1e-4  # x span: mesh level, the winner's t below every other patch's finite t
+
+# the seeds of aimed_triples per lens of lens_set (tests/test_ref64.py says why robot's is not 24)
+SEEDS = {"origin": 21, "cfg2": 22, "cfg1": 23, "robot": 26}
+
+
+def mesh_span(patches):
+    cp = np.asarray(patches)[:, 19:49].reshape(-1, 3).astype(np.float64)
+    return float((cp.max(axis=0) - cp.min(axis=0)).max())
+
+
+def _dot(a, b):
+    return (a * b).sum(axis=-1)
+
+
+def _unit(a):
+    """Eigen normalized() as unit_or_self states it: a / sqrt(a.a) when a.a > 0, else a unchanged."""
+    z = _dot(a, a)
+    ok = z > 0.0
+    return np.where(ok[:, None], a / np.sqrt(np.where(ok, z, 1.0))[:, None], a)
+
+
+def _plane_ray(n, c, start, direction):
+    """Plane::intersect with D1 (the point for any t) and D2 (point = start, t = 0 when |cos| < 1e-5f)."""
+    cs = _dot(direction, n)
+    ok = np.abs(cs) >= EPS_COS
+    t = np.where(ok, (c - _dot(n, start)) / np.where(ok, cs, 1.0), 0.0)
+    point = np.where(ok[:, None], start + direction * t[:, None], start)
+    return ok & (t > 0.0), point, cs, t
+
+
+def _matvec(m, v):  # m [k, col, row]: the record's col-major Minv
+    return np.einsum("kcr,kc->kr", m, v)
+
+
+def _interpolate(cp, b):
+    b0, b1, b2 = b[:, 0:1], b[:, 1:2], b[:, 2:3]
+    q0, q1, q2 = b0 * b0, b1 * b1, b2 * b2
+    lin = cp[:, 0] * b0 * q0 + cp[:, 1] * b1 * q1 + cp[:, 2] * b2 * q2
+    side = (cp[:, 3] * b1 * q0 + cp[:, 4] * b0 * q1 + cp[:, 5] * b2 * q1 + cp[:, 6] * b1 * q2 + cp[:, 7] * b0 * q2
+            + cp[:, 8] * b2 * q0)
+    return lin + 3.0 * side + 6.0 * cp[:, 9] * b0 * b1 * b2
+
+
+def _surface_normal(cp, da, db, b):
+    b0, b1, b2 = b[:, 0:1], b[:, 1:2], b[:, 2:3]
+    q0, q1, q2 = b0 * b0, b1 * b1, b2 * b2
+    # control point slots: 300=0 030=1 003=2 210=3 120=4 021=5 012=6 102=7 201=8 111=9
+    k0 = cp[:, 0] * q0 + cp[:, 7] * q2 + cp[:, 4] * q1 + 2.0 * (cp[:, 8] * b0 * b2 + cp[:, 3] * b0 * b1 + cp[:, 9] * b2 * b1)
+    k1 = cp[:, 1] * q1 + cp[:, 6] * q2 + cp[:, 3] * q0 + 2.0 * (cp[:, 9] * b0 * b2 + cp[:, 4] * b0 * b1 + cp[:, 5] * b1 * b2)
+    k2 = cp[:, 2] * q2 + cp[:, 8] * q0 + cp[:, 5] * q1 + 2.0 * (cp[:, 7] * b0 * b2 + cp[:, 6] * b1 * b2 + cp[:, 9] * b0 * b1)
+    ca = da[:, 0:1] * k0 + da[:, 1:2] * k1 + da[:, 2:3] * k2
+    cb = db[:, 0:1] * k0 + db[:, 1:2] * k1 + db[:, 2:3] * k2
+    return _unit(np.cross(ca, cb))
+
+
+def patch_intersect64(patches, idx, limit, rays, gated=False):
+    """BezierTriangle::intersect for the triples (patches[idx[k]], rays[:, k], limit[k]) in binary64.
+
+    gated: the triples are taken to have passed the planar gate (the culled pipeline's candidates), whatever
+    binary64 makes of it.  Returns a namespace of arrays over the triples: t, point [m, 3], cs, bary [m, 3],
+    normal [m, 3], what, passed (the gate), and the margins perp (norm of the acceptance's perpendicular), divider
+    (the point's least distance from a divider plane), height (the gate's height tests' least slack), gate_bary (the
+    gate barycentrics' least distance from 0 and 1), all as computed when the gate passes and zero when it fails."""
+    rec = np.asarray(patches, dtype=np.float32)[np.asarray(idx, dtype=np.int64)].astype(np.float64)
+    limit = np.asarray(limit)
+    r = np.asarray(rays, dtype=np.float32).astype(np.float64)
+    s, d = r[:3].T, r[3:].T
+    n, c = rec[:, 0:3], rec[:, 3]
+    div = rec[:, 4:16].reshape(-1, 3, 4)
+    cp = rec[:, 19:49].reshape(-1, 10, 3)
+    minv = rec[:, 49:58].reshape(-1, 3, 3)
+    hin, hout = rec[:, 58], rec[:, 59]
+    da, db = rec[:, 60:63], rec[:, 63:66]
+    m = len(rec)
+    with np.errstate(all="ignore"):
+        valid, ip, ic, it = _plane_ray(n, c, s, d)
+        b0 = _matvec(minv, ip)
+        height = np.minimum(np.abs(it) + hin, np.abs(it) - hout)
+        gate_bary = np.minimum(b0.min(axis=1), 1.0 - b0.max(axis=1))
+        passed = valid & (np.abs(it) > -hin) & (np.abs(it) > hout) & ((limit != 0) | (gate_bary >= 0.0))
+        if gated is not False:
+            passed = passed | np.asarray(gated, dtype=bool)
+        din, dout = hin / ic, hout / ic
+        closer = it + np.where(ic > 0.0, din, dout)
+        further = it + np.where(ic > 0.0, dout, din)
+
+        def diff(tt):
+            por = s + d * tt[:, None]
+            dist = _dot(por, n) - c
+            q = _interpolate(cp, _matvec(minv, por - n * dist[:, None]))
+            return np.abs(dist) - np.abs(_dot(q, n) - c)
+
+        diffc, difff = diff(closer), diff(further)
+        den = diffc - difff
+        small = np.abs(den) < EPS_DEN
+        middle = np.where(small, (closer + further) / 2.0, (diffc * further - difff * closer) / np.where(small, 1.0, den))
+        pdir = n
+        for _ in range(4):
+            t = middle
+            por = s + d * middle[:, None]
+            _, pp, _, _ = _plane_ray(n, c, por, pdir)
+            bary = _matvec(minv, pp)
+            normal = _surface_normal(cp, da, db, bary)
+            point = _interpolate(cp, bary)
+            pdir = _unit(point - pp)
+            middle = _dot(point - s, normal) / _dot(d, normal)
+        rel = point - s
+        perp = rel - d * _dot(rel, d)[:, None]
+        perp_norm = np.sqrt(_dot(perp, perp))
+        rejected = (perp_norm > PERP_MAX) | (t < (further - closer))
+        dist = np.einsum("kjc,kc->kj", div[:, :, :3], point) - div[:, :, 3]
+        out = (dist < 0.0).astype(np.int64) @ np.array([1, 2, 4])
+        what = np.select([rejected, out == 1, out == 2, out == 4], [NONE, 0, 1, 2], INTERSECT)
+        cs = np.where(what == INTERSECT, _dot(d, normal), 0.0)
+        divider = (np.abs(dist) / np.sqrt((div[:, :, :3] ** 2).sum(axis=2))).min(axis=1)
+    h = SimpleNamespace(t=t, point=point, cs=cs, bary=bary, normal=normal, what=what, passed=passed, perp=perp_norm,
+                        divider=divider, height=height, gate_bary=gate_bary)
+    fail = ~passed
+    for name in ("t", "point", "cs", "bary", "normal", "perp", "divider", "height", "gate_bary"):
+        getattr(h, name)[fail] = 0.0
+    h.what[fail] = NONE
+    assert h.t.shape == (m,)
+    return h
+
+
+def well_conditioned(h, limit, span):
+    """The triples of patch_intersect64's result whose class and fields a float32 evaluation can be expected to
+    reproduce: INTERSECT with a finite t, and every decision on the way taken with a margin."""
+    limit = np.asarray(limit)
+    with np.errstate(invalid="ignore"):
+        return ((h.what == INTERSECT) & np.isfinite(h.t) & (h.perp < PERP_WELL) & (h.divider >= DIVIDER_WELL * span)
+                & (h.height >= HEIGHT_WELL * span) & ((limit != 0) | (h.gate_bary >= BARY_WELL)) & (np.abs(h.cs) > COS_WELL))
+
+
+def intersect64(patches, rays, gate):
+    """BezierMesh::intersect in binary64 over the candidate pairs of the exact float32 gate matrix `gate`
+    [rays, patches] (oracle.planar_gate): BZR_MODE_FAST's contract is that it sees exactly these candidates, so the
+    selection is not re-derived here.  Per pair cThis (taken as gated); a follow-side result is retried on the named
+    neighbour with cNone and keeps the pair's place in the scan; the winner is the first strict minimum over finite t.
+
+    Returns a namespace over the rays: what (INTERSECT or NONE), patch (0xFFFFFFFF for a miss), t, point, cs, bary,
+    normal, and well: the winner is well-conditioned (and so is the cThis evaluation that named it, for a retry) and
+    its t lies below the finite t of every candidate on another patch by more than SEPARATION_WELL x span."""
+    patches = np.asarray(patches, dtype=np.float32)
+    rays = np.asarray(rays, dtype=np.float32)
+    nr = rays.shape[1]
+    span = mesh_span(patches)
+    neigh = np.ascontiguousarray(patches).view(np.uint32)[:, 16:19]
+    ri, pi = np.nonzero(gate)  # row-major: by ray, then in scan order
+    h1 = patch_intersect64(patches, pi, np.zeros(len(pi), np.uint32), rays[:, ri], gated=True)
+    follow = h1.what <= 2
+    src = pi.copy()
+    src[follow] = neigh[pi[follow], h1.what[follow]]
+    h2 = patch_intersect64(patches, src[follow], np.ones(int(follow.sum()), np.uint32), rays[:, ri[follow]])
+    h = SimpleNamespace(**{k: np.array(v, copy=True) for k, v in vars(h1).items()})
+    for name in vars(h):
+        getattr(h, name)[follow] = getattr(h2, name)
+    limit = follow.astype(np.uint32)
+    first_ok = ~follow | ((h1.perp < PERP_WELL) & (h1.divider >= DIVIDER_WELL * span))
+    good = well_conditioned(h, limit, span) & first_ok
+    cand = (h.what == INTERSECT) & np.isfinite(h.t)
+    tc = np.where(cand, h.t, np.inf)
+    order = np.lexsort((np.arange(len(ri)), tc, ri))  # per ray: smallest t first, scan order among equals
+    lead = order[np.r_[True, ri[order][1:] != ri[order][:-1]]] if len(order) else order
+    lead = lead[cand[lead]]
+    out = SimpleNamespace(what=np.full(nr, NONE), patch=np.full(nr, 0xFFFFFFFF, np.int64), t=np.full(nr, np.inf),
+                          point=np.zeros((nr, 3)), cs=np.zeros(nr), bary=np.zeros((nr, 3)), normal=np.zeros((nr, 3)),
+                          well=np.zeros(nr, bool))
+    w = ri[lead]
+    out.what[w], out.patch[w], out.t[w], out.cs[w] = INTERSECT, src[lead], h.t[lead], h.cs[lead]
+    out.point[w], out.bary[w], out.normal[w] = h.point[lead], h.bary[lead], h.normal[lead]
+    rival = np.full(nr, np.inf)  # the least finite t on a patch other than the winner's
+    other = cand & (src != out.patch[ri])
+    np.minimum.at(rival, ri[other], h.t[other])
+    out.well[w] = good[lead] & (rival[w] - out.t[w] > SEPARATION_WELL * span)
+    return out
+
+
+# ------------------------------------------------------------------ inputs the CPU and the GPU tests share
+def lens_set(orc):
+    """name -> (patches, x of the rays' origin plane, (y range, z range) of the origins): the four lenses of the
+    per-triple measurements, built with the oracle's Mesh."""
+    from bzr_amd.configs import CONFIGS, Lens, build_lens
+
+    def made(lens):
+        p = build_lens(orc.OMesh, lens).bezier_patches()
+        p.setflags(write=False)
+        return p
+
+    return {
+        "origin": (made(Lens("ellipsoid", 32, 16, (1.0, 4.0, 2.0), (0.0, 0.0, 0.0))), -5.0, ((-5, 5), (-3, 3))),
+        "cfg2": (made(CONFIGS["cfg2"].lenses[0]), 0.0, ((-5, 5), (-3, 3))),
+        "cfg1": (made(CONFIGS["cfg1"].lenses[0]), -5.0, ((-1.5, 1.5), (-1.5, 1.5))),
+        "robot": (made(Lens("stl", split=1)), -100.0, ((-25, 25), (-25, 25))),
+    }
+
+
+def aimed_triples(patches, origin_x, yz, seed, n=8192):
+    """(idx, limit, rays): n triples, each ray aimed at a point of its patch's corner triangle scaled 1.15 x about
+    its centroid, from an origin on the plane x = origin_x; both limits."""
+    rng = np.random.default_rng(seed)
+    idx = rng.integers(0, len(patches), n).astype(np.uint32)
+    limit = rng.integers(0, 2, n).astype(np.uint32)
+    corners = np.asarray(patches)[:, 19:28].reshape(-1, 3, 3).astype(np.float64)[idx]
+    w = rng.dirichlet((1, 1, 1), n)
+    centroid = corners.mean(axis=1)
+    target = centroid + 1.15 * ((corners * w[:, :, None]).sum(axis=1) - centroid)
+    origin = np.stack([np.full(n, float(origin_x)), rng.uniform(*yz[0], n), rng.uniform(*yz[1], n)], 1).astype(np.float32)
+    d = target - origin
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    return idx, limit, np.ascontiguousarray(np.concatenate([origin.T, d.T.astype(np.float32)]).astype(np.float32))
+
+
+def errors(got, ref, sel, span):
+    """Per selected column of the float32 hit rows `got` [13, n] against the binary64 namespace `ref`: t relative,
+    point / span, barycentric and normal maxima."""
+    g = np.asarray(got)[:, sel].astype(np.float64)
+    with np.errstate(all="ignore"):
+        return {
+            "t": np.abs(g[0] - ref.t[sel]) / np.abs(ref.t[sel]),
+            "point": np.abs(g[1:4].T - ref.point[sel]).max(axis=1) / span,
+            "bary": np.abs(g[5:8].T - ref.bary[sel]).max(axis=1),
+            "normal": np.abs(g[8:11].T - ref.normal[sel]).max(axis=1),
+        }
+
+
+def quantiles(err):
+    """{field: (median, p99)}; a non-finite error counts as infinite."""
+    out = {}
+    for k, v in err.items():
+        v = np.where(np.isfinite(v), v, np.inf)
+        out[k] = tuple(float(np.quantile(v, q, method="higher")) for q in (0.5, 0.99)) if len(v) else (0.0, 0.0)
+    return out

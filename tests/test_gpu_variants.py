@@ -25,6 +25,9 @@ with an origin of each tier-boundary class in every wave and the batch with NaN,
 lane, against the oracle on all three modes: the 4-entry stack overflows mid-walk beside a NaN lane, and the per-lane
 walk, the one-level walk and both staged pair layouts see those inputs.
 
+Every variant also runs the cfg2 128^2 chain in BZR_MODE_FAST on both pipelines through tests/test_gpu_fast.py's gates
+against the oracle (status, segments, exit directions): the kFast instantiations of each build.
+
 The variant runs in a child process (BZR_LIBRARY selects the library; one process = one libbzr).
 """
 import json
@@ -62,6 +65,16 @@ for name, mode in (("fused", bzr.PIPELINE_FUSED), ("staged", bzr.PIPELINE_STAGED
     c = ctx.counters_report(); ctx.counters(False)
     out[f"cfg2_{name}_equal"] = all(np.array_equal(bits(g), bits(w)) for g, w in zip(got, want))
     out[f"cfg2_{name}_overflow_rays"] = c["overflow_rays"]
+# BZR_MODE_FAST in this build: the cfg2 128^2 chain through tests/test_gpu_fast.py's gates against the oracle
+rays_f = grid_rays(CONFIGS["cfg2"], side=128)
+wo, ws, wg = orc.trace_chain([lens], [1.3], rays_f)
+for name, mode in (("fused", bzr.PIPELINE_FUSED), ("staged", bzr.PIPELINE_STAGED)):
+    o, s, g = bzr.trace_chain(ctx, [dm], [1.3], rays_f, mode=mode | bzr.MODE_FAST)
+    ok = (s == ws) & (ws != 0)
+    out[f"fast_{name}_status_agree"] = float((s == ws).mean())
+    out[f"fast_{name}_segments_agree"] = float((g == wg).mean())
+    out[f"fast_{name}_exiting"] = int(ok.sum())
+    out[f"fast_{name}_dir_p99"] = float(np.quantile(np.abs(o[3:6][:, ok] - wo[3:6][:, ok]).max(axis=0), 0.99))
 # stacked cfg1 lens (tests/test_gpu_stacked.py's "dup"): 20 copies and the first half of a 21st, every hit an exact tie
 # the first copy wins; 40, 41 and 42 gate passes beside 0 and 80..168, so listed and overflowed rays share waves
 base = build_lens(orc.OMesh, CONFIGS["cfg1"].lenses[0]).bezier_patches()
@@ -169,6 +182,14 @@ def assert_edge_inputs_ran(out):
     assert out["long8_full_length_rays"] >= 2000 and out["edges_beyond_s_max"] > 1000 and out["edges_poisoned"] > 2000, out
 
 
+def assert_fast_gates(out):
+    """BZR_MODE_FAST in the variant build: tests/test_gpu_fast.py's chain gates (cfg2, 128^2) on both pipelines."""
+    for name in ("fused", "staged"):
+        assert out[f"fast_{name}_exiting"] > 1000, out
+        assert out[f"fast_{name}_status_agree"] >= 0.995 and out[f"fast_{name}_segments_agree"] >= 0.99, (name, out)
+        assert out[f"fast_{name}_dir_p99"] < 1e-3, (name, out)
+
+
 @pytest.mark.gpu
 def test_tiny_stack_overflow_path_is_exact():
     lib = PKG / "lib" / "stack4" / "libbzr.so"
@@ -183,6 +204,7 @@ def test_tiny_stack_overflow_path_is_exact():
         if k.endswith("_equal"):
             assert v, (k, out)
     assert_edge_inputs_ran(out)
+    assert_fast_gates(out)
     # the tiny stack really overflowed on both pipelines (the brute-force scan has no stack)
     for k in ("cfg2_fused", "cfg2_staged", "cfg5_fused", "cfg5_staged"):
         assert out[f"{k}_overflow_rays"] > 0, (k, out)
@@ -210,6 +232,7 @@ def test_trace_bundle_walk_is_exact(variant):
         if k.endswith("_equal"):
             assert v, (k, out)
     assert_edge_inputs_ran(out)
+    assert_fast_gates(out)
     assert out["far_overflow_rays"] == out["far_count"]
     assert out["cfg2_fused_overflow_rays"] == 0
     # the stacked lens: k_traverse's walk is the default one; k_trace's one-level-per-batch bundle walk (tracebundle)
@@ -238,6 +261,7 @@ def test_staged_pair_layout_extremes_are_exact(variant):
         if k.endswith("_equal"):
             assert v, (k, out)
     assert_edge_inputs_ran(out)
+    assert_fast_gates(out)
     assert out["stack_fused_overflow_rays"] == 0 and out["stack_staged_overflow_rays"] == out["stack_gate_over_40"] > 0, out
     if variant == "dense1":
         assert out["cfg5_staged_lane_chunks"] == 0, out
