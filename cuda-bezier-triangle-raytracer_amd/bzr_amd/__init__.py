@@ -116,6 +116,8 @@ _SIGS = {
     "bzr_debug_fast_unit": [_P, _P, _U32, _P],
     "bzr_debug_wave_clock": [_P, _P, _U32],
     "bzr_debug_wave_clock_rate": [_P, _P, _U32],
+    "bzr_debug_chunk_plan": [ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(_U32), ctypes.POINTER(_U32)],
+    "bzr_debug_chunk_cap": [_P, _U32, ctypes.POINTER(_U32)],
 }
 _RET = {"bzr_last_error": ctypes.c_char_p, "bzr_abi_version": _I32}
 
@@ -600,9 +602,9 @@ def emit(ctx: Context, em: Emitter, first: int, n: int, rays=None, patch=None):
     return rays, patch
 
 
-def illuminate(ctx: Context, lenses, ri, em: Emitter, total_rays: int, target: Target, hist=None):
+def illuminate(ctx: Context, lenses, ri, em: Emitter, total_rays: int, target: Target, hist=None, mode=MODE_PARITY):
     """Emitter -> bounding-sphere cull -> refraction chain -> target counts.  Returns (hist [bins_v, bins_u]
-    uint32, accumulated into `hist` if given, stats dict)."""
+    uint32, accumulated into `hist` if given, stats dict).  mode: PIPELINE_STAGED / PIPELINE_FUSED, MODE_FAST."""
     nl = len(lenses)
     handles = (_P * nl)(*[m.handle for m in lenses])
     ris = (_F * nl)(*[float(x) for x in ri])
@@ -612,7 +614,7 @@ def illuminate(ctx: Context, lenses, ri, em: Emitter, total_rays: int, target: T
     res = _residency(h)
     with _stream_for(ctx, res):
         _check(lib().bzr_illuminate(ctx.handle, handles, ris, nl, ctypes.byref(em), int(total_rays),
-                                    ctypes.byref(target), h.ptr, stats, res))
+                                    ctypes.byref(target), h.ptr, stats, res | mode))
     return hist, dict(zip(ILLUM_STATS, [int(x) for x in stats]))
 
 

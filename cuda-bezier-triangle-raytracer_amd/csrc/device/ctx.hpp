@@ -31,6 +31,7 @@ struct bzr_ctx {
   double ms[BZR_KERNEL_COUNT] = {};
   uint32_t calls[BZR_KERNEL_COUNT] = {};
   uint32_t chunk_cap = 0;                // staged-path rays per chunk (0: not yet sized, chunk_for)
+  uint32_t chunk_limit = 0;              // test hook (bzr_debug_chunk_cap): lowers chunk_cap while nonzero
   bool counting = false;                 // work counters (bzr_ctx_counters)
   unsigned long long *counters = nullptr;  // device [BZR_COUNTER_COUNT]
   unsigned long long *wave_clock = nullptr;  // test hook (bzr_debug_wave_clock): per k_trace wave, device

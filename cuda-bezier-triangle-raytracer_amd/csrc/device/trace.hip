@@ -2764,18 +2764,29 @@ static_assert(BZR_CHUNK_LOG2 <= 26, "pair records hold a chunk's ray index in 26
 static_assert((uint64_t)kMaxCand * kChunk + 64ull * (kStagedPatchLimit + 1) < (1ull << 32),
               "32-bit pair indices");
 static_assert(kMaxCand <= 64, "winner keys hold a list slot in 6 bits");
-uint32_t chunk_for(bzr_ctx *ctx, uint64_t n) {
-  if (!ctx->chunk_cap) {
-    size_t free_b = 0, total_b = 0;
-    uint64_t cap = kChunk;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b)
-      cap = std::min<uint64_t>(cap, std::max<uint64_t>(free_b / 4 / kWorkBytesPerRay / 64 * 64, 64));
-    ctx->chunk_cap = static_cast<uint32_t>(cap);
-  }
-  const uint64_t cap = ctx->chunk_cap, pieces = (n + cap - 1) / cap;
+// The chunking rule, host arithmetic only (bzr_debug_chunk_plan exports it).  Cap: whole waves, at least one, at most
+// kChunk; free_b == 0 (free memory unknown) gives kChunk.
+uint32_t chunk_cap_of(uint64_t free_b) {
+  uint64_t cap = kChunk;
+  if (free_b) cap = std::min<uint64_t>(cap, std::max<uint64_t>(free_b / 4 / kWorkBytesPerRay / 64 * 64, 64));
+  return static_cast<uint32_t>(cap);
+}
+// Chunk length for n rays under `cap`: n itself when it fits, else equal pieces rounded up to whole waves.
+uint32_t chunk_len(uint64_t n, uint64_t cap) {
+  const uint64_t pieces = (n + cap - 1) / cap;
   if (pieces <= 1) return static_cast<uint32_t>(std::max<uint64_t>(n, 1));
   return static_cast<uint32_t>(std::min<uint64_t>(cap, ((n + pieces - 1) / pieces + 63) / 64 * 64));
 }
+// The cap in force: the automatic one (sized once), lowered by the test hook bzr_debug_chunk_cap if set.
+uint32_t chunk_cap(bzr_ctx *ctx) {
+  if (!ctx->chunk_cap) {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+    ctx->chunk_cap = chunk_cap_of(free_b);
+  }
+  return ctx->chunk_limit ? std::min(ctx->chunk_cap, ctx->chunk_limit) : ctx->chunk_cap;
+}
+uint32_t chunk_for(bzr_ctx *ctx, uint64_t n) { return chunk_len(n, chunk_cap(ctx)); }
 
 // One BezierMesh::intersect per ray of rays [off, off + n) (+ refraction, per kMode).
 template <int kMode, bool kFast>
@@ -3581,6 +3592,22 @@ extern "C" bzr_status bzr_debug_div_heights(void *ctxp, const float *a, uint32_t
   DeviceGuard g(ctx->device);
   hipLaunchKernelGGL(k_debug_div_heights, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, a, n, out);
   BZR_HIP(hipGetLastError());
+  return BZR_OK;
+}
+
+extern "C" bzr_status bzr_debug_chunk_plan(uint64_t free_bytes, uint64_t n, uint32_t *cap, uint32_t *chunk) {
+  if (!cap || !chunk) return set_error(BZR_ERR_INVALID_ARGUMENT, "null argument");
+  *cap = chunk_cap_of(free_bytes);
+  *chunk = chunk_len(n, *cap);
+  return BZR_OK;
+}
+
+extern "C" bzr_status bzr_debug_chunk_cap(void *ctxp, uint32_t rays, uint32_t *effective) {
+  bzr_ctx *ctx = static_cast<bzr_ctx *>(ctxp);
+  if (!ctx) return set_error(BZR_ERR_INVALID_ARGUMENT, "null context");
+  DeviceGuard g(ctx->device);
+  ctx->chunk_limit = rays ? std::max(rays / 64u * 64u, 64u) : 0u;
+  if (effective) *effective = chunk_cap(ctx);
   return BZR_OK;
 }
 

@@ -60,6 +60,17 @@ int32_t bzr_debug_div_heights(void *ctx, const float *a, uint32_t n, float *out)
  * device memory [5][n]: row 0 fast::div_rn(a0, a1), row 1 fast::sqrt_rn(|a0|), rows 2-4 fast::normalized(a).
  * Asynchronous on the context's stream. */
 int32_t bzr_debug_fast_unit(void *ctx, const float *a, uint32_t n, float *out);
+/* The staged path's chunking rule as pure host arithmetic (no device): *cap = the rays-per-chunk cap for a device with
+ * `free_bytes` free (whole waves, at least 64, at most 2^BZR_CHUNK_LOG2 = 8 M; a quarter of the free memory at the
+ * workspace's bytes per ray; free_bytes == 0 means unknown and gives the ceiling), *chunk = the chunk length for a
+ * batch of n rays under that cap (n itself when it fits, else equal pieces rounded up to whole waves, never above
+ * the cap; the last chunk is ragged). */
+int32_t bzr_debug_chunk_plan(uint64_t free_bytes, uint64_t n, uint32_t *cap, uint32_t *chunk);
+/* Lowers the context's chunk cap for the following calls (staged calls and bzr_illuminate's batches): the cap in
+ * force becomes `rays` rounded down to whole waves, at least 64, and never above the cap the context derives itself
+ * (free memory at its first staged call, 8 M).  rays == 0 restores the automatic cap.  *effective (optional) = the
+ * cap now in force (asking for it sizes the automatic cap now if no staged call has yet).  ctx is a bzr_ctx* (bzr.h). */
+int32_t bzr_debug_chunk_cap(void *ctx, uint32_t rays, uint32_t *effective);
 /* Per-wave timing of the fused kernel: while set, every fused call (k_trace, one 64-ray wave per 64
  * consecutive rays) of `n` <= 64 * waves rays writes clock[2w] = the wave's start (s_memtime ticks) and
  * clock[2w+1] = its duration, for wave w = ray index / 64.  `clock` is device memory; NULL turns it off.

@@ -125,7 +125,9 @@ def test_illuminate_with_an_always_listed_patch(bzr, orc, ctx):
 
 @pytest.mark.slow
 def test_illuminate_two_batches(bzr, orc, ctx):
-    """More rays than one 1M-ray batch: the batches continue the global ray numbering."""
+    """1 051 576 rays, once more than one batch: bzr_illuminate's batch is now the staged chunk size (up to 8 M rays on
+    a free device), so this runs as one fused batch (>= 256 rays per patch of the 3 072).  The batch loop's second
+    pass is tests/test_gpu_chunks.py's part, under a lowered cap."""
     cfg = CONFIGS["cfg2"]
     lens = build_lens(bzr.TriMesh, cfg.lenses[0]).bezier_patches()
     n = (1 << 20) + 3000

@@ -28,6 +28,10 @@ walk, the one-level walk and both staged pair layouts see those inputs.
 Every variant also runs the cfg2 128^2 chain in BZR_MODE_FAST on both pipelines through tests/test_gpu_fast.py's gates
 against the oracle (status, segments, exit directions): the kFast instantiations of each build.
 
+Every variant last lowers the staged chunk cap to 192 rays (bzr_debug_chunk_cap, tests/test_gpu_chunks.py) and runs the
+staged stacked-lens, tier-boundary and garbage jobs again against the same oracle words: the 4-entry stack's mid-walk
+overflow and both pair-layout extremes at chunk offsets other than zero, 6 to 68 chunks per call.
+
 The variant runs in a child process (BZR_LIBRARY selects the library; one process = one libbzr).
 """
 import json
@@ -109,12 +113,13 @@ out["edges_beyond_s_max"] = int((np.abs(tier_mix[:3]).max(axis=0) > s_max).sum()
 out["edges_poisoned"] = int(third_mask.sum())
 jobs = [("long8", tl.chain_rays(), "chain8"), ("tiers", tier_mix, "intersect"), ("tiers", tier_mix, "chain1"),
         ("third", third, "intersect"), ("third", third, "chain1")]
+wants = {}
 for label, rr, op in jobs:
     if op == "chain8":
         want_e = [bits(a) for a in orc.trace_chain(l8, [1.3] * tl.N_LENS, rr)]
         out["long8_full_length_rays"] = int((want_e[2] == 16).sum())
     else:
-        want_e = te.run_orc(orc, l8, op, rr)[0]
+        want_e = wants[(label, op)] = te.run_orc(orc, l8, op, rr)[0]
     for name, mode in (("fused", bzr.PIPELINE_FUSED), ("staged", bzr.PIPELINE_STAGED), ("brute", bzr.ACCEL_NONE)):
         if op == "chain8":
             got_e = [bits(a) for a in bzr.trace_chain(ctx, d8, [1.3] * tl.N_LENS, rr, mode=mode)]
@@ -170,6 +175,22 @@ if "--more" in sys.argv:
     out["far_fused_equal"] = bool(np.array_equal(gf, bits(orc.intersect(lr, rr))))
     out["far_overflow_rays"] = cnt["overflow_rays"]
     out["far_count"] = int(far.sum())
+# the staged stack, tiers and third jobs again in chunks of at most 192 rays (bzr_debug_chunk_cap, tests/test_gpu_chunks.py),
+# against the oracle words computed above: this build's overflow paths and pair layout at chunk offsets other than zero
+import ctypes
+eff = ctypes.c_uint32(0)
+assert bzr.lib().bzr_debug_chunk_cap(ctx.handle, 192, ctypes.byref(eff)) == 0
+out["chunk_cap"] = eff.value
+ctx.counters(True); ctx.counters_report()
+got = bits(bzr.intersect(ctx, dms, rs, mode=bzr.PIPELINE_STAGED))
+c = ctx.counters_report(); ctx.counters(False)
+out["stack_staged192_equal"] = bool(np.array_equal(got, want_hit))
+out["stack_staged192_overflow_rays"] = c["overflow_rays"]
+got = bzr.trace_chain(ctx, [dms], [1.3], rs, mode=bzr.PIPELINE_STAGED)
+out["stack_staged192_chain_equal"] = all(np.array_equal(bits(g), bits(w)) for g, w in zip(got, want_chain))
+for label, rr, op in jobs[1:]:
+    got_e = te.run_gpu(bzr, ctx, d8, op, rr, bzr.PIPELINE_STAGED)
+    out[f"{label}_{op}_staged192_equal"] = not bool(te.differing(got_e, wants[(label, op)]).any())
 print(json.dumps(out))
 """
 
@@ -178,7 +199,9 @@ def assert_edge_inputs_ran(out):
     """The long chain, the tier boundaries and the garbage lanes were traced on all three modes, over the populations
     tests/test_gpu_long_chains.py and tests/test_gpu_ray_edges.py assert."""
     keys = [k for k in out if k.endswith("_equal") and k.split("_")[0] in ("long8", "tiers", "third")]
-    assert len(keys) == 15, keys
+    assert len(keys) == 19, keys  # 5 jobs x 3 modes, and the tiers and third jobs staged in chunks of 192 rays
+    assert out["chunk_cap"] == 192 and "stack_staged192_equal" in out and "stack_staged192_chain_equal" in out, out
+    assert out["stack_staged192_overflow_rays"] == out["stack_staged_overflow_rays"], out
     assert out["long8_full_length_rays"] >= 2000 and out["edges_beyond_s_max"] > 1000 and out["edges_poisoned"] > 2000, out
 
 
