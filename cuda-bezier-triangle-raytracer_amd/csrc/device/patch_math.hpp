@@ -250,8 +250,9 @@ using namespace exact;
 // kGated: the caller has already evaluated the planar gate (:124-131) with this same arithmetic and
 // it passed (the culled pipeline's candidates), so its early returns are skipped -- same result bits.
 // kFast: the gate stays exact (same candidates as the reference), the rest runs in fast::.
-template <bool kGated = false, bool kFast = false, typename P>
-__device__ __forceinline__ Hit patch_intersect(const P &p, f3 s, f3 d, bool limitNone) {
+// need: newton_tail's hook (whether the last iteration's normal is evaluated; default: always).
+template <bool kGated = false, bool kFast = false, typename P, typename Need = NormalAlways>
+__device__ __forceinline__ Hit patch_intersect(const P &p, f3 s, f3 d, bool limitNone, Need need = Need()) {
   Hit h;
   h.t = 0.0f;
   h.point = mk(0.0f, 0.0f, 0.0f);
@@ -272,8 +273,8 @@ __device__ __forceinline__ Hit patch_intersect(const P &p, f3 s, f3 d, bool limi
     const bool in = (b0.x >= 0.0f) & (b0.x <= 1.0f) & (b0.y >= 0.0f) & (b0.y <= 1.0f) & (b0.z >= 0.0f) & (b0.z <= 1.0f);
     const bool ok = valid & (fabsf(it) > -p.hin()) & (fabsf(it) > p.hout()) & (limitNone | in);
     Hit r;
-    if constexpr (kFast) r = fast::newton_tail(p, s, d, ic, it);
-    else r = newton_tail(p, s, d, ic, it);
+    if constexpr (kFast) r = fast::newton_tail(p, s, d, ic, it, need);
+    else r = newton_tail(p, s, d, ic, it, need);
     return ok ? r : h;
   }
 #endif
@@ -283,8 +284,8 @@ __device__ __forceinline__ Hit patch_intersect(const P &p, f3 s, f3 d, bool limi
     if (!(limitNone || (b0.x >= 0.0f && b0.x <= 1.0f && b0.y >= 0.0f && b0.y <= 1.0f && b0.z >= 0.0f && b0.z <= 1.0f)))
       return h;
   }
-  if constexpr (kFast) return fast::newton_tail(p, s, d, ic, it);
-  else return newton_tail(p, s, d, ic, it);
+  if constexpr (kFast) return fast::newton_tail(p, s, d, ic, it, need);
+  else return newton_tail(p, s, d, ic, it, need);
 }
 
 }  // namespace bzr_dev

@@ -84,8 +84,17 @@ __device__ __forceinline__ f3 surface_normal(const P &p, f3 b) {
 // BezierTriangle::intersect after its planar gate (reference/bezierTriangle.cpp:132-195): bracket,
 // secant start, Newton steps, acceptance and the divider-plane classification.  (ic, it) are the
 // gate's plane cosine and distance.
-template <typename P>
-__device__ __forceinline__ Hit newton_tail(const P &p, f3 s, f3 d, float ic, float it) {
+// `need` decides whether the last iteration evaluates its surface normal.  That iteration's `middle` is
+// the returned h.t, and its normal feeds h.normal and h.cs only -- the acceptance test and the divider
+// classification read h.point -- so a caller that knows h.t cannot win (trace.hip trace_segment's vote)
+// skips it: h.normal and h.cs are then zero (callers must not rely on that), everything else has the same
+// bits.  need(h.t) must be wave-uniform on the device.  NormalAlways (the default) is plain C++: the body
+// also compiles for the host.
+struct NormalAlways {
+  __device__ __forceinline__ bool operator()(float) const { return true; }
+};
+template <typename P, typename Need = NormalAlways>
+__device__ __forceinline__ Hit newton_tail(const P &p, f3 s, f3 d, float ic, float it, Need need = Need()) {
   Hit h;
   h.t = 0.0f;
   h.point = mk(0.0f, 0.0f, 0.0f);
@@ -113,7 +122,7 @@ __device__ __forceinline__ Hit newton_tail(const P &p, f3 s, f3 d, float ic, flo
 #if BZR_NEWTON_UNROLL
 #pragma unroll
 #endif
-  for (int i = 0; i < BZR_NEWTON_ITERS; ++i) {  // csRootSearchIterations
+  for (int i = 0; i + 1 < BZR_NEWTON_ITERS; ++i) {  // csRootSearchIterations, all but the last
     h.t = middle;
     por = add(s, scale(d, middle));
     f3 pp;
@@ -128,21 +137,36 @@ __device__ __forceinline__ Hit newton_tail(const P &p, f3 s, f3 d, float ic, flo
     BZR_NEWTON_PROBE(i, middle, pdir);  // host experiments only (scripts/newton_fixpoint.cpp)
 #endif
   }
+  // The last iteration.  Its Newton step is never taken, so what it leaves is h.t (the t it enters with), the
+  // barycentrics, the point and the normal; the normal comes last, behind everything that reads the point, and
+  // only when the caller needs it.
+  h.t = middle;
+  por = add(s, scale(d, middle));
+  f3 pp;
+  float pc, pt;
+  plane_ray(p.n(), p.c(), por, pdir, pp, pc, pt);
+  h.bary = matvec(p, pp);
+  h.point = interpolate(p, h.bary);
   f3 rel = sub(h.point, s);
   f3 perp = sub(rel, scale(d, dot(rel, d)));
-  if (sqrt_above_hundredth(dot(perp, perp)) || h.t < (further - closer) * 1.0f) {  // norm(perp) > 0.01f
-    h.what = kNone;
-    return h;
+  uint32_t what = kNone;
+  if (!(sqrt_above_hundredth(dot(perp, perp)) || h.t < (further - closer) * 1.0f)) {  // norm(perp) > 0.01f: none
+    uint32_t out = plane_distance(p.dn(0), p.dc(0), h.point) < 0.0f ? 1u : 0u;
+    out |= plane_distance(p.dn(1), p.dc(1), h.point) < 0.0f ? 2u : 0u;
+    out |= plane_distance(p.dn(2), p.dc(2), h.point) < 0.0f ? 4u : 0u;
+    what = out == 1u ? 0u : (out == 2u ? 1u : (out == 4u ? 2u : kIntersect));
   }
-  uint32_t out = plane_distance(p.dn(0), p.dc(0), h.point) < 0.0f ? 1u : 0u;
-  out |= plane_distance(p.dn(1), p.dc(1), h.point) < 0.0f ? 2u : 0u;
-  out |= plane_distance(p.dn(2), p.dc(2), h.point) < 0.0f ? 4u : 0u;
-  if (out == 1u) h.what = 0u;
-  else if (out == 2u) h.what = 1u;
-  else if (out == 4u) h.what = 2u;
-  else {
-    h.what = kIntersect;
-    h.cs = dot(d, h.normal);
+  h.what = what;
+  if (need(h.t)) {
+    h.normal = surface_normal(p, h.bary);
+    if (what == kIntersect) h.cs = dot(d, h.normal);
+#ifdef BZR_NEWTON_PROBE
+    pdir = normalized(sub(h.point, pp));
+    middle = div_rn(dot(sub(h.point, s), h.normal), dot(d, h.normal));
+    BZR_NEWTON_PROBE(BZR_NEWTON_ITERS - 1, middle, pdir);
+#endif
+  } else {
+    h.normal = mk(0.0f, 0.0f, 0.0f);  // (not the previous iteration's, which would stay live to here)
   }
   return h;
 }

@@ -286,7 +286,8 @@ __device__ __forceinline__ Hit no_hit() {
 
 // Planar gate of BezierTriangle::intersect with cThis (reference/bezierTriangle.cpp:124-131),
 // evaluated from the 64-byte scan record; same arithmetic as patch_intersect's first lines.
-__device__ __forceinline__ bool planar_gate(float4 q0, float4 q1, float4 q2, float4 q3, f3 s, f3 d) {
+// `gt` gets the plane distance t (whatever the decision).
+__device__ __forceinline__ bool planar_gate(float4 q0, float4 q1, float4 q2, float4 q3, f3 s, f3 d, float &gt) {
 #if BZR_GATE_FLAT
   // Branch-free: every term is evaluated and the conditions are combined with '&' (the same decision as
   // plane_ray's early outs below -- a lane with |cos| < 1e-5 fails whatever its t), so the walk runs no
@@ -295,6 +296,7 @@ __device__ __forceinline__ bool planar_gate(float4 q0, float4 q1, float4 q2, flo
   const float cs = dot(d, n);
   const float t = div_rn(q0.w - dot(n, s), cs);
   const f3 ip = add(s, scale(d, t));
+  gt = t;
   const bool valid = (fabsf(cs) >= 0.00001f) & (t > 0.0f) & (fabsf(t) > -q1.x) & (fabsf(t) > q1.y);
   const float b0 = q1.z * ip.x + (q1.w * ip.y + q2.x * ip.z);
   const float b1 = q2.y * ip.x + (q2.z * ip.y + q2.w * ip.z);
@@ -305,6 +307,7 @@ __device__ __forceinline__ bool planar_gate(float4 q0, float4 q1, float4 q2, flo
   f3 ip;
   float ic, it;
   bool valid = plane_ray(n, q0.w, s, d, ip, ic, it);
+  gt = it;
   if (!(valid && fabsf(it) > -q1.x && fabsf(it) > q1.y)) return false;
   // row-major copy of M: rows (q1.z q1.w q2.x) (q2.y q2.z q2.w) (q3.x q3.y q3.z)
   float b0 = q1.z * ip.x + (q1.w * ip.y + q2.x * ip.z);
@@ -312,6 +315,10 @@ __device__ __forceinline__ bool planar_gate(float4 q0, float4 q1, float4 q2, flo
   float b2 = q3.x * ip.x + (q3.y * ip.y + q3.z * ip.z);
   return b0 >= 0.0f && b0 <= 1.0f && b1 >= 0.0f && b1 <= 1.0f && b2 >= 0.0f && b2 <= 1.0f;
 #endif
+}
+__device__ __forceinline__ bool planar_gate(float4 q0, float4 q1, float4 q2, float4 q3, f3 s, f3 d) {
+  float gt;
+  return planar_gate(q0, q1, q2, q3, s, d, gt);
 }
 
 // One iteration of the reference loop body: patch b with cThis, and on a follow-side result its
@@ -619,8 +626,11 @@ typedef __attribute__((address_space(4))) const u32x8 cu32x8;
 //      [L - B|p~| - C(|s|+|p~|), H + ...] at p~ = s + d (num x rcp(cs)) -- ~3 % of cfg5's pairs pass.
 // Only then the exact gate (the division and fl(M p)), so the always list costs ~25 VALU per pair
 // instead of ~50.  Same candidates as the gate alone.
-__device__ __forceinline__ bool always_gate_rec(const u32x16 &r, const u32x8 &wq, bool act, f3 s, f3 d, uint32_t &patch) {
+// `gt` gets the gate's plane distance t for the lanes that pass.
+__device__ __forceinline__ bool always_gate_rec(const u32x16 &r, const u32x8 &wq, bool act, f3 s, f3 d, uint32_t &patch,
+                                                float &gt) {
   patch = r[15];
+  gt = 0.0f;
   const float4 q0 = leaf_q(r, 0);
   const f3 n = mk(q0.x, q0.y, q0.z);
   const float cs = dot(d, n), num = q0.w - dot(n, s);
@@ -635,12 +645,21 @@ __device__ __forceinline__ bool always_gate_rec(const u32x16 &r, const u32x8 &wq
   const float slack = __builtin_fmaf(__uint_as_float(wq[5]), pm, __uint_as_float(wq[6]) * (sm + pm));
   keep &= !(w > __uint_as_float(wq[4]) + slack) & !(w < __uint_as_float(wq[3]) - slack);
   if (!__any(keep)) return false;
-  return keep & planar_gate(q0, leaf_q(r, 1), leaf_q(r, 2), leaf_q(r, 3), s, d);
+  return keep & planar_gate(q0, leaf_q(r, 1), leaf_q(r, 2), leaf_q(r, 3), s, d, gt);
 }
-__device__ __forceinline__ bool always_gate(const float4 *always, uint32_t k, bool act, f3 s, f3 d, uint32_t &patch) {
+__device__ __forceinline__ bool always_gate_rec(const u32x16 &r, const u32x8 &wq, bool act, f3 s, f3 d, uint32_t &patch) {
+  float gt;
+  return always_gate_rec(r, wq, act, s, d, patch, gt);
+}
+__device__ __forceinline__ bool always_gate(const float4 *always, uint32_t k, bool act, f3 s, f3 d, uint32_t &patch,
+                                            float &gt) {
   const u32x16 r = *((const cu32x16 *)(uintptr_t)(always + (size_t)kAlwaysQuads * k));
   const u32x8 wq = *((const cu32x8 *)(uintptr_t)(always + (size_t)kAlwaysQuads * k + 4));
-  return always_gate_rec(r, wq, act, s, d, patch);
+  return always_gate_rec(r, wq, act, s, d, patch, gt);
+}
+__device__ __forceinline__ bool always_gate(const float4 *always, uint32_t k, bool act, f3 s, f3 d, uint32_t &patch) {
+  float gt;
+  return always_gate(always, k, act, s, d, patch, gt);
 }
 
 // Wave-level pre-test of the always list.  The active rays of a wave form a bundle: origins in the box
@@ -1786,6 +1805,7 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_small(const uint32_t *__r
 // (same Newton site, patches in index order).
 struct TraceCtr {  // wave-uniform work counters (kCount)
   uint32_t nodes = 0, leaves = 0, gate_tests = 0, rounds = 0, pairs = 0, follows = 0, segments = 0, ovf = 0;
+  uint32_t shorts = 0;  // passes that skipped the last Newton normal (BZR_TRACE_SHORT)
   uint32_t rounds_odd = 0, runs_odd = 0;  // odd chain segments (a lens's back surface): passes, pairs + follows
 };
 // BZR_TRACE_PRIO (default 3; 0 = off): wave priority (s_setprio) of k_trace's BVH walk phase, back to 0
@@ -1816,6 +1836,24 @@ struct TraceCtr {  // wave-uniform work counters (kCount)
 #ifndef BZR_TRACE_PARK_HITS
 #define BZR_TRACE_PARK_HITS 1
 #endif
+// BZR_TRACE_SHORT (default 1; 0 = off): a Newton pass none of whose lanes can win skips the last iteration's
+// surface normal (newton_tail's hook).  The last iteration enters with the t it returns, so each lane knows its
+// key (t order, scanned patch) before that iteration: when no lane of the pass has a key below its running best
+// -- and none is a parking lane, whose result must be whole -- consider() would drop every result, and the
+// normal and cosine only it reads are not evaluated.  On entering a lens most rays pass the gates of a front
+// and a back patch, and the back patch's pass loses once the front one has run.  The vote is wave-uniform
+// (__any over the lanes in the call) and takes the same decision consider() takes: no output bit depends on it.
+// A losing pass is only short when its lanes' winners ran before it, so with 1 a batch of collected leaves is
+// first put in the order of their gates' plane distance (each entry's first passing lane's), near side first:
+// a stable lane-parallel rank over the <= kEntries entries.  The winner is the minimum of (t order, scanned
+// patch) over a set, so the order of the passes cannot reach it.  2: the vote without the reorder.
+// cfg4: 26 % of the passes short (17.6 % with 2), each 242 of 2 130 VALU shorter; bench.py 11 503 -> 11 699 Mrays/s,
+// lone frames 4.344 -> 4.271 ms (2: 4.299); cfg2 in flight +2.9 %, lone frames 0.400 -> 0.414 ms
+// (profiles/r07_bench_ab.jsonl, r07_ab_short_cfg{4,2}.jsonl).
+#ifndef BZR_TRACE_SHORT
+#define BZR_TRACE_SHORT 1
+#endif
+static_assert(BZR_TRACE_SHORT >= 0 && BZR_TRACE_SHORT <= 2, "BZR_TRACE_SHORT: 0, 1 or 2");
 constexpr uint32_t kEntries = BZR_TRACE_ENTRIES;  // collected leaves per batch: power of two, <= 64
 static_assert(kEntries >= 4 && kEntries <= 64 && (kEntries & (kEntries - 1)) == 0, "kEntries");
 // Words kept per lane: the winner (all of BezierIntersection for kModeHits; what refraction reads
@@ -1838,6 +1876,9 @@ struct TraceLds {  // per wave
   unsigned long long emask[kEntries];        // collected leaves: gate ballot
   float bundle[kBundleWords];                // the always list's ray bundle (always_bundle_keep)
   uint32_t eid[kEntries];                    // and patch index
+#if BZR_TRACE_SHORT == 1
+  uint32_t ekey[kEntries];                   // and order key (entry_key): the passes run near side first
+#endif
 #if BZR_TRACE_BUNDLE
   uint32_t pend[64];                         // the bundle walk's queued leaf slots
 #endif
@@ -1883,6 +1924,33 @@ __device__ __forceinline__ void consider(const Hit &h, uint32_t scan, uint32_t s
       }
     }
   }
+}
+
+// newton_tail's hook for a pass of trace_segment: the last normal is needed when some lane of the call may
+// still win -- a parking lane (`spec`: its result is kept whole), or a lane whose key, from the t that enters
+// the last iteration and the scanned patch consider() will get, is below its best.  A NaN t cannot win, as in
+// consider(); best == ~0 loses to every finite key.  `skipped` records a "no" for the counters.
+struct PassVote {
+  unsigned long long best;
+  uint32_t scan;
+  bool spec;
+  bool *skipped;
+  __device__ __forceinline__ bool operator()(float t) const {
+#if BZR_TRACE_SHORT
+    const bool may = spec || (t < FLT_MAX && (((unsigned long long)t_order(t) << 32) | scan) < best);
+    const bool any = __any(may);
+    *skipped = !any;
+    return any;
+#else
+    (void)t;
+    return true;
+#endif
+  }
+};
+
+// Order key of a collected entry: the gate's plane distance of its first passing lane (pm: the gate ballot).
+__device__ __forceinline__ uint32_t entry_key(float gt, unsigned long long pm) {
+  return t_order(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(gt), (int)__builtin_ctzll(pm))));
 }
 
 // The lane's winner back from LDS (best != ~0).
@@ -1947,6 +2015,7 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
   constexpr bool kPark = TraceWords<kMode>::kPark > 0;
   constexpr uint32_t kNo = 0xFFFFFFFFu;
   constexpr int kCap = TraceWords<kMode>::kStackCap;
+  constexpr bool kOrder = BZR_TRACE_SHORT == 1;  // the batch's passes near side first
   best = ~0ull;
   const float amax = fmaxf(fmaxf(fabsf(s.x), fabsf(s.y)), fabsf(s.z));
   bool ovf = false;  // this lane takes the in-order full scan
@@ -2005,16 +2074,22 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
         const uint32_t slot = __builtin_amdgcn_readfirstlane(L.pend[pi]);
         ++pi;
         const u32x16 r = *((const cu32x16 *)(uintptr_t)leaf + slot);
-        const bool pass = act & planar_gate(leaf_q(r, 0), leaf_q(r, 1), leaf_q(r, 2), leaf_q(r, 3), s, d);
+        float gt;
+        const bool pass = act & planar_gate(leaf_q(r, 0), leaf_q(r, 1), leaf_q(r, 2), leaf_q(r, 3), s, d, gt);
         if (kCount) {
           ++ctr.leaves;
           ctr.gate_tests += popc64(__ballot(act));
         }
         const unsigned long long pm = __ballot(pass);
         if (pm) {
+          const uint32_t key = kOrder ? entry_key(gt, pm) : 0u;
+          (void)key;
           if (lane == 0u) {
             L.eid[ne] = r[15];
             L.emask[ne] = pm;
+#if BZR_TRACE_SHORT == 1
+            L.ekey[ne] = key;
+#endif
           }
           ++ne;
         }
@@ -2076,17 +2151,22 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
           const float4 g1 = make_float4(__uint_as_float(r[4]), __uint_as_float(r[5]), __uint_as_float(r[6]), __uint_as_float(r[7]));
           const float4 g2 = make_float4(__uint_as_float(r[8]), __uint_as_float(r[9]), __uint_as_float(r[10]), __uint_as_float(r[11]));
           const float4 g3 = make_float4(__uint_as_float(r[12]), __uint_as_float(r[13]), __uint_as_float(r[14]), 0.0f);
-          const bool pass = hit[c] & planar_gate(g0, g1, g2, g3, s, d)
-              ;
+          float gt;
+          const bool pass = hit[c] & planar_gate(g0, g1, g2, g3, s, d, gt);
           if (kCount) {
             ++ctr.leaves;
             ctr.gate_tests += popc64(hm);
           }
           const unsigned long long pm = __ballot(pass);
           if (pm) {
+            const uint32_t key = kOrder ? entry_key(gt, pm) : 0u;
+            (void)key;
             if (lane == 0u) {
               L.eid[ne] = r[15];
               L.emask[ne] = pm;
+#if BZR_TRACE_SHORT == 1
+              L.ekey[ne] = key;
+#endif
             }
             ++ne;
           }
@@ -2114,16 +2194,22 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
       const uint32_t k = (ab - 1u) * 64u + __builtin_ctzll(am);
       am &= am - 1ull;
       uint32_t b;
-      const bool pass = always_gate(m.always, k, act, s, d, b);
+      float gt;
+      const bool pass = always_gate(m.always, k, act, s, d, b, gt);
       if (kCount) {
         ++ctr.leaves;
         ctr.gate_tests += popc64(__ballot(act));
       }
       const unsigned long long pm = __ballot(pass);
       if (pm) {
+        const uint32_t key = kOrder ? entry_key(gt, pm) : 0u;
+        (void)key;
         if (lane == 0u) {
           L.eid[ne] = b;
           L.emask[ne] = pm;
+#if BZR_TRACE_SHORT == 1
+          L.ekey[ne] = key;
+#endif
         }
         ++ne;
       }
@@ -2155,6 +2241,29 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
 #if BZR_TRACE_PRIO
     __builtin_amdgcn_s_setprio(0);
 #endif
+    if (kOrder && ne >= 2u) {
+      // near side first: lane e < ne ranks entry e among the batch's keys (stable: ties keep their order) and
+      // moves its index and ballot to that place; the join and park logic below sees the permuted list only
+      const uint32_t slot = lane & (kEntries - 1u);
+#if BZR_TRACE_SHORT == 1
+      const uint32_t ekey = L.ekey[slot];
+#else
+      const uint32_t ekey = 0u;
+#endif
+      uint32_t rank = 0;  // < ne for the lanes below ne: a permutation of [0, ne)
+      for (uint32_t j = 0; j < ne; ++j) {
+        const uint32_t kj = (uint32_t)__builtin_amdgcn_readlane((int)ekey, (int)j);
+        rank += (kj < ekey || (kj == ekey && j < lane)) ? 1u : 0u;
+      }
+      const uint32_t id = L.eid[slot];
+      const unsigned long long em = L.emask[slot];
+      __builtin_amdgcn_wave_barrier();
+      if (lane < ne) {
+        L.eid[rank] = id;
+        L.emask[rank] = em;
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
     for (uint32_t e = 0; e < ne; ++e) {
       const uint32_t b = __builtin_amdgcn_readfirstlane(L.eid[e]);
       const auto hp = uniform_patch(m.full, b);
@@ -2179,8 +2288,9 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
         ctr.follows += popc64(__ballot(joined));
       }
       uint32_t what = kNone;
+      bool skipped = false;
       if (run0 || joined || spec) {
-        const Hit h = patch_intersect<false, kFast>(hp, s, d, joined || spec);
+        const Hit h = patch_intersect<false, kFast>(hp, s, d, joined || spec, PassVote{best, sidx, spec, &skipped});
         if (spec) {
           park(h, L, lane);
           parked_nb = b;
@@ -2189,6 +2299,7 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
           if (!joined) what = h.what;
         }
       }
+      if (kCount && __any(skipped)) ++ctr.shorts;
       for (uint32_t side = 0; side < 3u; ++side) {
         bool fl = run0 && what == side;
         if (!__any(fl)) continue;
@@ -2218,10 +2329,12 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
           ctr.follows += popc64(__ballot(fl));
         }
         const auto pa = uniform_patch(m.full, nb);
+        skipped = false;
         if (fl) {
-          const Hit h = patch_intersect<false, kFast>(pa, s, d, true);
+          const Hit h = patch_intersect<false, kFast>(pa, s, d, true, PassVote{best, b, false, &skipped});
           consider(h, b, nb, best, L, lane);
         }
+        if (kCount && __any(skipped)) ++ctr.shorts;
       }
     }
   }
@@ -2425,15 +2538,16 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
       job.wave_clock[2 * (i >> 6) + 1] = t_end - t_start;
     }
   }
-  if (kCount && lane < 10u) {  // one atomic per counter per wave, spread over kCounterReplicas copies
-    const uint32_t v[10] = {ctr.segments, ctr.pairs, ctr.follows, ctr.ovf, ctr.nodes, ctr.leaves, ctr.gate_tests,
-                            ctr.rounds, ctr.rounds_odd, ctr.runs_odd};
-    const uint32_t id[10] = {BZR_COUNTER_SEGMENTS, BZR_COUNTER_PAIRS, BZR_COUNTER_FOLLOWS, BZR_COUNTER_OVERFLOW_RAYS,
+  if (kCount && lane < 11u) {  // one atomic per counter per wave, spread over kCounterReplicas copies
+    const uint32_t v[11] = {ctr.segments, ctr.pairs, ctr.follows, ctr.ovf, ctr.nodes, ctr.leaves, ctr.gate_tests,
+                            ctr.rounds, ctr.rounds_odd, ctr.runs_odd, ctr.shorts};
+    const uint32_t id[11] = {BZR_COUNTER_SEGMENTS, BZR_COUNTER_PAIRS, BZR_COUNTER_FOLLOWS, BZR_COUNTER_OVERFLOW_RAYS,
                              BZR_COUNTER_NODE_VISITS, BZR_COUNTER_LEAF_FETCHES, BZR_COUNTER_GATE_TESTS,
-                             BZR_COUNTER_NEWTON_ROUNDS, BZR_COUNTER_ROUNDS_ODD, BZR_COUNTER_RUNS_ODD};
+                             BZR_COUNTER_NEWTON_ROUNDS, BZR_COUNTER_ROUNDS_ODD, BZR_COUNTER_RUNS_ODD,
+                             BZR_COUNTER_SHORT_PASSES};
     uint32_t mine = 0, which = 0;
 #pragma unroll
-    for (uint32_t k = 0; k < 10u; ++k)
+    for (uint32_t k = 0; k < 11u; ++k)
       if (lane == k) {
         mine = v[k];
         which = id[k];

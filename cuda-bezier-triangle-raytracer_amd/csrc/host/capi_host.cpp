@@ -7,6 +7,7 @@
 #include <string>
 
 #include "bzr/bzr.hpp"
+#include "single_ray.hpp"
 
 extern "C" void bzr_internal_set_error(const char *msg);
 
@@ -177,6 +178,26 @@ bzr_status bzr_bezier_interpolate(const bzr_trimesh *m, int32_t divisor, bzr_tri
   if (!m || !out) return bad("null argument");
   if (divisor < 1) return bad("divisor must be >= 1");
   return guarded([&] { out->mesh = BezierMesh(m->mesh).interpolate(divisor); });
+}
+
+// include/bzr_debug.h
+int32_t bzr_debug_newton_short(const void *patches, uint32_t n, uint32_t stride, const uint32_t *patch,
+                               const float *rays, const uint8_t *limit, uint32_t m, float *full, float *skipped) {
+  if ((!patches && n) || ((!patch || !rays || !limit || !full || !skipped) && m)) return bad("null argument");
+  if (stride < sizeof(bzr_patch) || stride % 4u) return bad("stride");
+  for (uint32_t i = 0; i < m; ++i)
+    if (patch[i] >= n) return bad("patch index out of range");
+  for (uint32_t i = 0; i < m; ++i) {
+    const float *rec = reinterpret_cast<const float *>(static_cast<const char *>(patches) + (std::size_t)stride * patch[i]);
+    const float ray[6] = {rays[i],
+                          rays[(std::size_t)m + i],
+                          rays[(std::size_t)2 * m + i],
+                          rays[(std::size_t)3 * m + i],
+                          rays[(std::size_t)4 * m + i],
+                          rays[(std::size_t)5 * m + i]};
+    bzr_host::newton_short_pair(rec, ray, limit[i] != 0, full + (std::size_t)12 * i, skipped + (std::size_t)12 * i);
+  }
+  return BZR_OK;
 }
 
 }  // extern "C"

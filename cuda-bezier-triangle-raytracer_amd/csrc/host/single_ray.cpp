@@ -78,7 +78,8 @@ using namespace exact;
 
 // patch_math.hpp patch_intersect (ungated): the planar gate (reference/bezierTriangle.cpp:124-131), then the
 // bracket, Newton steps and classification.
-Hit patch_intersect(const PatchView &p, f3 s, f3 d, bool limitNone) {
+template <typename Need = NormalAlways>
+Hit patch_intersect(const PatchView &p, f3 s, f3 d, bool limitNone, Need need = Need()) {
   Hit h;
   h.t = 0.0f;
   h.point = mk(0.0f, 0.0f, 0.0f);
@@ -93,7 +94,7 @@ Hit patch_intersect(const PatchView &p, f3 s, f3 d, bool limitNone) {
   const f3 b0 = matvec(p, ip);
   if (!(limitNone || (b0.x >= 0.0f && b0.x <= 1.0f && b0.y >= 0.0f && b0.y <= 1.0f && b0.z >= 0.0f && b0.z <= 1.0f)))
     return h;
-  return newton_tail(p, s, d, ic, it);
+  return newton_tail(p, s, d, ic, it, need);
 }
 
 Hit no_hit() {
@@ -151,6 +152,23 @@ uint32_t refract_hit(const Hit &h, float ri, f3 s, f3 d, uint32_t expected, f3 &
     }
   }
   return st == expected ? st : uint32_t(BZR_RR_NONE);
+}
+
+// newton_tail's hook answering "not needed" (bzr_debug_newton_short)
+struct NormalNever {
+  bool operator()(float) const { return false; }
+};
+void put_hit(const Hit &h, float out[12]) {
+  const float w[11] = {h.t,      h.point.x, h.point.y,  h.point.z,  h.cs,      h.bary.x,
+                       h.bary.y, h.bary.z,  h.normal.x, h.normal.y, h.normal.z};
+  std::memcpy(out, w, sizeof w);
+  std::memcpy(out + 11, &h.what, 4);
+}
+void newton_short_pair(const float *record, const float ray[6], bool limitNone, float full[12], float skipped[12]) {
+  const PatchView p{record};
+  const f3 s = mk(ray[0], ray[1], ray[2]), d = mk(ray[3], ray[4], ray[5]);
+  put_hit(patch_intersect(p, s, d, limitNone), full);
+  put_hit(patch_intersect(p, s, d, limitNone, NormalNever()), skipped);
 }
 
 f3 v3(Vector const &v) { return mk(v(0), v(1), v(2)); }

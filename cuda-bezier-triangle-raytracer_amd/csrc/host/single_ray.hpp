@@ -6,6 +6,12 @@
 
 #include "bzr/bzr.hpp"
 
+namespace bzr_host {
+// BezierTriangle::intersect on one 66-word record, twice: whole, and with newton_tail's hook answering "not
+// needed" (the last normal skipped).  12 words each: t, point, cos, barycentrics, normal, what.
+void newton_short_pair(const float *record, const float ray[6], bool limitNone, float full[12], float skipped[12]);
+}  // namespace bzr_host
+
 namespace bzr {
 namespace host {
 // BezierTriangle::intersect(ray, limit) (reference/bezierTriangle.cpp:123-195); limitNone = cNone.

@@ -177,7 +177,7 @@ enum {
   BZR_COUNTER_NEWTON_ROUNDS = 8, /* fused path: patch-uniform Newton passes (per wave; cThis + follow-side) */
   BZR_COUNTER_ROUNDS_ODD = 9,    /* fused path: the passes of odd chain segments (refract(OUTSIDE): a lens's back surface) */
   BZR_COUNTER_RUNS_ODD = 10,     /* fused path: their Newton runs (pairs + follow retries) */
-  BZR_COUNTER_DIRTY_ROWS = 11,   /* reserved, always 0 (the slot of a removed experiment; kept so the ids do not move) */
+  BZR_COUNTER_SHORT_PASSES = 11, /* fused: Newton passes that skipped the last normal: no lane could win (BZR_TRACE_SHORT) */
   BZR_COUNTER_COUNT = 12
 };
 /* While enabled, each culled segment adds its counts on the device (one tiny kernel per segment). */

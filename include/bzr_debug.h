@@ -80,6 +80,14 @@ int32_t bzr_debug_wave_clock(void *ctx, unsigned long long *clock, uint32_t wave
  * MI355X_MICROARCH.md "DVFS give-back" item 6): clock[4w] = start, [4w+1] = duration (s_memtime ticks),
  * [4w+2] = start, [4w+3] = duration (s_memrealtime ticks); the wave's clock is [4w+1] / [4w+3] x 100 MHz. */
 int32_t bzr_debug_wave_clock_rate(void *ctx, unsigned long long *clock, uint32_t waves);
+/* Host check of the short Newton pass (patch_math_body.inc newton_tail's hook; trace.hip BZR_TRACE_SHORT): for
+ * each of m triples (patch[i] < n, ray i of `rays` in SoA [6, m], limit[i]: 0 = cThis, 1 = cNone) the host's
+ * BezierTriangle::intersect twice -- `full` as always, `skipped` with the hook answering "not needed", so the last
+ * iteration's normal is not evaluated.  12 words per triple each: t, point xyz, cos, barycentrics, normal xyz,
+ * what (uint32).  In `skipped` the normal and cos words are unspecified; every other word must equal `full`'s.
+ * No device.  Returns 0 on success. */
+int32_t bzr_debug_newton_short(const void *patches, uint32_t n, uint32_t stride, const uint32_t *patch,
+                               const float *rays, const uint8_t *limit, uint32_t m, float *full, float *skipped);
 #ifdef __cplusplus
 }
 #endif
