@@ -76,6 +76,7 @@ _SIGS = {
     "bzr_patch_intersect": [_P, _P, _P, _P, _P, _U32, _P, _U32],
     "bzr_refract": [_P, _P, _F, _P, _P, _U32, _U32, _P, _P, _U32],
     "bzr_trace_chain": [_P, _P, _P, _U32, _P, _U32, _P, _P, _P, _U32],
+    "bzr_trace_chain_power": [_P, _P, _P, _U32, _P, _P, _U32, _P, _P, _P, _P, _U32],
     "bzr_trace_tiled": [_P, _U32, _P, _P, _U32, _P, _U32, _U32, _P, _P, _P, _U32],
     "bzr_tiled_create": [_P, _U32, _U32, _U32, _U32, _I32, ctypes.POINTER(_P)],
     "bzr_tiled_destroy": [_P],
@@ -90,6 +91,7 @@ _SIGS = {
     "bzr_mesh_interpolate": [_P, _P, _I32, _P, _U32],
     "bzr_emit": [_P, _P, ctypes.c_uint64, _U32, _P, _P, _U32],
     "bzr_illuminate": [_P, _P, _P, _U32, _P, ctypes.c_uint64, _P, _P, _P, _U32],
+    "bzr_illuminate_power": [_P, _P, _P, _U32, _P, ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _U32],
     "bzr_mesh_bounding_sphere": [_P, _P],
     "bzr_trimesh_create": [ctypes.POINTER(_P)],
     "bzr_trimesh_destroy": [_P],
@@ -118,7 +120,10 @@ _SIGS = {
     "bzr_debug_wave_clock_rate": [_P, _P, _U32],
     "bzr_debug_chunk_plan": [ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(_U32), ctypes.POINTER(_U32)],
     "bzr_debug_chunk_cap": [_P, _U32, ctypes.POINTER(_U32)],
+    "bzr_debug_fresnel": [_P, _P, _U32, _P],
 }
+# entry points added without an ABI bump: an explicitly chosen earlier build (BZR_LIBRARY) may lack them
+_ADDED = ("bzr_trace_chain_power", "bzr_illuminate_power")
 _RET = {"bzr_last_error": ctypes.c_char_p, "bzr_abi_version": _I32}
 
 _lib = None
@@ -146,7 +151,8 @@ def lib():
             raise BzrError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
         handle = ctypes.CDLL(str(LIB_PATH))
         for name, args in _SIGS.items():
-            if os.environ.get("BZR_LIBRARY") and name.startswith("bzr_debug_") and not hasattr(handle, name):
+            if (os.environ.get("BZR_LIBRARY") and (name.startswith("bzr_debug_") or name in _ADDED)
+                    and not hasattr(handle, name)):
                 continue  # an explicitly chosen other build (A/B against an earlier round): its debug hooks may differ
             fn = getattr(handle, name)
             fn.argtypes = args
@@ -186,8 +192,10 @@ class _Buf:
         if _is_tensor(x):
             if not x.is_contiguous():
                 raise BzrError("tensor arguments must be contiguous")
-            want = {np.float32: "torch.float32", np.uint32: "torch.uint32", np.int32: "torch.int32"}
-            if str(x.dtype) not in (want[dtype], "torch.int32" if dtype == np.uint32 else want[dtype]):
+            want = {np.float32: "torch.float32", np.uint32: "torch.uint32", np.int32: "torch.int32",
+                    np.uint64: "torch.uint64"}
+            same_bits = {np.uint32: "torch.int32", np.uint64: "torch.int64"}
+            if str(x.dtype) not in (want[dtype], same_bits.get(dtype, want[dtype])):
                 raise BzrError(f"tensor dtype {x.dtype} where {want[dtype]} is expected")
             self.ptr, self.device, self.keep = x.data_ptr(), bool(x.is_cuda), x
         else:
@@ -413,6 +421,29 @@ def trace_chain(ctx: Context, lenses, ri, rays, out_rays=None, out_status=None, 
     return out_rays, out_status, out_segments
 
 
+def trace_chain_power(ctx: Context, lenses, ri, rays, weight=None, out_rays=None, out_weight=None, out_status=None,
+                      out_segments=None, mode=MODE_PARITY):
+    """trace_chain with the rays' power -> (rays, weight [n], status [n], segments [n]).  weight [n] float32 is the
+    power the rays start with (None: 1.0 each); out_weight[i] = weight[i] x the Fresnel transmittance of each successful
+    refraction of ray i (bzr.h bzr_trace_chain_power).  out_weight may be `weight` itself."""
+    n = _n_of(rays, mode)
+    nl = len(lenses)
+    handles = (_P * nl)(*[m.handle for m in lenses])
+    ris = (_F * nl)(*[float(x) for x in ri])
+    out_rays = _empty_like(rays, 6, np.float32, mode) if out_rays is None else out_rays
+    out_weight = _empty_like(rays, 0, np.float32, mode) if out_weight is None else out_weight
+    out_status = _empty_like(rays, 0, np.uint32, mode) if out_status is None else out_status
+    out_segments = _empty_like(rays, 0, np.uint32, mode) if out_segments is None else out_segments
+    r, wi = _Buf(rays, np.float32), _Buf(weight, np.float32)
+    o, w = _Buf(out_rays, np.float32, True), _Buf(out_weight, np.float32, True)
+    s, g = _Buf(out_status, np.uint32, True), _Buf(out_segments, np.uint32, True)
+    res = _residency(r, o, w, s, g, *([wi] if weight is not None else []))
+    with _stream_for(ctx, res):
+        _check(lib().bzr_trace_chain_power(ctx.handle, ctypes.cast(handles, _P), ctypes.cast(ris, _P), nl, r.ptr, wi.ptr,
+                                           n, o.ptr, w.ptr, s.ptr, g.ptr, res | mode))
+    return out_rays, out_weight, out_status, out_segments
+
+
 PACK_IMAGE, PACK_RAYS, PACK_COMPACT = 0, 1, 2  # BZR_PACK_*
 PACK_LAYOUTS = {"image": PACK_IMAGE, "rays": PACK_RAYS, "compact": PACK_COMPACT}
 
@@ -616,6 +647,60 @@ def illuminate(ctx: Context, lenses, ri, em: Emitter, total_rays: int, target: T
         _check(lib().bzr_illuminate(ctx.handle, handles, ris, nl, ctypes.byref(em), int(total_rays),
                                     ctypes.byref(target), h.ptr, stats, res | mode))
     return hist, dict(zip(ILLUM_STATS, [int(x) for x in stats]))
+
+
+EMISSION_UNIFORM, EMISSION_LAMBERT = 0, 1  # BZR_EMISSION_*: w0 = 1 | w0 = the direction's x component
+SURFACE_LOSSLESS, SURFACE_FRESNEL = 0, 1  # BZR_SURFACE_*: T = 1 | the unpolarised Fresnel transmittance
+
+
+class Radiometry(ctypes.Structure):
+    """bzr_radiometry"""
+    _fields_ = [("emission", _U32), ("surface", _U32)]
+
+
+def illuminate_power(ctx: Context, lenses, ri, em: Emitter, total_rays: int, target: Target,
+                     emission=EMISSION_LAMBERT, surface=SURFACE_FRESNEL, flux=None, hist=None, mode=MODE_PARITY):
+    """illuminate with ray power.  Returns (flux uint64 [bins_v, bins_u] in 32.32 fixed point (flux_to_float),
+    accumulated into `flux` if given; hist uint32 [bins_v, bins_u] as illuminate's, accumulated into `hist` if given;
+    stats dict; power dict: the emitted / culled / exited / landed power in the same fixed point)."""
+    nl = len(lenses)
+    handles = (_P * nl)(*[m.handle for m in lenses])
+    ris = (_F * nl)(*[float(x) for x in ri])
+    if flux is None:
+        flux = np.zeros((target.bins_v, target.bins_u), np.uint64)
+    if hist is None:
+        if _is_tensor(flux):
+            import torch
+
+            hist = torch.zeros((target.bins_v, target.bins_u), dtype=torch.int32, device=flux.device)
+        else:
+            hist = np.zeros((target.bins_v, target.bins_u), np.uint32)
+    f, h = _Buf(flux, np.uint64, True), _Buf(hist, np.uint32, True)
+    rad = Radiometry(int(emission), int(surface))
+    stats, power = (ctypes.c_uint64 * 4)(), (ctypes.c_uint64 * 4)()
+    res = _residency(f, h)
+    with _stream_for(ctx, res):
+        _check(lib().bzr_illuminate_power(ctx.handle, handles, ris, nl, ctypes.byref(em), int(total_rays),
+                                          ctypes.byref(target), ctypes.byref(rad), f.ptr, h.ptr, stats, power, res | mode))
+    return (flux, hist, dict(zip(ILLUM_STATS, [int(x) for x in stats])),
+            dict(zip(ILLUM_STATS, [int(x) for x in power])))
+
+
+def flux_to_float(flux) -> np.ndarray:
+    """32.32 fixed-point power (illuminate_power's flux and power sums) as float64."""
+    a = flux.cpu().numpy() if _is_tensor(flux) else np.asarray(flux)
+    return a.astype(np.uint64).astype(np.float64) / 2.0 ** 32
+
+
+def debug_fresnel(eta, cs) -> np.ndarray:
+    """bzr_debug_fresnel: the kernels' Fresnel transmittance evaluated on the host for (eta, cos) pairs; 0 where
+    eta^2 (1 - cos^2) >= 0.99."""
+    e, c = np.ascontiguousarray(eta, np.float32), np.ascontiguousarray(cs, np.float32)
+    if e.shape != c.shape or e.ndim != 1:
+        raise BzrError("eta and cs must be 1-D arrays of one length")
+    out = np.empty(e.shape, np.float32)
+    _check(lib().bzr_debug_fresnel(e.ctypes.data, c.ctypes.data, e.size, out.ctypes.data))
+    return out
 
 
 def bounding_sphere(mesh: DeviceMesh) -> np.ndarray:

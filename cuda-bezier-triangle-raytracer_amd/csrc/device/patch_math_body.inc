@@ -9,6 +9,7 @@
 //   interpolate      reference/bezierTriangle.cpp:105-121
 //   surface_normal   reference/bezierTriangle.cpp:197-233
 //   newton_tail      reference/bezierTriangle.cpp:132-195
+//   fresnel_t        no reference counterpart: the transmittance of a refraction (DESIGN.md (a), ray power)
 __device__ __forceinline__ f3 add(f3 a, f3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
 __device__ __forceinline__ f3 sub(f3 a, f3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
 __device__ __forceinline__ f3 scale(f3 a, float s) { return mk(a.x * s, a.y * s, a.z * s); }
@@ -19,6 +20,18 @@ __device__ __forceinline__ f3 cross(f3 a, f3 b) {
 __device__ __forceinline__ f3 normalized(f3 a) {
   float z = dot(a, a);
   return unit_or_self(a, z);
+}
+
+// Unpolarised Fresnel transmittance of one refraction (DESIGN.md (a), ray power).  eta, cs and
+// s2 = eta^2 (1 - cs^2) < 0.99 are the values Snell's step has (refract_hit): c2 >= 0.1 and eta > 0, so both
+// denominators are positive.  The direction-kept branch (s2 <= 1e-12) takes the same formula.
+__device__ __forceinline__ float fresnel_t(float eta, float cs, float s2) {
+  const float c1 = fabsf(cs), c2 = sqrt_rn(1.0f - s2);
+  const float a = eta * c1;
+  const float rs = div_rn(a - c2, a + c2);
+  const float b = eta * c2;
+  const float rp = div_rn(b - c1, b + c1);
+  return 1.0f - 0.5f * (rs * rs + rp * rp);
 }
 
 template <typename P>

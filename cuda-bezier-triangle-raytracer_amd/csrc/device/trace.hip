@@ -360,9 +360,11 @@ __device__ __forceinline__ Hit mesh_intersect_scan(const MeshView &m, f3 s, f3 d
 }
 
 // The refraction of BezierLens::refract after the mesh intersection.  Returns the status;
-// o_s/o_d = refracted ray when status != NONE.
-__device__ __forceinline__ uint32_t refract_hit(const Hit &h, float ri, f3 s, f3 d, uint32_t expected, f3 &o_s,
-                                                f3 &o_d) {
+// o_s/o_d = refracted ray when status != NONE.  kGain: `gain` = the refraction's Fresnel transmittance
+// (patch_math_body.inc fresnel_t, from this step's own eta and s2) when the status is not NONE.
+template <bool kGain>
+__device__ __forceinline__ uint32_t refract_hit_t(const Hit &h, float ri, f3 s, f3 d, uint32_t expected, f3 &o_s,
+                                                  f3 &o_d, float &gain) {
   o_s = s;
   o_d = d;
   uint32_t st = BZR_RR_NONE;
@@ -371,6 +373,8 @@ __device__ __forceinline__ uint32_t refract_hit(const Hit &h, float ri, f3 s, f3
     o_s = h.point;
     float eta = st == BZR_RR_INSIDE ? div_rn(1.0f, ri) : ri;
     float s2 = eta * eta * (1.0f - h.cs * h.cs);
+    // (ahead of the branch: lanes with s2 >= 0.99 return NONE and their gain is not read)
+    if constexpr (kGain) gain = fresnel_t(eta, h.cs, s2);
     if (s2 < 0.99f) {
       if (s2 > 1e-12f) {
         float sgn = st == BZR_RR_INSIDE ? 1.0f : -1.0f;
@@ -384,6 +388,11 @@ __device__ __forceinline__ uint32_t refract_hit(const Hit &h, float ri, f3 s, f3
     }
   }
   return st == expected ? st : BZR_RR_NONE;
+}
+__device__ __forceinline__ uint32_t refract_hit(const Hit &h, float ri, f3 s, f3 d, uint32_t expected, f3 &o_s,
+                                                f3 &o_d) {
+  float gain;
+  return refract_hit_t<false>(h, ri, s, d, expected, o_s, o_d, gain);
 }
 
 __device__ __forceinline__ void load_ray(const float *__restrict__ r, uint32_t n, uint32_t i, f3 &s, f3 &d) {
@@ -526,7 +535,11 @@ struct Work {
 };
 constexpr uint32_t kSlotWords = 12;  // t, point, cos, bary, normal, source patch
 
-enum OutMode { kModeHits = 0, kModeRefract = 1, kModeStage = 2 };
+// kModePower: kModeStage plus the ray's power -- one weight per ray, multiplied by the Fresnel transmittance
+// (patch_math_body.inc fresnel_t) of each successful refraction.  A mode of its own, not a run-time branch of
+// kModeStage: the instantiations of the other three modes compile to the code they had.
+enum OutMode { kModeHits = 0, kModeRefract = 1, kModeStage = 2, kModePower = 3 };
+constexpr bool is_stage(int mode) { return mode == kModeStage || mode == kModePower; }
 struct Out {
   float *hits;               // kModeHits: SoA [13][ld]
   float *rays;               // kModeRefract: output rays; kModeStage: rays in flight (in place)
@@ -537,6 +550,8 @@ struct Out {
   float ri;
   uint32_t first;            // kModeStage: the chain's first stage -- every ray is alive, its input comes
                              // from the caller's rays and its ray / status / segments are all written here
+  float *weight;             // kModePower: the weights in flight [ld] (as rays: in place)
+  const float *weight_in;    // kModePower, first stage: the caller's weights, or null -> 1
 };
 
 template <int kMode>
@@ -545,8 +560,9 @@ __device__ __forceinline__ void emit(const Out &o, uint32_t ld, uint32_t gi, f3 
     store_hit(o.hits, ld, gi, h, patch);
   } else {
     f3 os, od;
-    uint32_t st = refract_hit(h, o.ri, s, d, o.expected ? o.expected[gi] : o.expected_all, os, od);
-    if (kMode == kModeRefract || st != BZR_RR_NONE || (kMode == kModeStage && o.first)) {
+    float gain = 1.0f;
+    uint32_t st = refract_hit_t<kMode == kModePower>(h, o.ri, s, d, o.expected ? o.expected[gi] : o.expected_all, os, od, gain);
+    if (kMode == kModeRefract || st != BZR_RR_NONE || (is_stage(kMode) && o.first)) {
       if (st == BZR_RR_NONE) {
         os = s;
         od = d;
@@ -554,7 +570,14 @@ __device__ __forceinline__ void emit(const Out &o, uint32_t ld, uint32_t gi, f3 
       store_ray(o.rays, ld, gi, os, od);
     }
     o.status[gi] = st;
-    if (kMode == kModeStage && o.segments) o.segments[gi] = o.first ? 1u : o.segments[gi] + 1u;
+    if (is_stage(kMode) && o.segments) o.segments[gi] = o.first ? 1u : o.segments[gi] + 1u;
+    if constexpr (kMode == kModePower) {  // the first stage writes every ray's weight, later ones the refracted rays'
+      if (o.first || st != BZR_RR_NONE) {
+        float w = o.first ? (o.weight_in ? o.weight_in[gi] : 1.0f) : o.weight[gi];
+        if (st != BZR_RR_NONE) w = w * gain;
+        o.weight[gi] = w;
+      }
+    }
   }
 }
 
@@ -1628,7 +1651,7 @@ __global__ __launch_bounds__(kBlock) BZR_FINISH_ATTR void k_finish(MeshView m, c
     store_hit(o.hits, ld, gi, h, patch);
     return;
   }
-  if (kMode == kModeStage && !o.first && o.status[gi] == BZR_RR_NONE) return;
+  if (is_stage(kMode) && !o.first && o.status[gi] == BZR_RR_NONE) return;
   // the ray is loaded unconditionally: making the load depend on w.count (an intersect chunk's hits need it
   // only for an overflow ray) serialises the two reads and measured slower (cfg3 k_finish 0.059 -> 0.069 ms,
   // profiles/r04_ab_traverse_wpe8.jsonl, variant "finish")
@@ -2342,7 +2365,8 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
 
 // Trace job of one launch.  Modes: kModeHits (one BezierMesh::intersect per ray -> hits), kModeRefract
 // (one BezierLens::refract -> ray', status), kModeStage (the chain over lenses [0, count): refract(INSIDE)
-// then refract(OUTSIDE) per lens, a NONE ends the ray -- reference/test.cpp:376-401).
+// then refract(OUTSIDE) per lens, a NONE ends the ray -- reference/test.cpp:376-401), kModePower (kModeStage with
+// the rays' power: wherever kModeStage is named below, kModePower's fields are the same).
 struct TraceJob {
   const float *rays;         // input [6][n]
   float *hits;               // kModeHits [13][n]
@@ -2358,6 +2382,8 @@ struct TraceJob {
   uint32_t wave_real;              // wave_clock holds [4 * waves]: + s_memrealtime start, duration (100 MHz)
   const uint32_t *order;           // optional: block b traces tile order[b] (cost-ordered dispatch, run_fused)
   uint32_t *cost;                  // optional: per tile, its cost bin (sched_bin of the block's duration)
+  float *weight;                   // kModePower [n]: the traced rays' power (may alias weight_in)
+  const float *weight_in;          // kModePower [n]: the power the rays start with, or null -> 1
 };
 
 // BZR_TRACE_WPE (default 6): amdgpu_waves_per_eu lower bound for k_trace.  The chain kernel needs 72 VGPRs
@@ -2479,11 +2505,12 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
   const uint32_t n = job.n;
   TraceCtr ctr;
   bool alive = i < n;
-  if (kMode == kModeStage && job.alive_in && alive) alive = job.alive_in[i] != BZR_RR_NONE;
+  if (is_stage(kMode) && job.alive_in && alive) alive = job.alive_in[i] != BZR_RR_NONE;
   const bool traced = alive;
   f3 s = mk(0.0f, 0.0f, 0.0f), d = s;
   if (i < n) load_ray(job.rays, job.ld, i, s, d);
-  const uint32_t nseg = kMode == kModeStage ? 2u * lenses.count : 1u;
+  float wgt = 1.0f;  // kModePower: the lane's power (loaded behind the first segment's walk, below)
+  const uint32_t nseg = is_stage(kMode) ? 2u * lenses.count : 1u;
   uint32_t st = BZR_RR_NONE, seg = 0;
   for (uint32_t k = 0; k < nseg; ++k) {
     if (!__any(alive)) break;
@@ -2498,6 +2525,11 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
         ctr.runs_odd += ctr.pairs + ctr.follows - w0;
       }
     }
+    // The caller's weight is first needed by the first refraction.  Loaded here, its register is not live across
+    // the first (longest) walk; loaded with the ray, the non-counting kernels came out with 36 B of scratch
+    // reserved (never accessed), here with none.
+    if constexpr (kMode == kModePower)
+      if (k == 0u && i < n && job.weight_in) wgt = job.weight_in[i];
     Hit h = no_hit();
     uint32_t patch = 0xFFFFFFFFu;
     if (best != ~0ull) h = winner(L, lane, patch);
@@ -2507,7 +2539,8 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
       const uint32_t expected = kMode == kModeRefract ? (job.expected ? (alive ? job.expected[i] : 0u) : job.expected_all)
                                                       : ((k & 1u) ? uint32_t(BZR_RR_OUTSIDE) : uint32_t(BZR_RR_INSIDE));
       f3 os, od;
-      const uint32_t r = refract_hit(h, m.ri, s, d, expected, os, od);
+      float gain = 1.0f;
+      const uint32_t r = refract_hit_t<kMode == kModePower>(h, m.ri, s, d, expected, os, od, gain);
       if (alive) {
         ++seg;
         st = r;
@@ -2515,6 +2548,7 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
         else {
           s = os;
           d = od;
+          if constexpr (kMode == kModePower) wgt = wgt * gain;
         }
       }
     }
@@ -2522,7 +2556,8 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
   if (kMode != kModeHits && traced) {
     store_ray(job.out_rays, job.ld, i, s, d);
     job.status[i] = st;
-    if (kMode == kModeStage && job.segments) job.segments[i] = seg;
+    if (is_stage(kMode) && job.segments) job.segments[i] = seg;
+    if constexpr (kMode == kModePower) job.weight[i] = wgt;
   }
   if (job.cost && threadIdx.x == 0u) job.cost[tile] = sched_bin(__builtin_amdgcn_s_memtime() - t_start);
   if (job.wave_clock && lane == 0u) {  // the wave's tile (ray index / 64): start tick and duration
@@ -2615,6 +2650,42 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
   store_ray(out_rays, n, i, s, d);
   out_status[i] = st;
   if (out_segments) out_segments[i] = seg;
+}
+
+// k_chain_scan with the rays' power (kModePower's brute-force form, the A/B reference of the two culled paths):
+// weight_in may be null (1) and may alias out_weight.
+__global__ __launch_bounds__(kBlock) void k_chain_scan_power(LensSet lenses, const float *__restrict__ rays, uint32_t n,
+                                                             float *__restrict__ out_rays, uint32_t *__restrict__ out_status,
+                                                             uint32_t *__restrict__ out_segments, const float *weight_in,
+                                                             float *out_weight) {
+  uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  f3 s, d;
+  load_ray(rays, n, i, s, d);
+  float wgt = weight_in ? weight_in[i] : 1.0f;
+  uint32_t st = BZR_RR_NONE, seg = 0;
+  bool alive = true;
+  for (uint32_t l = 0; l < lenses.count && alive; ++l) {
+    for (uint32_t j = 0; j < 2u && alive; ++j) {
+      f3 os, od;
+      uint32_t patch;
+      ++seg;
+      Hit h = mesh_intersect_scan(lenses.lens[l], s, d, patch);
+      float gain = 1.0f;
+      st = refract_hit_t<true>(h, lenses.lens[l].ri, s, d, j == 0 ? BZR_RR_INSIDE : BZR_RR_OUTSIDE, os, od, gain);
+      if (st == BZR_RR_NONE) {
+        alive = false;
+      } else {
+        s = os;
+        d = od;
+        wgt = wgt * gain;
+      }
+    }
+  }
+  store_ray(out_rays, n, i, s, d);
+  out_status[i] = st;
+  if (out_segments) out_segments[i] = seg;
+  out_weight[i] = wgt;
 }
 
 template <bool kFast>
@@ -3553,9 +3624,13 @@ extern "C" bzr_status bzr_refract(bzr_ctx *ctx, const bzr_mesh *mesh, float ri, 
   return BZR_OK;
 }
 
-extern "C" bzr_status bzr_trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
-                                      const float *rays, uint32_t n, float *out_rays, uint32_t *out_status,
-                                      uint32_t *out_segments, uint32_t flags) {
+// bzr_trace_chain (kModeStage) and bzr_trace_chain_power (kModePower: + weight_in, may be null, and out_weight,
+// plain [n] rows in either ray layout).
+template <int kMode>
+static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
+                              const float *rays, const float *weight_in, uint32_t n, float *out_rays, float *out_weight,
+                              uint32_t *out_status, uint32_t *out_segments, uint32_t flags) {
+  constexpr bool kPower = kMode == kModePower;
   if (bzr_status s = check_flags(flags, true)) return s;
   if (!ctx) return set_error(BZR_ERR_INVALID_ARGUMENT, "null context");
   if (nlens == 0 || nlens > kMaxLenses) return set_error(BZR_ERR_INVALID_ARGUMENT, "nlens must be 1..8");
@@ -3567,18 +3642,21 @@ extern "C" bzr_status bzr_trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lense
     set.lens[l] = view_of(lenses[l], ri[l]);
   }
   if (n == 0) return BZR_OK;
-  if (!rays || !out_rays || !out_status) return set_error(BZR_ERR_INVALID_ARGUMENT, "null buffer");
+  if (!rays || !out_rays || !out_status || (kPower && !out_weight)) return set_error(BZR_ERR_INVALID_ARGUMENT, "null buffer");
   if (rays == out_rays) return set_error(BZR_ERR_INVALID_ARGUMENT, "rays and out_rays must not alias");
   DeviceGuard g(ctx->device);
   const float *d_rays = rays;
   float *d_out = out_rays;
   uint32_t *d_st = out_status, *d_seg = out_segments;
+  const float *d_win = weight_in;
+  float *d_w = out_weight;
   const bool host = !(flags & BZR_DEVICE_PTRS), aos = (flags & BZR_RAYS_AOS) != 0;
   float *tmp = nullptr;  // host + AoS: the records on the device, in and out
   if (host || aos) {
     size_t rb = (size_t)n * 24, ib = (size_t)n * 4;
     if (bzr_status s = ensure_buffer(ctx->scratch, ctx->scratch_bytes,
-                                     2 * round256(rb) + (host ? 2 * round256(ib) : 0) + (host && aos ? round256(rb) : 0)))
+                                     2 * round256(rb) + (host ? (kPower ? 3 : 2) * round256(ib) : 0) +
+                                         (host && aos ? round256(rb) : 0)))
       return s;
     Staging st{static_cast<char *>(ctx->scratch)};
     float *r = st.take<float>((size_t)n * 6);
@@ -3586,13 +3664,21 @@ extern "C" bzr_status bzr_trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lense
     if (host) {
       d_st = st.take<uint32_t>(n);
       d_seg = st.take<uint32_t>(n);
+      if (kPower) {
+        d_w = st.take<float>(n);
+        if (weight_in) BZR_HIP(hipMemcpyAsync(d_w, weight_in, ib, hipMemcpyHostToDevice, ctx->stream));
+        d_win = weight_in ? d_w : nullptr;
+      }
     }
     if (host && aos) tmp = st.take<float>((size_t)n * 6);
     if (bzr_status s = rays_in(ctx, rays, r, n, host, aos, tmp)) return s;
     d_rays = r;
   }
   if (use_scan(flags)) {
-    launch(ctx, BZR_KERNEL_CHAIN_SCAN, k_chain_scan, dim3(grid_for(n)), set, d_rays, n, d_out, d_st, d_seg);
+    if constexpr (kPower)
+      launch(ctx, BZR_KERNEL_CHAIN_SCAN, k_chain_scan_power, dim3(grid_for(n)), set, d_rays, n, d_out, d_st, d_seg, d_win, d_w);
+    else
+      launch(ctx, BZR_KERNEL_CHAIN_SCAN, k_chain_scan, dim3(grid_for(n)), set, d_rays, n, d_out, d_st, d_seg);
     BZR_HIP(hipGetLastError());
   } else if (!use_staged(flags, n, max_patches(set))) {
     TraceJob job{};
@@ -3601,7 +3687,9 @@ extern "C" bzr_status bzr_trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lense
     job.status = d_st;
     job.segments = d_seg;
     job.n = job.ld = n;
-    if (bzr_status s = run_fused<kModeStage>(ctx, set, job, flags)) return s;
+    job.weight = d_w;
+    job.weight_in = d_win;
+    if (bzr_status s = run_fused<kMode>(ctx, set, job, flags)) return s;
   } else {
     // stage by stage: out_rays holds the rays in flight, out_status != NONE marks them alive
     uint32_t nb = 0;
@@ -3622,7 +3710,9 @@ extern "C" bzr_status bzr_trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lense
           o.segments = d_seg;
           o.ri = set.lens[l].ri;
           o.first = (l == 0 && j == 0) ? 1u : 0u;
-          if (bzr_status s = run_segment<kModeStage>(use_fast(flags), ctx, set.lens[l], o.first ? d_rays : d_out, n, off,
+          o.weight = d_w;
+          o.weight_in = d_win;
+          if (bzr_status s = run_segment<kMode>(use_fast(flags), ctx, set.lens[l], o.first ? d_rays : d_out, n, off,
                                                      m, o.first ? nullptr : d_st, o, w))
             return s;
         }
@@ -3635,9 +3725,24 @@ extern "C" bzr_status bzr_trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lense
     BZR_HIP(hipMemcpyAsync(out_status, d_st, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (out_segments)
       BZR_HIP(hipMemcpyAsync(out_segments, d_seg, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (kPower) BZR_HIP(hipMemcpyAsync(out_weight, d_w, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     BZR_HIP(hipStreamSynchronize(ctx->stream));
   }
   return BZR_OK;
+}
+
+extern "C" bzr_status bzr_trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
+                                      const float *rays, uint32_t n, float *out_rays, uint32_t *out_status,
+                                      uint32_t *out_segments, uint32_t flags) {
+  return trace_chain<kModeStage>(ctx, lenses, ri, nlens, rays, nullptr, n, out_rays, nullptr, out_status, out_segments, flags);
+}
+
+extern "C" bzr_status bzr_trace_chain_power(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
+                                            const float *rays, const float *weight_in, uint32_t n, float *out_rays,
+                                            float *out_weight, uint32_t *out_status, uint32_t *out_segments,
+                                            uint32_t flags) {
+  return trace_chain<kModePower>(ctx, lenses, ri, nlens, rays, weight_in, n, out_rays, out_weight, out_status,
+                                 out_segments, flags);
 }
 
 // ------------------------------------------------------------ test hook: normalized()
@@ -3876,6 +3981,92 @@ __global__ __launch_bounds__(kBlock) void k_land(bzr_target tg, float4 plane, fl
   }
 }
 
+// Ray power as unsigned 64-bit fixed point with 32 fraction bits: q(w) = trunc(w x 2^32) for w in [0, 1] (the
+// product is exact in binary32, the conversion truncates).  Integer sums do not depend on the order of arrival.
+__device__ __forceinline__ unsigned long long power_q32(float w) {
+  return w > 0.0f ? (unsigned long long)(w * 4294967296.0f) : 0ull;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int k = 32; k >= 1; k >>= 1) v += __shfl_xor(v, k, 64);
+  return v;
+}
+
+// k_emit for bzr_illuminate_power: the batch's rays with their status and segments as k_emit writes them, plus each
+// ray's initial power w0 (1, or with `lambert` the direction's x component: cos to the emitter's +x normal) and
+// power[EMITTED], power[CULLED] = the sums of q(w0), reduced over the wave first.
+__global__ __launch_bounds__(kBlock) void k_emit_power(bzr_emitter em, BeltTable bt, uint64_t first, uint32_t n, uint32_t ld,
+                                                       float *__restrict__ rays, uint32_t *__restrict__ status,
+                                                       uint32_t *__restrict__ segments, float *__restrict__ weight,
+                                                       uint32_t lambert, float4 sphere, const float4 *__restrict__ always,
+                                                       uint32_t n_always, unsigned long long *__restrict__ stats,
+                                                       unsigned long long *__restrict__ power) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  bool culled = false;
+  f3 o = mk(0.0f, 0.0f, 0.0f), d = o;
+  if (i < n) {
+    uint32_t p;
+    emit_ray(em, bt, first + i, o, d, p);
+    store_ray(rays, ld, i, o, d);
+    const float sp[4] = {sphere.x, sphere.y, sphere.z, sphere.w};
+    culled = !may_hit_sphere(o, d, sp);
+  }
+  for (uint32_t k = 0; k < n_always && __any(culled); ++k) {
+    uint32_t b;
+    if (always_gate(always, k, culled, o, d, b)) culled = false;
+  }
+  const float w0 = lambert ? d.x : 1.0f;
+  if (i < n) {
+    status[i] = culled ? BZR_RR_NONE : BZR_RR_INSIDE;
+    segments[i] = 0u;
+    weight[i] = w0;
+  }
+  const unsigned long long made = __ballot(i < n), cut = __ballot(culled);
+  const unsigned long long q = i < n ? power_q32(w0) : 0ull;
+  const unsigned long long qe = wave_sum_u64(q), qc = wave_sum_u64(culled ? q : 0ull);
+  if ((threadIdx.x & 63u) == 0u) {
+    if (made) atomicAdd(&stats[BZR_ILLUM_EMITTED], (unsigned long long)__popcll(made));
+    if (cut) atomicAdd(&stats[BZR_ILLUM_CULLED], (unsigned long long)__popcll(cut));
+    if (qe) atomicAdd(&power[BZR_ILLUM_EMITTED], qe);
+    if (qc) atomicAdd(&power[BZR_ILLUM_CULLED], qc);
+  }
+}
+
+// k_land for bzr_illuminate_power: each landed ray adds q(its weight) to its cell of flux (64-bit atomic) and, with
+// `hist`, one count as k_land does; stats as k_land's, power[EXITED], power[LANDED] = the sums of q(w), one atomic
+// per wave and counter.
+__global__ __launch_bounds__(kBlock) void k_land_power(bzr_target tg, float4 plane, float cell_u, float cell_v,
+                                                       const float *__restrict__ rays, uint32_t ld, uint32_t n,
+                                                       const uint32_t *__restrict__ status,
+                                                       const float *__restrict__ weight,
+                                                       unsigned long long *__restrict__ flux, uint32_t *__restrict__ hist,
+                                                       unsigned long long *__restrict__ stats,
+                                                       unsigned long long *__restrict__ power) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  bool exited = false, landed = false;
+  unsigned long long q = 0ull;
+  if (i < n && status[i] == BZR_RR_OUTSIDE) {
+    exited = true;
+    q = power_q32(weight[i]);
+    f3 s, d;
+    load_ray(rays, ld, i, s, d);
+    const int32_t cell = target_cell(tg, mk(plane.x, plane.y, plane.z), plane.w, cell_u, cell_v, s, d);
+    if (cell >= 0) {
+      landed = true;
+      atomicAdd(&flux[cell], q);
+      if (hist) atomicAdd(&hist[cell], 1u);
+    }
+  }
+  const unsigned long long ex = __ballot(exited), la = __ballot(landed);
+  const unsigned long long qx = wave_sum_u64(q), ql = wave_sum_u64(landed ? q : 0ull);
+  if ((threadIdx.x & 63u) == 0u) {
+    if (ex) atomicAdd(&stats[BZR_ILLUM_EXITED], (unsigned long long)__popcll(ex));
+    if (la) atomicAdd(&stats[BZR_ILLUM_LANDED], (unsigned long long)__popcll(la));
+    if (qx) atomicAdd(&power[BZR_ILLUM_EXITED], qx);
+    if (ql) atomicAdd(&power[BZR_ILLUM_LANDED], ql);
+  }
+}
+
 // UniformHemisphere(belts)'s patch table (reference/hostUtil.cpp:3-14, same float expressions) and the
 // belt boundaries cos(i * width) the device compares cos(incidence) against.
 bzr_status belt_tables(uint32_t belts, std::vector<float> &cos_lo, std::vector<uint32_t> &count,
@@ -3956,12 +4147,21 @@ extern "C" bzr_status bzr_emit(bzr_ctx *ctx, const bzr_emitter *em, uint64_t fir
   return BZR_OK;
 }
 
-extern "C" bzr_status bzr_illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
-                                     const bzr_emitter *em, uint64_t total_rays, const bzr_target *tg, uint32_t *hist,
-                                     uint64_t stats[4], uint32_t flags) {
+// bzr_illuminate (rad and flux null: counts only) and bzr_illuminate_power (rad and flux given, hist optional).
+static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
+                             const bzr_emitter *em, uint64_t total_rays, const bzr_target *tg, const bzr_radiometry *rad,
+                             uint64_t *flux, uint32_t *hist, uint64_t stats[4], uint64_t power[4], uint32_t flags) {
+  const bool with_power = rad != nullptr;
   if (!ctx) return set_error(BZR_ERR_INVALID_ARGUMENT, "null context");
   if (nlens == 0 || nlens > kMaxLenses) return set_error(BZR_ERR_INVALID_ARGUMENT, "nlens must be 1..8");
-  if (!lenses || !ri || !tg || !hist) return set_error(BZR_ERR_INVALID_ARGUMENT, "null argument");
+  if (!lenses || !ri || !tg || (!with_power && !hist)) return set_error(BZR_ERR_INVALID_ARGUMENT, "null argument");
+  if (with_power) {
+    if (!flux) return set_error(BZR_ERR_INVALID_ARGUMENT, "null flux_q32");
+    if (total_rays >= (1ull << 32)) return set_error(BZR_ERR_INVALID_ARGUMENT, "total_rays must be below 2^32 (64-bit power sums)");
+    if (rad->emission > BZR_EMISSION_LAMBERT) return set_error(BZR_ERR_INVALID_ARGUMENT, "unknown emission");
+    if (rad->surface > BZR_SURFACE_FRESNEL) return set_error(BZR_ERR_INVALID_ARGUMENT, "unknown surface");
+  }
+  const bool fresnel = with_power && rad->surface == BZR_SURFACE_FRESNEL;
   if (bzr_status s = check_emitter(em)) return s;
   if (!tg->bins_u || !tg->bins_v || !(tg->size_u > 0.0f) || !(tg->size_v > 0.0f))
     return set_error(BZR_ERR_INVALID_ARGUMENT, "target bins and sizes must be positive");
@@ -3993,7 +4193,9 @@ extern "C" bzr_status bzr_illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses
   const uint32_t B = chunk_for(ctx, total_rays);
   if (bzr_status s = ensure_buffer(ctx->scratch, ctx->scratch_bytes,
                                    belt_bytes(em->belts) + round256((size_t)B * 24) + 2 * round256((size_t)B * 4) +
-                                       round256(32) + (host ? round256(cells * 4) : 0)))
+                                       round256(32) + (host && hist ? round256(cells * 4) : 0) +
+                                       (with_power ? round256((size_t)B * 4) + round256(32) + (host ? round256(cells * 8) : 0)
+                                                   : 0)))
     return s;
   Staging st{static_cast<char *>(ctx->scratch)};
   BeltTable bt;
@@ -4003,9 +4205,20 @@ extern "C" bzr_status bzr_illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses
   float *d_rays = st.take<float>((size_t)B * 6);
   uint32_t *d_st = st.take<uint32_t>(B), *d_seg = st.take<uint32_t>(B);
   unsigned long long *d_stats = st.take<unsigned long long>(4);
-  uint32_t *d_hist = host ? st.take<uint32_t>(cells) : hist;
+  uint32_t *d_hist = host && hist ? st.take<uint32_t>(cells) : hist;
   BZR_HIP(hipMemsetAsync(d_stats, 0, 32, ctx->stream));
-  if (host) BZR_HIP(hipMemsetAsync(d_hist, 0, cells * 4, ctx->stream));
+  if (host && hist) BZR_HIP(hipMemsetAsync(d_hist, 0, cells * 4, ctx->stream));
+  float *d_w = nullptr;  // the batch's ray power, its four sums and the flux cells
+  unsigned long long *d_power = nullptr, *d_flux = reinterpret_cast<unsigned long long *>(flux);
+  if (with_power) {
+    d_w = st.take<float>(B);
+    d_power = st.take<unsigned long long>(4);
+    BZR_HIP(hipMemsetAsync(d_power, 0, 32, ctx->stream));
+    if (host) {
+      d_flux = st.take<unsigned long long>(cells);
+      BZR_HIP(hipMemsetAsync(d_flux, 0, cells * 8, ctx->stream));
+    }
+  }
   Work w;
   const bool staged = use_staged(flags, B, nb);
   if (staged)
@@ -4014,8 +4227,13 @@ extern "C" bzr_status bzr_illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses
                                     lenses[0]->sphere[3]);
   for (uint64_t first = 0; first < total_rays; first += B) {
     const uint32_t m = (uint32_t)std::min<uint64_t>(B, total_rays - first);
-    hipLaunchKernelGGL(k_emit, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays,
-                       (uint32_t *)nullptr, d_st, d_seg, sphere, set.lens[0].always, set.lens[0].n_always, d_stats);
+    if (with_power)
+      hipLaunchKernelGGL(k_emit_power, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays, d_st,
+                         d_seg, d_w, rad->emission == BZR_EMISSION_LAMBERT ? 1u : 0u, sphere, set.lens[0].always,
+                         set.lens[0].n_always, d_stats, d_power);
+    else
+      hipLaunchKernelGGL(k_emit, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays,
+                         (uint32_t *)nullptr, d_st, d_seg, sphere, set.lens[0].always, set.lens[0].n_always, d_stats);
     if (!staged) {  // the chain in place over the batch; culled rays (status NONE) are skipped
       TraceJob job{};
       job.rays = d_rays;
@@ -4025,7 +4243,10 @@ extern "C" bzr_status bzr_illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses
       job.alive_in = d_st;
       job.n = m;
       job.ld = B;
-      if (bzr_status s = run_fused<kModeStage>(ctx, set, job, flags)) return s;
+      job.weight = d_w;  // (a lossless surface leaves the weights as emitted: the plain chain)
+      job.weight_in = d_w;
+      if (bzr_status s = fresnel ? run_fused<kModePower>(ctx, set, job, flags) : run_fused<kModeStage>(ctx, set, job, flags))
+        return s;
     } else {
       for (uint32_t l = 0; l < nlens; ++l)
         for (uint32_t j = 0; j < 2; ++j) {
@@ -4035,21 +4256,53 @@ extern "C" bzr_status bzr_illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses
           o.status = d_st;
           o.segments = d_seg;
           o.ri = set.lens[l].ri;
-          if (bzr_status s = run_segment<kModeStage>(use_fast(flags), ctx, set.lens[l], d_rays, B, 0, m, d_st, o, w)) return s;
+          o.weight = d_w;
+          if (bzr_status s = fresnel ? run_segment<kModePower>(use_fast(flags), ctx, set.lens[l], d_rays, B, 0, m, d_st, o, w)
+                                     : run_segment<kModeStage>(use_fast(flags), ctx, set.lens[l], d_rays, B, 0, m, d_st, o, w))
+            return s;
         }
     }
-    hipLaunchKernelGGL(k_land, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg, make_float4(pn.x, pn.y, pn.z, pc),
-                       cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats);
+    if (with_power)
+      hipLaunchKernelGGL(k_land_power, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg,
+                         make_float4(pn.x, pn.y, pn.z, pc), cell_u, cell_v, d_rays, B, m, d_st, d_w, d_flux, d_hist, d_stats,
+                         d_power);
+    else
+      hipLaunchKernelGGL(k_land, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg, make_float4(pn.x, pn.y, pn.z, pc),
+                         cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats);
     BZR_HIP(hipGetLastError());
   }
   unsigned long long hs[4];
   BZR_HIP(hipMemcpyAsync(hs, d_stats, 32, hipMemcpyDeviceToHost, ctx->stream));
-  std::vector<uint32_t> hh(host ? cells : 0);
-  if (host) BZR_HIP(hipMemcpyAsync(hh.data(), d_hist, cells * 4, hipMemcpyDeviceToHost, ctx->stream));
+  std::vector<uint32_t> hh(host && hist ? cells : 0);
+  if (host && hist) BZR_HIP(hipMemcpyAsync(hh.data(), d_hist, cells * 4, hipMemcpyDeviceToHost, ctx->stream));
+  unsigned long long hp[4] = {0, 0, 0, 0};
+  std::vector<unsigned long long> hf(host && with_power ? cells : 0);
+  if (with_power) {
+    BZR_HIP(hipMemcpyAsync(hp, d_power, 32, hipMemcpyDeviceToHost, ctx->stream));
+    if (host) BZR_HIP(hipMemcpyAsync(hf.data(), d_flux, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
   BZR_HIP(hipStreamSynchronize(ctx->stream));
-  if (host)
+  if (host && hist)
     for (size_t k = 0; k < cells; ++k) hist[k] += hh[k];
+  if (host && with_power)
+    for (size_t k = 0; k < cells; ++k) flux[k] += hf[k];
   if (stats)
     for (int k = 0; k < 4; ++k) stats[k] = hs[k];
+  if (power)
+    for (int k = 0; k < 4; ++k) power[k] = hp[k];
   return BZR_OK;
+}
+
+extern "C" bzr_status bzr_illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
+                                     const bzr_emitter *em, uint64_t total_rays, const bzr_target *tg, uint32_t *hist,
+                                     uint64_t stats[4], uint32_t flags) {
+  return illuminate(ctx, lenses, ri, nlens, em, total_rays, tg, nullptr, nullptr, hist, stats, nullptr, flags);
+}
+
+extern "C" bzr_status bzr_illuminate_power(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
+                                           const bzr_emitter *em, uint64_t total_rays, const bzr_target *tg,
+                                           const bzr_radiometry *rad, uint64_t *flux_q32, uint32_t *hist, uint64_t stats[4],
+                                           uint64_t power_q32[4], uint32_t flags) {
+  if (!rad) return set_error(BZR_ERR_INVALID_ARGUMENT, "null radiometry");
+  return illuminate(ctx, lenses, ri, nlens, em, total_rays, tg, rad, flux_q32, hist, stats, power_q32, flags);
 }

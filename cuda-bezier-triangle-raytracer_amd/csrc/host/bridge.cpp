@@ -79,6 +79,25 @@ void traceChain(std::vector<BezierLens const *> const &lenses, Ray const *rays, 
   }
 }
 
+void traceChainPower(std::vector<BezierLens const *> const &lenses, Ray const *rays, float const *weights, std::size_t n,
+                     Ray *outRays, float *outWeights, RefractionResult *outStatus, uint32_t *outSegments, Context *ctx) {
+  Context &c = ctx ? *ctx : defaultContext();
+  std::vector<bzr_mesh const *> meshes;
+  std::vector<float> ri;
+  for (auto const *l : lenses) {
+    meshes.push_back(l->getMesh().device(c));
+    ri.push_back(l->getRefractiveIndex());
+  }
+  std::lock_guard<std::mutex> hold(c.lock());
+  for (std::size_t off = 0; off < n; off += kMaxBatch) {
+    const std::size_t m = std::min(kMaxBatch, n - off);
+    check(bzr_trace_chain_power(c.get(), meshes.data(), ri.data(), static_cast<uint32_t>(meshes.size()),
+                                records(rays + off), weights ? weights + off : nullptr, static_cast<uint32_t>(m),
+                                records(outRays + off), outWeights + off, words(outStatus + off),
+                                outSegments ? outSegments + off : nullptr, BZR_HOST_PTRS | BZR_RAYS_AOS));
+  }
+}
+
 namespace {
 // The contexts' locks, taken in id order: two calls over shared contexts cannot deadlock (a repeated context is
 // locked once).
@@ -222,6 +241,10 @@ void BezierLens::refract(Ray const *rays, RefractionResult const *expected, std:
                            static_cast<uint32_t>(m), bzr::records(outRays + off), bzr::words(outStatus + off),
                            BZR_HOST_PTRS | BZR_RAYS_AOS));
   }
+}
+
+std::tuple<Ray, RefractionResult, float> BezierLens::refractPower(Ray const &ray, RefractionResult expected) const {
+  return bzr::host::lensRefractPower(&mMesh[0], mMesh.size(), mRefractiveIndex, ray, expected);
 }
 
 std::pair<Ray, RefractionResult> BezierLens::refract(Ray const &ray, RefractionResult expected) const {

@@ -200,4 +200,10 @@ int32_t bzr_debug_newton_short(const void *patches, uint32_t n, uint32_t stride,
   return BZR_OK;
 }
 
+int32_t bzr_debug_fresnel(const float *eta, const float *cs, uint32_t n, float *t_out) {
+  if ((!eta || !cs || !t_out) && n) return bad("null argument");
+  bzr_host::fresnel_pairs(eta, cs, n, t_out);
+  return BZR_OK;
+}
+
 }  // extern "C"

@@ -11,6 +11,7 @@
 //   patchIntersect  BezierTriangle::intersect   reference/bezierTriangle.cpp:123-195
 //   meshIntersect   BezierMesh::intersect       reference/bezierMesh.cpp:206-227 (brute force, index order)
 //   lensRefract     BezierLens::refract         reference/bezierLens.cpp:4-34
+//   lensRefractPower  the same with the refraction's Fresnel transmittance (patch_math_body.inc fresnel_t)
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -129,8 +130,10 @@ Hit mesh_intersect(const float *records, std::size_t n, f3 s, f3 d, uint32_t &pa
   return best;
 }
 
-// BezierLens::refract after the intersection (trace.hip refract_hit, reference/bezierLens.cpp:8-32).
-uint32_t refract_hit(const Hit &h, float ri, f3 s, f3 d, uint32_t expected, f3 &o_s, f3 &o_d) {
+// BezierLens::refract after the intersection (trace.hip refract_hit_t, reference/bezierLens.cpp:8-32); `gain` = the
+// refraction's Fresnel transmittance when the status is not NONE.
+uint32_t refract_hit(const Hit &h, float ri, f3 s, f3 d, uint32_t expected, f3 &o_s, f3 &o_d, float &gain) {
+  gain = 1.0f;
   o_s = s;
   o_d = d;
   uint32_t st = BZR_RR_NONE;
@@ -140,6 +143,7 @@ uint32_t refract_hit(const Hit &h, float ri, f3 s, f3 d, uint32_t expected, f3 &
     const float eta = st == BZR_RR_INSIDE ? div_rn(1.0f, ri) : ri;
     const float s2 = eta * eta * (1.0f - h.cs * h.cs);
     if (s2 < 0.99f) {
+      gain = fresnel_t(eta, h.cs, s2);
       if (s2 > 1e-12f) {
         const float sgn = st == BZR_RR_INSIDE ? 1.0f : -1.0f;
         const f3 nn = scale(h.normal, sgn);
@@ -152,6 +156,15 @@ uint32_t refract_hit(const Hit &h, float ri, f3 s, f3 d, uint32_t expected, f3 &
     }
   }
   return st == expected ? st : uint32_t(BZR_RR_NONE);
+}
+
+// bzr_debug_fresnel: the shared Fresnel text for (eta, cos) pairs, with Snell's step's own s2; 0 where it does not
+// refract.
+void fresnel_pairs(const float *eta, const float *cs, uint32_t n, float *t_out) {
+  for (uint32_t i = 0; i < n; ++i) {
+    const float s2 = eta[i] * eta[i] * (1.0f - cs[i] * cs[i]);
+    t_out[i] = s2 < 0.99f ? fresnel_t(eta[i], cs[i], s2) : 0.0f;
+  }
 }
 
 // newton_tail's hook answering "not needed" (bzr_debug_newton_short)
@@ -207,22 +220,30 @@ BezierIntersection meshIntersect(BezierTriangle const *patches, std::size_t n, R
   return to_reference(h);
 }
 
-std::pair<Ray, RefractionResult> lensRefract(BezierTriangle const *patches, std::size_t n, float ri, Ray const &ray,
-                                             RefractionResult expected) {
+std::tuple<Ray, RefractionResult, float> lensRefractPower(BezierTriangle const *patches, std::size_t n, float ri,
+                                                          Ray const &ray, RefractionResult expected) {
   using namespace bzr_host;
   const f3 s = v3(ray.mStart), d = v3(ray.mDirection);
   uint32_t p;
   const Hit h = mesh_intersect(reinterpret_cast<const float *>(patches), n, s, d, p);
   f3 os, od;
-  const uint32_t st = refract_hit(h, ri, s, d, static_cast<uint32_t>(expected), os, od);
+  float t;
+  const uint32_t st = refract_hit(h, ri, s, d, static_cast<uint32_t>(expected), os, od, t);
   Ray out;
-  if (st == BZR_RR_NONE) {  // the input ray, as the batch path returns it
+  if (st == BZR_RR_NONE) {  // the input ray, as the batch path returns it; a NONE leaves the power untouched
     os = s;
     od = d;
+    t = 1.0f;
   }
   out.mStart = vec(os);
   out.mDirection = vec(od);
-  return {out, static_cast<RefractionResult>(st)};
+  return {out, static_cast<RefractionResult>(st), t};
+}
+
+std::pair<Ray, RefractionResult> lensRefract(BezierTriangle const *patches, std::size_t n, float ri, Ray const &ray,
+                                             RefractionResult expected) {
+  const auto r = lensRefractPower(patches, n, ri, ray, expected);
+  return {std::get<0>(r), std::get<1>(r)};
 }
 
 }  // namespace host

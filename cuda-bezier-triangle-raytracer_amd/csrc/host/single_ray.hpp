@@ -2,6 +2,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <tuple>
 #include <utility>
 
 #include "bzr/bzr.hpp"
@@ -10,6 +11,8 @@ namespace bzr_host {
 // BezierTriangle::intersect on one 66-word record, twice: whole, and with newton_tail's hook answering "not
 // needed" (the last normal skipped).  12 words each: t, point, cos, barycentrics, normal, what.
 void newton_short_pair(const float *record, const float ray[6], bool limitNone, float full[12], float skipped[12]);
+// The Fresnel transmittance of n (eta, cos) pairs, 0 where Snell's step does not refract (bzr_debug_fresnel).
+void fresnel_pairs(const float *eta, const float *cs, uint32_t n, float *t_out);
 }  // namespace bzr_host
 
 namespace bzr {
@@ -21,5 +24,8 @@ BezierIntersection meshIntersect(BezierTriangle const *patches, std::size_t n, R
 // BezierLens::refract(ray, expected) (reference/bezierLens.cpp:4-34); the input ray on cNone.
 std::pair<Ray, RefractionResult> lensRefract(BezierTriangle const *patches, std::size_t n, float ri, Ray const &ray,
                                              RefractionResult expected);
+// The same scan and refraction, with the refraction's Fresnel transmittance T (1 on cNone).
+std::tuple<Ray, RefractionResult, float> lensRefractPower(BezierTriangle const *patches, std::size_t n, float ri,
+                                                          Ray const &ray, RefractionResult expected);
 }  // namespace host
 }  // namespace bzr

@@ -96,7 +96,7 @@ enum {
    * `Ray` of reference/3dGeomUtil.h:168, 24 bytes) instead of [6][n].  Host or device pointers alike; the library
    * transposes on the device (48 bytes per ray each way, HBM-bound), so a C++ caller hands its std::vector<Ray>
    * over with no host-side conversion.  Accepted by bzr_intersect (rays), bzr_refract, bzr_trace_chain,
-   * bzr_trace_tiled, bzr_tiled_set_rays (rays) and bzr_tiled_trace (out_rays); other calls reject it.  Other
+   * bzr_trace_chain_power, bzr_trace_tiled, bzr_tiled_set_rays (rays) and bzr_tiled_trace (out_rays); other calls reject it.  Other
    * arrays (hits, status, segments, expected) keep their layouts. */
   BZR_RAYS_AOS = 32u
 };
@@ -231,6 +231,21 @@ bzr_status bzr_refract(bzr_ctx *ctx, const bzr_mesh *mesh, float refractive_inde
 bzr_status bzr_trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *refractive_index,
                            uint32_t nlens, const float *rays_soa, uint32_t n, float *out_rays_soa,
                            uint32_t *out_status, uint32_t *out_segments, uint32_t flags);
+/* bzr_trace_chain with the rays' power.  weight_in [n] (may be NULL: every ray starts at 1.0f) and out_weight [n]
+ * are plain rows in either ray layout, host or device memory as the rays; weight_in == out_weight is allowed.
+ * out_weight[i] = weight_in[i] times the unpolarised Fresnel transmittance T of each successful refraction of
+ * ray i, multiplied in chain order.  With eta = 1/ri entering and ri leaving, cs the hit's cosine and
+ * s2 = eta^2 (1 - cs^2) < 0.99 as Snell's step has them, in IEEE binary32 without contraction:
+ *   c1 = |cs|   c2 = sqrt(1 - s2)   rs = (eta c1 - c2) / (eta c1 + c2)   rp = (eta c2 - c1) / (eta c2 + c1)
+ *   T = 1 - 0.5 (rs rs + rp rp)
+ * always in exact arithmetic (BZR_MODE_FAST too: the Fresnel term belongs to Snell's step).  A refraction that
+ * returns NONE leaves the weight untouched, so a ray that never refracts keeps weight_in[i].  Everything else --
+ * flags, BZR_RAYS_AOS for the ray arrays, pipeline choice, out_rays / out_status / out_segments bit for bit -- is
+ * bzr_trace_chain's. */
+bzr_status bzr_trace_chain_power(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *refractive_index,
+                                 uint32_t nlens, const float *rays_soa, const float *weight_in, uint32_t n,
+                                 float *out_rays_soa, float *out_weight, uint32_t *out_status, uint32_t *out_segments,
+                                 uint32_t flags);
 /* Multi-GPU refraction chain in ONE process (C/C++ hosts without torch.distributed):
  * image-plane tiles are dealt round-robin to the contexts, one per device.  Tile k is the rays
  * [k * tile_rays, (k + 1) * tile_rays) of the SoA input (callers order rays tile-major, e.g. 64x64-pixel
@@ -347,6 +362,23 @@ bzr_status bzr_emit(bzr_ctx *ctx, const bzr_emitter *em, uint64_t first, uint32_
 bzr_status bzr_illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *refractive_index,
                           uint32_t nlens, const bzr_emitter *em, uint64_t total_rays, const bzr_target *target,
                           uint32_t *hist, uint64_t stats[4], uint32_t flags);
+/* Radiometry of bzr_illuminate_power: each ray's initial power w0 and what a lens surface transmits. */
+enum { BZR_EMISSION_UNIFORM = 0, BZR_EMISSION_LAMBERT = 1 };   /* w0 = 1  |  w0 = direction . (+x) = dx */
+enum { BZR_SURFACE_LOSSLESS = 0, BZR_SURFACE_FRESNEL = 1 };    /* T = 1   |  T of bzr_trace_chain_power */
+typedef struct bzr_radiometry { uint32_t emission, surface; } bzr_radiometry;
+/* bzr_illuminate (same emitter stream, sphere cull, batching and pipelines) with ray power.  Power is summed as
+ * unsigned 64-bit fixed point with 32 fraction bits, q(w) = (uint64) trunc(w x 2^32) for w in [0, 1]: integer sums
+ * do not depend on the order of arrival, so every output is bit-reproducible.  Each landed ray adds q(w) to its
+ * cell of flux_q32[bins_v][bins_u] (accumulates: zero it first) and, when hist is not NULL, one count to hist as
+ * bzr_illuminate does.  stats (may be NULL): the BZR_ILLUM_* counts.  power_q32 (may be NULL), same fixed point:
+ * [EMITTED] the sum of q(w0) over every emitted ray, [CULLED] over the culled ones, [EXITED] and [LANDED] the sums
+ * of q(w).  total_rays >= 2^32 (the 64-bit sums could overflow), an unknown emission or surface, or a NULL rad or
+ * flux_q32 return BZR_ERR_INVALID_ARGUMENT before any output is touched.  Synchronous; flux_q32 and hist are
+ * host or device memory per `flags`. */
+bzr_status bzr_illuminate_power(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *refractive_index,
+                                uint32_t nlens, const bzr_emitter *em, uint64_t total_rays, const bzr_target *target,
+                                const bzr_radiometry *rad, uint64_t *flux_q32, uint32_t *hist, uint64_t stats[4],
+                                uint64_t power_q32[4], uint32_t flags);
 /* The bounding sphere bzr_illuminate culls with: center xyz, radius. */
 bzr_status bzr_mesh_bounding_sphere(const bzr_mesh *mesh, float out[4]);
 

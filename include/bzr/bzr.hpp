@@ -30,6 +30,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <type_traits>
 #include <unordered_map>
 #include <unordered_set>
@@ -435,6 +436,9 @@ class BezierLens final {
   BezierLens(float ri, BezierMesh const &mesh) : mRefractiveIndex(ri), mMesh(mesh) {}
   BezierLens(float ri, BezierMesh &&mesh) : mRefractiveIndex(ri), mMesh(std::move(mesh)) {}
   std::pair<Ray, RefractionResult> refract(Ray const &ray, RefractionResult expected) const;  // host, as intersect(Ray)
+  // refract(ray, expected) with the refraction's unpolarised Fresnel transmittance T (bzr.h bzr_trace_chain_power;
+  // 1 on cNone): host, the same ray and status bits as refract.
+  std::tuple<Ray, RefractionResult, float> refractPower(Ray const &ray, RefractionResult expected) const;
   void refract(Ray const *rays, RefractionResult const *expected, std::size_t n, Ray *outRays,
                RefractionResult *outStatus, bzr::Context *ctx = nullptr) const;
   float getRefractiveIndex() const { return mRefractiveIndex; }
@@ -449,6 +453,11 @@ namespace bzr {
 // Whole refraction chain through `lenses` in one GPU launch (reference/test.cpp:376-401 semantics).
 void traceChain(std::vector<BezierLens const *> const &lenses, Ray const *rays, std::size_t n, Ray *outRays,
                 RefractionResult *outStatus, uint32_t *outSegments = nullptr, Context *ctx = nullptr);
+// traceChain with the rays' power (bzr_trace_chain_power): weights [n] may be null (every ray starts at 1) and may
+// be outWeights; outWeights[i] = weights[i] x the Fresnel transmittance of each successful refraction of ray i.
+void traceChainPower(std::vector<BezierLens const *> const &lenses, Ray const *rays, float const *weights, std::size_t n,
+                     Ray *outRays, float *outWeights, RefractionResult *outStatus, uint32_t *outSegments = nullptr,
+                     Context *ctx = nullptr);
 // The same chain over several devices from one process (bzr_trace_tiled): tiles of tileRays
 // consecutive rays dealt round-robin to `ctxs` (one per device, distinct), results in input order.
 void traceChainTiled(std::vector<Context *> const &ctxs, std::vector<BezierLens const *> const &lenses,

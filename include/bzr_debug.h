@@ -88,6 +88,10 @@ int32_t bzr_debug_wave_clock_rate(void *ctx, unsigned long long *clock, uint32_t
  * No device.  Returns 0 on success. */
 int32_t bzr_debug_newton_short(const void *patches, uint32_t n, uint32_t stride, const uint32_t *patch,
                                const float *rays, const uint8_t *limit, uint32_t m, float *full, float *skipped);
+/* Host evaluation of the Fresnel transmittance the kernels run (patch_math_body.inc fresnel_t, the text
+ * bzr_trace_chain_power documents in bzr.h): for each of n pairs (eta[i], cs[i]), s2 = eta^2 (1 - cs^2) as Snell's
+ * step computes it and t_out[i] = T, or 0 where s2 >= 0.99 (no refraction).  No device.  Returns 0 on success. */
+int32_t bzr_debug_fresnel(const float *eta, const float *cs, uint32_t n, float *t_out);
 #ifdef __cplusplus
 }
 #endif

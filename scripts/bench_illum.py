@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
 """Throughput of the illumination pipeline (bzr_illuminate: emit -> sphere cull -> chain -> target counts)
 on the cfg2 lens, emitter just behind it (inside the lens's bounding sphere, so nothing is culled and
-every ray is traced).  Prints one JSON line: emitted rays / s and the landed fraction."""
+every ray is traced).  Prints one JSON line: emitted rays / s and the landed fraction.
+
+usage: bench_illum.py [total_rays] [--power]
+--power times bzr_illuminate_power (Lambert emitter, Fresnel surfaces: k_emit_power -> chain with weights ->
+k_land_power, 64-bit flux cells) beside bzr_illuminate on the same rays, alternating, and prints one more JSON line
+with both; the chain kernels' share comes from the context's event timing in a separate pass, the rest of a call is
+its emit and landing kernels and the host's part.  Per-kernel durations of k_land / k_land_power: run this under a
+kernel-trace profiler."""
 import json
+import statistics
 import sys
 import time
 from pathlib import Path
@@ -16,7 +24,9 @@ from bzr_amd.configs import CONFIGS, build_lens  # noqa: E402
 
 
 def main():
-    total = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 24
+    args = [a for a in sys.argv[1:] if a != "--power"]
+    power = "--power" in sys.argv[1:]
+    total = int(args[0]) if args else 1 << 24
     ctx = bzr_amd.Context(0)
     dm = bzr_amd.DeviceMesh(ctx, build_lens(bzr_amd.TriMesh, CONFIGS["cfg2"].lenses[0]).bezier_patches())
     em = bzr_amd.Emitter(origin=(0.0, -0.5, -0.5), edge_u=(0.0, 1.0, 0.0), edge_v=(0.0, 0.0, 1.0), parts_u=4,
@@ -30,6 +40,39 @@ def main():
     print(json.dumps({"workload": "illuminate cfg2 lens, emitter at x=0 (no cull), 512^2 target",
                       "rays": total, "seconds": round(dt, 4), "mrays_per_s": round(total / dt / 1e6, 1),
                       "stats": stats, "landed_fraction": round(stats["landed"] / total, 5)}))
+    if not power:
+        return
+
+    def counts():
+        return bzr_amd.illuminate(ctx, [dm], [1.3], em, total, tg)[1]
+
+    def weighted():
+        return bzr_amd.illuminate_power(ctx, [dm], [1.3], em, total, tg)[2:]
+
+    bzr_amd.illuminate_power(ctx, [dm], [1.3], em, 1 << 20, tg)  # warm-up
+    wall = {"illuminate": [], "illuminate_power": []}
+    for _ in range(5):  # alternating, so drift hits both alike
+        for name, call in (("illuminate", counts), ("illuminate_power", weighted)):
+            t0 = time.perf_counter()
+            out = call()
+            wall[name].append(time.perf_counter() - t0)
+    pstats, ppower = out
+    chain = {}
+    for name, call in (("illuminate", counts), ("illuminate_power", weighted)):  # event timing perturbs the wall time
+        ctx.timing(True)
+        ctx.timing_report()
+        call()
+        chain[name] = sum(v[0] for v in ctx.timing_report().values()) / 1e3
+        ctx.timing(False)
+    med = {k: statistics.median(v) for k, v in wall.items()}
+    print(json.dumps({"workload": "illuminate_power (Lambert, Fresnel) beside illuminate, same rays, 512^2 target",
+                      "rays": total,
+                      "seconds": {k: round(v, 4) for k, v in med.items()},
+                      "mrays_per_s": {k: round(total / v / 1e6, 1) for k, v in med.items()},
+                      "chain_kernels_seconds": {k: round(v, 4) for k, v in chain.items()},
+                      "emit_land_host_seconds": {k: round(med[k] - chain[k], 4) for k in med},
+                      "power_over_counts": round(med["illuminate_power"] / med["illuminate"], 4),
+                      "stats": pstats, "landed_power_fraction": round(ppower["landed"] / max(ppower["emitted"], 1), 5)}))
 
 
 if __name__ == "__main__":
