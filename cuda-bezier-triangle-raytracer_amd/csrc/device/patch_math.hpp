@@ -120,10 +120,6 @@ struct Hit {
 #define BZR_NEWTON_UNROLL 1
 #endif
 constexpr uint32_t kFollow2 = 2u, kNone = 3u, kIntersect = 4u;
-// BZR_PASS_FLAT (default 0): patch_intersect's gate without the early return (see there).
-#ifndef BZR_PASS_FLAT
-#define BZR_PASS_FLAT 0
-#endif
 
 // Correctly rounded binary32 division and square root.  HIP compiles `/` and
 // __builtin_sqrtf correctly rounded by default (-fhip-fp32-correctly-rounded-divide-sqrt);
@@ -163,12 +159,8 @@ __device__ __forceinline__ float div_unscaled(float a, float b, float y) {  // y
 // the largest float whose correctly rounded square root is <= 0.01f -- checked over all 2^32 float bit
 // patterns, NaN and negatives included (tests/test_sqrt_threshold.py repeats it on a sample).
 __device__ __forceinline__ bool sqrt_above_hundredth(float z) { return z > __uint_as_float(0x38d1b718u); }
-#ifndef BZR_UNIT_SHARED
-#define BZR_UNIT_SHARED 1
-#endif
 // Eigen normalized() with z = a.a: a / sqrt(z) when z > 0, else a unchanged.
 __device__ __forceinline__ f3 unit_or_self(f3 a, float z) {
-#if BZR_UNIT_SHARED
   // the plain chain for every lane; lanes outside the guard (z <= 0 among them) redo it with the full
   // sequences or keep a (the branch is rarely taken, and the common path needs no copies at the join)
   const float s = sqrt_unscaled(z);
@@ -184,11 +176,6 @@ __device__ __forceinline__ f3 unit_or_self(f3 a, float z) {
     }
   }
   return r;
-#else
-  if (!(z > 0.0f)) return a;
-  float s = sqrt_rn(z);
-  return mk(div_rn(a.x, s), div_rn(a.y, s), div_rn(a.z, s));
-#endif
 }
 // BZR_DIV_HEIGHTS (default 1): newton_tail's two bracket quotients din = hIn / cos and dout = hOut / cos
 // (reference/bezierTriangle.cpp:132-133) share their divisor, so they share one refined reciprocal and take the
@@ -264,20 +251,6 @@ __device__ __forceinline__ Hit patch_intersect(const P &p, f3 s, f3 d, bool limi
   float ic, it;
   bool valid = plane_ray(p.n(), p.c(), s, d, ip, ic, it);
   (void)valid;
-#if BZR_PASS_FLAT
-  if (!kGated) {
-    // Branch-free form: every lane of the call runs the Newton tail and lanes whose gate fails get the
-    // kNone record afterwards -- the same bits for the lanes that pass, and no divergent branch, so the
-    // record's scalar loads need not wait inside one (they batch ahead of the arithmetic).
-    const f3 b0 = matvec(p, ip);
-    const bool in = (b0.x >= 0.0f) & (b0.x <= 1.0f) & (b0.y >= 0.0f) & (b0.y <= 1.0f) & (b0.z >= 0.0f) & (b0.z <= 1.0f);
-    const bool ok = valid & (fabsf(it) > -p.hin()) & (fabsf(it) > p.hout()) & (limitNone | in);
-    Hit r;
-    if constexpr (kFast) r = fast::newton_tail(p, s, d, ic, it, need);
-    else r = newton_tail(p, s, d, ic, it, need);
-    return ok ? r : h;
-  }
-#endif
   if (!kGated) {
     if (!(valid && fabsf(it) > -p.hin() && fabsf(it) > p.hout())) return h;
     f3 b0 = matvec(p, ip);

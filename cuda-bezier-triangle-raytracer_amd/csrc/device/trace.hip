@@ -24,7 +24,6 @@
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
-#include <functional>
 
 #include <cstdio>
 #include <cstring>
@@ -74,7 +73,7 @@ struct bzr_mesh {
   bzr_host::Bvh4ObbNode *obb_near;
   float4 *kids;      // the far tree's children AoS (2 float4 per child: lo.xyz ref, hi.xyz 0): the bundle walk's
   float4 *kids_near; // per-lane child records (kids_of), and the near tree's
-  float4 *wide;      // two levels per node for k_traverse's bundle walk (BZR_TRAV_WIDE, wide_of): node i's 16
+  float4 *wide;      // two levels per node for k_traverse's bundle walk (wide_of): node i's 16
   float4 *wide_near; // grandchild slots, 2 float4 each as in kids
   float4 *always;   // 8 float4 per always-tested patch (bvh.hpp Bvh::always): planar record with the patch index
                     // in its last word, then the wedge pre-test (always_wedge: w.xyz L H B C 0) and 8 pad words
@@ -90,10 +89,7 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr uint32_t kMaxLenses = 8;
-#ifndef BZR_MAX_CAND
-#define BZR_MAX_CAND 40
-#endif
-constexpr uint32_t kMaxCand = BZR_MAX_CAND;  // candidate list length per ray and segment
+constexpr uint32_t kMaxCand = 40;  // candidate list length per ray and segment
 constexpr uint32_t kOverflow = 0x8000u;  // count flag: resolve with the full scan (the low bits keep the listed count)
 // Traversal stack entries per wave (LDS).  BZR_STACK (A/B and test knob): a tiny stack makes waves run out
 // mid-walk, which sends the affected lanes to the in-order full scan (tests/test_gpu_variants.py).
@@ -117,23 +113,7 @@ __device__ __forceinline__ uint32_t xcd_contiguous(uint32_t b, uint32_t nblocks)
   const uint32_t q = nblocks / kXcds, r = nblocks % kXcds, x = b % kXcds;
   return x * q + (x < r ? x : r) + b / kXcds;
 }
-// Block b's index under a dealing policy: 0 = dispatch order (XCD x gets every 8th block), 1 =
-// xcd_contiguous, G > 1 = runs of G blocks dealt round-robin to the XCDs (whole rounds of 8 runs; the
-// ragged rest keeps its index).  A bijection on [0, nblocks) in every case.
-template <uint32_t kPolicy>
-__device__ __forceinline__ uint32_t deal_blocks(uint32_t b, uint32_t nblocks) {
-  if constexpr (kPolicy == 0) {
-    return b;
-  } else if constexpr (kPolicy == 1) {
-    return xcd_contiguous(b, nblocks);
-  } else {
-    const uint32_t full = nblocks / (kXcds * kPolicy) * (kXcds * kPolicy);
-    if (b >= full) return b;
-    const uint32_t x = b % kXcds, k = b / kXcds;
-    return (k / kPolicy * kXcds + x) * kPolicy + k % kPolicy;
-  }
-}
-// Threads per k_traverse block (BZR_TRAV_BLOCK, default 64): one-wave blocks let a finished wave be replaced
+// Threads per k_traverse block (kTravBlock): one-wave blocks let a finished wave be replaced
 // at once, as in k_trace; 256 (4 waves sharing a CU's scalar cache on neighbouring rays, rounds 1-3) measured
 // 0.5-1 % slower on cfg5 and 0.1-0.2 % on cfg3 at bench level, 128 4 % slower on cfg3
 // (profiles/r04_bench_ab_trav_block.jsonl).
@@ -148,75 +128,24 @@ __device__ __forceinline__ uint32_t deal_blocks(uint32_t b, uint32_t nblocks) {
 #define BZR_TRAV_ABLOCK 1
 #endif
 static_assert(BZR_TRAV_ABLOCK == 0 || BZR_TRAV_ABLOCK == 1, "BZR_TRAV_ABLOCK: 0 or 1");
-#ifndef BZR_TRAV_BLOCK
-#define BZR_TRAV_BLOCK 64
-#endif
 #ifndef BZR_ABLOCK_BLOCK
 #define BZR_ABLOCK_BLOCK 256
 #endif
 constexpr uint32_t kAblockMin = 64, kAblockMax = 1024, kAblockBlock = BZR_ABLOCK_BLOCK;  // threads per pre-testing block
-constexpr int kTravBlock = BZR_TRAV_BLOCK;
-// BZR_SLAB_FMA (default 1): the traversal slab test as fma(lo, inv, -s*inv) (mirrored by bvh.cpp slab_h).
-#ifndef BZR_SLAB_FMA
-#define BZR_SLAB_FMA 1
-#endif
-// BZR_NEWTON_XCD (default 0): k_newton waves take chunks in XCD-contiguous order (measured +6 %, off).
-// BZR_GATE_FLAT (default 1): planar_gate without early-out branches (see there).
-// BZR_NODE_ASM (default 0): fetch a BVH node's two halves with one inline-asm pair of scalar loads and
-// a single wait (node_children).
-#ifndef BZR_NODE_ASM
-#define BZR_NODE_ASM 0
-#endif
-// BZR_BUNDLE_SPREAD (default 0.5): waves whose ray directions spread wider (bundle_setup_dpp) take the
-// per-lane walk instead of the bundle walk.
-#ifndef BZR_BUNDLE_SPREAD
-#define BZR_BUNDLE_SPREAD 0.5f
-#endif
-// BZR_TRAV_PRETEST (default 1): k_traverse's bundle walk pre-tests its queued leaves against the bundle
-// (bundle_gate_keep, 64 leaves per pass) before the per-lane gates: the host replay keeps 64 % of cfg5's
-// bundle leaves, 48 % of cfg3's, 36 % of cfg4's; k_traverse cfg5 -1.2 %, cfg3 -4 %, cfg2 within noise
-// (profiles/r03s2_ab_leaf_pretest.jsonl; 68 VGPRs: 7 waves per SIMD instead of 8).
-#ifndef BZR_TRAV_PRETEST
-#define BZR_TRAV_PRETEST 1
-#endif
-// BZR_TRAV_LEAF_PAIRS (default 1): k_traverse's bundle walk fetches its queued leaves two at a time (cfg5 /
-// cfg3 / cfg2 staged k_traverse -2 to -2.5 %, frames -1 %; profiles/r03s2_ab_leaf_pairs.jsonl).
-#ifndef BZR_TRAV_LEAF_PAIRS
-#define BZR_TRAV_LEAF_PAIRS 1
-#endif
-// BZR_TRAV_WIDE (default 1): k_traverse's bundle walk takes two tree levels per batch over 16-slot records
-// (bzr_mesh wide / wide_near: each node's grandchildren), 4 nodes per batch instead of 16 nodes' children;
-// 2: three levels over 64-slot records (one node per batch, a 4x deeper LDS stack); 0: one level.
-#ifndef BZR_TRAV_WIDE
-#define BZR_TRAV_WIDE 1
-#endif
-constexpr uint32_t kWideSlots = BZR_TRAV_WIDE == 2 ? 64u : 16u;  // slots per node of the wide records
-// k_traverse's stack: a three-level batch (BZR_TRAV_WIDE 2) can push 64 entries at once
-constexpr int kTravStack = BZR_TRAV_WIDE == 2 ? 4 * kStack : kStack;
+constexpr int kTravBlock = 64;
+// Waves whose ray directions spread wider than this (bundle_setup_dpp) take the per-lane walk instead of the
+// bundle walk.
+constexpr float kBundleSpread = 0.5f;
+// Slots per node of the wide records (bzr_mesh wide / wide_near: each node's grandchildren): k_traverse's
+// bundle walk takes two tree levels per batch over them, 4 nodes per batch instead of 16 nodes' children
+// (profiles/r04_ab_wide_walk.jsonl).
+constexpr uint32_t kWideSlots = 16u;
 // BZR_TRACE_WIDE (default 1, with BZR_TRACE_BUNDLE): k_trace's bundle walk over the same two-level records.
 #ifndef BZR_TRACE_WIDE
 #define BZR_TRACE_WIDE 1
 #endif
-// BZR_TRAV_BUNDLE (default 1): k_traverse walks with the wave-bundle test in batches (traverse_rays):
-// cfg5 8192^2 staged k_traverse 6.61 -> 5.07 ms per frame, cfg3 0.283 -> 0.235, cfg2 0.134 -> 0.143
-// (profiles/r03s2_ab_bundle_walk.jsonl).
-#ifndef BZR_TRAV_BUNDLE
-#define BZR_TRAV_BUNDLE 1
-#endif
-#ifndef BZR_GATE_FLAT
-#define BZR_GATE_FLAT 1
-#endif
-#ifndef BZR_NEWTON_XCD
-#define BZR_NEWTON_XCD 0
-#endif
 // Blocks of k_resolve at most (its overflow part is grid-stride over (overflow ray, patch slice) items).
-#ifndef BZR_OVERFLOW_BLOCKS
-#define BZR_OVERFLOW_BLOCKS 2048u
-#endif
-// BZR_NEWTON_GATED (default 1): k_newton skips the planar gate its pairs already passed in k_traverse.
-#ifndef BZR_NEWTON_GATED
-#define BZR_NEWTON_GATED 1
-#endif
+constexpr uint32_t kOverflowBlocks = 2048u;
 // BZR_DENSE_MIN (default 16): the staged pair layout.  A patch bucket's pairs fill whole 64-pair chunks of
 // that one patch (dense chunks: patch-uniform Newton passes, every lane busy); its last, partial chunk is
 // padded to a whole chunk when it holds at least this many pairs, else its pairs go to the sparse region
@@ -245,7 +174,7 @@ struct MeshView {
   const float4 *__restrict__ always;  // patches without a proven gate region: gate-tested by every wave-segment
   const float4 *__restrict__ kids;       // AoS child records of nodes / nodes_near (bzr_mesh)
   const float4 *__restrict__ kids_near;
-  const float4 *__restrict__ wide;       // 16 grandchild records per node (BZR_TRAV_WIDE)
+  const float4 *__restrict__ wide;       // 16 grandchild records per node (wide_of)
   const float4 *__restrict__ wide_near;
   uint32_t n_always;
   uint32_t n;
@@ -288,9 +217,8 @@ __device__ __forceinline__ Hit no_hit() {
 // evaluated from the 64-byte scan record; same arithmetic as patch_intersect's first lines.
 // `gt` gets the plane distance t (whatever the decision).
 __device__ __forceinline__ bool planar_gate(float4 q0, float4 q1, float4 q2, float4 q3, f3 s, f3 d, float &gt) {
-#if BZR_GATE_FLAT
   // Branch-free: every term is evaluated and the conditions are combined with '&' (the same decision as
-  // plane_ray's early outs below -- a lane with |cos| < 1e-5 fails whatever its t), so the walk runs no
+  // plane_ray's early outs -- a lane with |cos| < 1e-5 fails whatever its t), so the walk runs no
   // exec-mask bookkeeping (s_and_saveexec / s_or exec per condition) on the scalar unit.
   const f3 n = mk(q0.x, q0.y, q0.z);
   const float cs = dot(d, n);
@@ -302,19 +230,6 @@ __device__ __forceinline__ bool planar_gate(float4 q0, float4 q1, float4 q2, flo
   const float b1 = q2.y * ip.x + (q2.z * ip.y + q2.w * ip.z);
   const float b2 = q3.x * ip.x + (q3.y * ip.y + q3.z * ip.z);
   return valid & (b0 >= 0.0f) & (b0 <= 1.0f) & (b1 >= 0.0f) & (b1 <= 1.0f) & (b2 >= 0.0f) & (b2 <= 1.0f);
-#else
-  f3 n = mk(q0.x, q0.y, q0.z);
-  f3 ip;
-  float ic, it;
-  bool valid = plane_ray(n, q0.w, s, d, ip, ic, it);
-  gt = it;
-  if (!(valid && fabsf(it) > -q1.x && fabsf(it) > q1.y)) return false;
-  // row-major copy of M: rows (q1.z q1.w q2.x) (q2.y q2.z q2.w) (q3.x q3.y q3.z)
-  float b0 = q1.z * ip.x + (q1.w * ip.y + q2.x * ip.z);
-  float b1 = q2.y * ip.x + (q2.z * ip.y + q2.w * ip.z);
-  float b2 = q3.x * ip.x + (q3.y * ip.y + q3.z * ip.z);
-  return b0 >= 0.0f && b0 <= 1.0f && b1 >= 0.0f && b1 <= 1.0f && b2 >= 0.0f && b2 <= 1.0f;
-#endif
 }
 __device__ __forceinline__ bool planar_gate(float4 q0, float4 q1, float4 q2, float4 q3, f3 s, f3 d) {
   float gt;
@@ -418,17 +333,10 @@ __device__ __forceinline__ float safe_inv(float x) {
 // Conservative only (the gate-region boxes are padded for its rounding, bvh.cpp): with FMA each
 // plane distance is one fma(lo, inv, -s*inv), error <= (|s| + |t|) * 2^-23 < the pad.
 __device__ __forceinline__ bool slab(float4 lo, float4 hi, f3 s, f3 sinv, f3 inv) {
-#if BZR_SLAB_FMA
   (void)s;
   float ax = __builtin_fmaf(lo.x, inv.x, -sinv.x), bx = __builtin_fmaf(hi.x, inv.x, -sinv.x);
   float ay = __builtin_fmaf(lo.y, inv.y, -sinv.y), by = __builtin_fmaf(hi.y, inv.y, -sinv.y);
   float az = __builtin_fmaf(lo.z, inv.z, -sinv.z), bz = __builtin_fmaf(hi.z, inv.z, -sinv.z);
-#else
-  (void)sinv;
-  float ax = (lo.x - s.x) * inv.x, bx = (hi.x - s.x) * inv.x;
-  float ay = (lo.y - s.y) * inv.y, by = (hi.y - s.y) * inv.y;
-  float az = (lo.z - s.z) * inv.z, bz = (hi.z - s.z) * inv.z;
-#endif
   float tnear = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
   float tfar = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
   return tnear <= tfar && tfar >= 0.0f;
@@ -473,19 +381,7 @@ __device__ __forceinline__ void node_children(const bzr_host::Bvh4Node *nodes, c
   }
   // the whole 128-byte node in two 64-byte scalar loads and one wait (all words used unconditionally)
   const cu32x16 *np = (const cu32x16 *)(uintptr_t)(nodes + ref);
-#if BZR_NODE_ASM
-  // Both loads issued back to back, then one wait.  Left to the compiler, k_trace's walk got a wait
-  // between the two (a scalar load's destination may still have a write pending from the previous
-  // iteration's leaf load on some path, and scalar loads return out of order, so the second load waited
-  // for everything): two L2 round trips per node.  Early-clobber outputs: the first load must not
-  // overwrite the address pair the second one reads.
-  u32x16 na, nb;
-  asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx16 %1, %2, 0x40\n\ts_waitcnt lgkmcnt(0)"
-               : "=&s"(na), "=&s"(nb)
-               : "s"(np));
-#else
   const u32x16 na = np[0], nb = np[1];
-#endif
   // words: lo.x[0..3] lo.y lo.z hi.x | hi.y hi.z child[0..3] pad
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
@@ -857,7 +753,7 @@ __device__ __forceinline__ uint32_t bundle_batch(const float4 *kids, uint32_t *s
   // (the lane index laundered: lane-derived addresses hoisted out of the walk stayed live across the Newton
   // passes of k_trace and cost it a wave of occupancy)
   asm volatile("" : "+v"(lane));
-  constexpr uint32_t kShift = kSlots == 64u ? 6u : (kSlots == 16u ? 4u : 2u);
+  constexpr uint32_t kShift = kSlots == 16u ? 4u : 2u;
   constexpr int kNodes = 64 / (int)kSlots;
   const uint32_t q = lane >> kShift, c = lane & (kSlots - 1u);
   // at most (kCap - sp) / (kSlots - 1) nodes (at least one), so their <= kSlots children each fit: the stack
@@ -1017,11 +913,6 @@ __device__ __forceinline__ bool bundle_gate_keep(const float *B, float4 q0, floa
 #else
 #define BZR_PHASE(k)
 #endif
-// BZR_TRAV_PRIO (A/B knob, default 0): the whole k_traverse wave at s_setprio(N), ahead of the other frame's
-// k_newton waves that share its CUs when frames are in flight.
-#ifndef BZR_TRAV_PRIO
-#define BZR_TRAV_PRIO 0
-#endif
 // The lanes whose gate of patch b passed list it as their next candidate (while the list has room; a lane
 // past kMaxCand overflows to the full scan).  (Counting the listing lanes into b's histogram word right here --
 // b is wave-uniform, so one atomic without return per wave -- and ranking the pairs in k_place instead of
@@ -1046,9 +937,6 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
   uint32_t ph_cur = 0;
 #endif
   uint32_t c_nodes = 0, c_leaves = 0, c_gates = 0;  // work counters (with counters on; wave-uniform)
-#if BZR_TRAV_PRIO
-  __builtin_amdgcn_s_setprio(BZR_TRAV_PRIO);  // the walk's chain of loads ahead of other waves' Newton passes
-#endif
   bool active = i < n && (alive == nullptr || alive[off + i] != BZR_RR_NONE);
   f3 s = mk(0.0f, 0.0f, 0.0f), d = s;
   if (i < n) load_ray(rays, ld, off + i, s, d);
@@ -1072,28 +960,21 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
   int sp = 0;  // the node to visit next stays in a scalar register; the other hit children go to stk
   uint32_t next = (m.n > 0 && __any(active)) ? 0u : 0xFFFFFFFFu;
   unsigned long long next_hm = 0ull;
-#if BZR_TRAV_BUNDLE
   // the bundle walk (trace_segment's): batches of up to 16 nodes against the wave's ray bundle, hit leaves
   // queued in pend and gate-tested by every active lane
   const bool walk = next != 0xFFFFFFFFu;  // (the bundle words are then in bl, for the always list too)
   bool bwalk = false;                    // the walk choice (trace_segment's)
   bool narrow = false;                   // else every node is tested per lane (as oriented-box nodes are)
   if (walk) {
-    narrow = bundle_setup_dpp(active, s, d, bl, threadIdx.x & 63u) <= BZR_BUNDLE_SPREAD;
+    narrow = bundle_setup_dpp(active, s, d, bl, threadIdx.x & 63u) <= kBundleSpread;
     if ((threadIdx.x & 63u) == 0u) stk[0] = 0u;
     sp = 1;
     next = 0xFFFFFFFFu;
     bwalk = true;
   }
-  const float4 *kids = near_tier ? m.kids_near : m.kids;
-#if BZR_TRAV_WIDE
   const float4 *wide = near_tier ? m.wide_near : m.wide;
-  (void)kids;
-#endif
   uint32_t npend = 0, pi = 0;  // leaves queued in pend, next to gate-test (uniform)
-#if BZR_TRAV_PRETEST
   uint32_t nraw = 0;  // leaves queued in raw, not yet pre-tested
-#endif
   // the always list's block pre-test (every thread of the block gets here: no early exit above)
   if constexpr (kAblock != 0) {
     if (!walk) bundle_setup_dpp(active, s, d, bl, threadIdx.x & 63u);  // (an empty wave's bundle is the identity)
@@ -1122,7 +1003,6 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
   while (bwalk) {
     if (pi < npend) {
       BZR_PHASE(1)
-#if BZR_TRAV_LEAF_PAIRS
       // two queued leaves per step: both 64-byte records in flight together (one wait for two round trips)
       const bool two = pi + 1u < npend;
       const uint32_t slot0 = __builtin_amdgcn_readfirstlane(pend[pi]);
@@ -1141,21 +1021,9 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
       if (two)
         list_candidate(active & planar_gate(leaf_q(r1, 0), leaf_q(r1, 1), leaf_q(r1, 2), leaf_q(r1, 3), s, d),
                        r1[15], w, n, i, cnt);
-#else
-      const uint32_t slot = __builtin_amdgcn_readfirstlane(pend[pi]);
-      ++pi;
-      const u32x16 r = *((const cu32x16 *)(uintptr_t)leaf + slot);
-      if (counters) {
-        ++c_leaves;
-        c_gates += (uint32_t)__popcll(__ballot(active));
-      }
-      list_candidate(active & planar_gate(leaf_q(r, 0), leaf_q(r, 1), leaf_q(r, 2), leaf_q(r, 3), s, d),
-                     r[15], w, n, i, cnt);
-#endif
       continue;
     }
     BZR_PHASE(2)
-#if BZR_TRAV_PRETEST
     if (sp == 0 || nraw > 64u) {  // the queued leaves' wave-level gate pre-test: the survivors go to pend
       if (nraw == 0u) break;
       pi = npend = 0;
@@ -1177,12 +1045,6 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
     }
     uint32_t *qbuf = raw;  // where this step queues its leaves
     uint32_t &qn = nraw;
-#else
-    if (sp == 0) break;
-    pi = npend = 0;
-    uint32_t *qbuf = pend;
-    uint32_t &qn = npend;
-#endif
     const uint32_t top = __builtin_amdgcn_readfirstlane(stk[sp - 1]);
     if (!narrow || (top & bzr_host::kObbFlag)) {  // one node, its children tested by each lane's own ray
       --sp;
@@ -1200,7 +1062,7 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
         if (ch[c] & bzr_host::kLeafFlag) {
           if ((threadIdx.x & 63u) == 0u) qbuf[qn] = ch[c] & ~bzr_host::kLeafFlag;
           ++qn;
-        } else if (sp < kTravStack) {
+        } else if (sp < kStack) {
           if ((threadIdx.x & 63u) == 0u) stk[sp] = ch[c];
           ++sp;
         } else if ((hm >> (threadIdx.x & 63u)) & 1ull) {
@@ -1211,15 +1073,10 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
     }
     bool full;
     uint32_t k;
-#if BZR_TRAV_WIDE
-    qn += bundle_batch<kTravStack, kWideSlots>(wide, stk, sp, qbuf, bl, threadIdx.x & 63u, full, k, qn);
-#else
-    qn += bundle_batch<kTravStack>(kids, stk, sp, qbuf, bl, threadIdx.x & 63u, full, k, qn);
-#endif
+    qn += bundle_batch<kStack, kWideSlots>(wide, stk, sp, qbuf, bl, threadIdx.x & 63u, full, k, qn);
     if (full && active) cnt |= kOverflow;  // stack exhausted: every active lane takes the full scan
     if (counters) c_nodes += k;
   }
-#endif
   BZR_PHASE(3)
   while (next != 0xFFFFFFFFu || sp > 0) {  // the per-lane walk
     const uint32_t node = next != 0xFFFFFFFFu ? next : __builtin_amdgcn_readfirstlane(stk[--sp]);
@@ -1245,7 +1102,7 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
         list_candidate(hit[c] & planar_gate(q0, q1, q2, q3, s, d), r[15], w, n, i, cnt);
       } else {
         if (next != 0xFFFFFFFFu) {
-          if (sp < kTravStack) stk[sp++] = next;
+          if (sp < kStack) stk[sp++] = next;
           else if ((next_hm >> (threadIdx.x & 63u)) & 1ull) cnt |= kOverflow;  // stack exhausted: full scan
         }
         next = ch[c];
@@ -1256,9 +1113,7 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
   // the always list (patches without a proven gate region, bvh.cpp): gate-tested for every active ray
   BZR_PHASE(4)
   if (m.n_always && __any(active)) {
-#if BZR_TRAV_BUNDLE
     if (!walk)  // (the bundle walk built it already)
-#endif
       bundle_to_lds(active, s, d, bl, threadIdx.x & 63u);
     if constexpr (kAblock != 0) {
       const uint32_t words = (m.n_always + 63u) / 64u;
@@ -1310,10 +1165,7 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
   const uint32_t listed = cnt <= kMaxCand ? cnt : 0u;
   // Four list slots per round: their candidate loads first, then the grouping, then all four rounds'
   // returning atomics in flight together (one wait instead of four: vmcnt retires in issue order).
-#ifndef BZR_RANK_BATCH
-#define BZR_RANK_BATCH 4
-#endif
-  constexpr int kRankBatch = BZR_RANK_BATCH;
+  constexpr int kRankBatch = 4;
   for (uint32_t j0 = 0; __any(j0 < listed); j0 += kRankBatch) {
     uint32_t b[kRankBatch], leader[kRankBatch], below[kRankBatch], base[kRankBatch];
 #pragma unroll
@@ -1364,12 +1216,7 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
 #endif
 }
 
-// Candidate search, one 64-ray wave per 64 consecutive rays.
-// BZR_TRAV_XCD (A/B knob, deal_blocks policy): 1 = XCD-contiguous ray ranges (round 1), 0 = dispatch
-// order, G > 1 = runs of G blocks per XCD.
-#ifndef BZR_TRAV_XCD
-#define BZR_TRAV_XCD 1
-#endif
+// Candidate search, one 64-ray wave per 64 consecutive rays, the blocks in XCD-contiguous ray ranges.
 // BZR_TRAV_WPE (default 8; 0 = the compiler's choice, 7 waves): amdgpu_waves_per_eu lower bound for k_traverse.
 // At 8 waves per SIMD it keeps 64 VGPRs (35 SGPRs spill into VGPR lanes, no scratch): its walk waits on memory
 // 45 % of its cycles, and the eighth wave hides more of it -- k_traverse -8 % on cfg5 (4.91 -> 4.52 ms per
@@ -1387,23 +1234,14 @@ template <int kBlk, int kAblock, bool kFast>
 __global__ __launch_bounds__(kBlk) BZR_TRAV_ATTR void k_traverse(MeshView m, const float *__restrict__ rays, uint32_t ld,
                                                          uint32_t off, const uint32_t *__restrict__ alive, uint32_t n,
                                                          Work w, unsigned long long *counters) {
-  __shared__ uint32_t stack[kBlk / 64][kTravStack];
+  __shared__ uint32_t stack[kBlk / 64][kStack];
   __shared__ float bundle[kBlk / 64][kBundleWords];  // the wave's ray bundle (bundle walk, always list)
-#if BZR_TRAV_BUNDLE
-  __shared__ uint32_t pend[kBlk / 64][BZR_TRAV_PRETEST ? 128 : 64];  // the bundle walk's queued leaf slots
+  __shared__ uint32_t pend[kBlk / 64][128];  // the bundle walk's queued leaf slots
   uint32_t *wpend = pend[threadIdx.x >> 6];
-#else
-  uint32_t *wpend = nullptr;
-#endif
-#if BZR_TRAV_BUNDLE && BZR_TRAV_PRETEST
   __shared__ uint32_t raw[kBlk / 64][128];  // leaves before the pre-test (up to two batches' worth)
   uint32_t *wraw = raw[threadIdx.x >> 6];
-#else
-  uint32_t *wraw = nullptr;
-#endif
-  const uint32_t b = deal_blocks<BZR_TRAV_XCD>(blockIdx.x, gridDim.x);
+  const uint32_t b = xcd_contiguous(blockIdx.x, gridDim.x);
   if constexpr (kAblock != 0) {
-    static_assert(!kAblock || BZR_TRAV_BUNDLE, "BZR_TRAV_ABLOCK needs the bundle walk");
     __shared__ float ubl[16];                                  // the block's union bundle (words 0..12)
     __shared__ unsigned long long akeep[kAblockMax / 64u];     // block-kept always-listed patches
     traverse_rays<kBlk, kAblock, kFast>(m, rays, ld, off, alive, n, w, counters, b * kBlk + threadIdx.x,
@@ -1496,13 +1334,11 @@ __device__ __forceinline__ void flush_follow(uint32_t *buf, uint32_t &nf, uint32
 // pair records while it computes the current one.  A dense chunk holds one patch (its lane 0 always a real
 // pair), processed with the record in scalar registers, `full` being a __restrict__ constant-address-space
 // read; the padded lanes of a bucket's last chunk (kNoPair) idle.
-// BZR_NEWTON_WPE (default 8): amdgpu_waves_per_eu lower bound for k_newton.  At 8 waves per SIMD the
+// kNewtonWpe: amdgpu_waves_per_eu lower bound for k_newton.  At 8 waves per SIMD the
 // compiler spills ~33 SGPRs to VGPR lanes and keeps 64 VGPRs; measured 2.4 % faster per frame than
 // the unconstrained 7 waves (66 VGPRs, 106 SGPRs), same output bits.
-#ifndef BZR_NEWTON_WPE
-#define BZR_NEWTON_WPE 8
-#endif
-#define BZR_NEWTON_ATTR __attribute__((amdgpu_waves_per_eu(BZR_NEWTON_WPE)))
+constexpr int kNewtonWpe = 8;
+#define BZR_NEWTON_ATTR __attribute__((amdgpu_waves_per_eu(kNewtonWpe)))
 template <bool kFast>
 __global__ __launch_bounds__(kBlock) BZR_NEWTON_ATTR void k_newton(const float *__restrict__ full,
                                                    const unsigned long long *__restrict__ total,
@@ -1516,11 +1352,8 @@ __global__ __launch_bounds__(kBlock) BZR_NEWTON_ATTR void k_newton(const float *
   const uint32_t D = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(*total >> 32));  // dense chunks
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t W = gridDim.x * kWaves;
-#if BZR_NEWTON_XCD
-  uint32_t q = xcd_contiguous(blockIdx.x, gridDim.x) * kWaves + (threadIdx.x >> 6);
-#else
+  // (chunks in dispatch order: XCD-contiguous order measured 6 % slower)
   uint32_t q = blockIdx.x * kWaves + (threadIdx.x >> 6);
-#endif
   q = __builtin_amdgcn_readfirstlane(q);
   uint2 pr = make_uint2(kNoPair, 0u);
   if (q < D) pr = pairs[q * 64u + lane];
@@ -1536,7 +1369,7 @@ __global__ __launch_bounds__(kBlock) BZR_NEWTON_ATTR void k_newton(const float *
     bool is_fol = false;
     const auto pa = uniform_patch(full, b);
     if (todo) {
-      const Hit h = patch_intersect<BZR_NEWTON_GATED != 0, kFast>(pa, s, d, false);
+      const Hit h = patch_intersect<true, kFast>(pa, s, d, false);
       if (h.what == kIntersect) record(slot, n, ray, j, b, h, b, &key[ray]);
       is_fol = h.what <= kFollow2;
       if (is_fol) reinterpret_cast<uint32_t *>(pairs)[2u * p + 1u] = b | (h.what << 30);  // the side, for k_resolve
@@ -1574,7 +1407,7 @@ __global__ __launch_bounds__(kBlock) void k_newton_lane(const float *__restrict_
       f3 s, d;
       load_ray(rays, ld, off + ray, s, d);
       const Patch pa = load_patch(full + (size_t)rec::kWords * b);
-      const Hit h = patch_intersect<BZR_NEWTON_GATED != 0, kFast>(pa, s, d, false);
+      const Hit h = patch_intersect<true, kFast>(pa, s, d, false);
       if (h.what == kIntersect) record(slot, n, ray, j, b, h, b, &key[ray]);
       is_fol = h.what <= kFollow2;
       if (is_fol) reinterpret_cast<uint32_t *>(pairs)[2u * p + 1u] = b | (h.what << 30);
@@ -1590,26 +1423,8 @@ __global__ __launch_bounds__(kBlock) void k_newton_lane(const float *__restrict_
 }
 
 template <int kMode, bool kFast>
-// BZR_FINISH_WPE / BZR_RESOLVE_WPE (A/B knobs, default 0 = the compiler's choice): amdgpu_waves_per_eu lower
-// bounds for k_finish (112 VGPRs -- the overflow rays' Newton re-evaluation -- so 4 waves per SIMD) and
-// k_resolve (120 VGPRs, 4 waves).  k_finish at 6 or 8 waves (27 / 72 VGPRs spilled) measured no faster -- it
-// is HBM-bound at ~6 TB/s either way (profiles/r04_ab_finish_split.jsonl); k_resolve spills 143 / 378.
-#ifndef BZR_FINISH_WPE
-#define BZR_FINISH_WPE 0
-#endif
-#ifndef BZR_RESOLVE_WPE
-#define BZR_RESOLVE_WPE 0
-#endif
-#if BZR_FINISH_WPE
-#define BZR_FINISH_ATTR __attribute__((amdgpu_waves_per_eu(BZR_FINISH_WPE)))
-#else
-#define BZR_FINISH_ATTR
-#endif
-#if BZR_RESOLVE_WPE
-#define BZR_RESOLVE_ATTR __attribute__((amdgpu_waves_per_eu(BZR_RESOLVE_WPE)))
-#else
-#define BZR_RESOLVE_ATTR
-#endif
+// (k_finish at 6 or 8 waves per SIMD through amdgpu_waves_per_eu measured no faster than the compiler's choice
+// -- it is HBM-bound at ~6 TB/s either way, profiles/r04_ab_finish_split.jsonl)
 // BZR_FINISH_NORAY (default 1; 0 = the round-4 k_finish): the intersect segments' k_finish reads no ray -- a
 // BezierIntersection needs none -- and the overflow rays (whose winner k_finish would evaluate again, with the ray)
 // are emitted by k_finish_ovf just before it; 24 B per ray less, one small launch more per chunk.  First measured
@@ -1623,7 +1438,7 @@ template <int kMode, bool kFast>
 #ifndef BZR_FINISH_NORAY
 #define BZR_FINISH_NORAY 1
 #endif
-__global__ __launch_bounds__(kBlock) BZR_FINISH_ATTR void k_finish(MeshView m, const float *rays, uint32_t ld, uint32_t off, uint32_t n,
+__global__ __launch_bounds__(kBlock) void k_finish(MeshView m, const float *rays, uint32_t ld, uint32_t off, uint32_t n,
                                                    Work w, Out o) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (blockIdx.x == 0 && threadIdx.x < 4) w.ctr[threadIdx.x] = 0u;  // last reader of the counters this segment
@@ -1719,7 +1534,7 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
 // blocks take (overflow ray, patch slice) items.  With no overflow rays the second loop is empty --
 // one launch per segment saved over separate kernels.
 template <bool kFast>
-__global__ __launch_bounds__(kBlock) BZR_RESOLVE_ATTR void k_resolve(MeshView m, const float *__restrict__ rays, uint32_t ld,
+__global__ __launch_bounds__(kBlock) void k_resolve(MeshView m, const float *__restrict__ rays, uint32_t ld,
                                                     uint32_t off, uint32_t n, Work w) {
   const uint32_t F = __builtin_amdgcn_readfirstlane(w.ctr[0]);
   for (uint32_t q = blockIdx.x * kBlock + threadIdx.x; q < F; q += gridDim.x * kBlock) {
@@ -1815,7 +1630,7 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_small(const uint32_t *__r
 //    the neighbour of side K is uniform too).  A retry whose neighbour is a collected leaf still to come
 //    joins that leaf's pass; one whose neighbour already ran takes the result that pass parked for it
 //    (below); only the rest take a pass of their own;
-//  - parking (BZR_TRACE_SPEC): a leaf's pass also runs, in its otherwise idle lanes, the cNone evaluation
+//  - parking: a leaf's pass also runs, in its otherwise idle lanes, the cNone evaluation
 //    for the lanes of later leaves that neighbour it -- the retry those lanes would ask for -- and parks
 //    the result in LDS (one per lane and segment; not for kModeHits, whose 12-word winner leaves no room).
 // Each lane keeps the lexicographic minimum of (t order key, scanned patch index) -- the reference's
@@ -1831,19 +1646,10 @@ struct TraceCtr {  // wave-uniform work counters (kCount)
   uint32_t shorts = 0;  // passes that skipped the last Newton normal (BZR_TRACE_SHORT)
   uint32_t rounds_odd = 0, runs_odd = 0;  // odd chain segments (a lens's back surface): passes, pairs + follows
 };
-// BZR_TRACE_PRIO (default 3; 0 = off): wave priority (s_setprio) of k_trace's BVH walk phase, back to 0
-// for the Newton passes.  The walk is a chain of dependent scalar loads with little VALU work; issuing
+// k_trace's BVH walk phase runs at wave priority 3 (s_setprio), back to 0 for the Newton passes.  The walk is a
+// chain of dependent scalar loads with little VALU work; issuing
 // it ahead of the VALU-bound passes of the CU's other waves keeps its loads in flight (cfg4 -3 %).
-#ifndef BZR_TRACE_PRIO
-#define BZR_TRACE_PRIO 3
-#endif
-#ifndef BZR_TRACE_ENTRIES
-#define BZR_TRACE_ENTRIES 16
-#endif
-#ifndef BZR_TRACE_SPEC
-#define BZR_TRACE_SPEC 1
-#endif
-// BZR_TRACE_PARK_HITS (default 1): park cNone results in the intersect kernel (kModeHits) as well: cfg5
+// The intersect kernel (kModeHits) parks cNone results as the refraction kernels do: cfg5
 // fused -7.8 % Newton passes, +3.2 % Mrays/s; cfg3 +1 % (profiles/r03_ab_cfg{5,3}_fused_parkhits.jsonl).
 // BZR_TRACE_BUNDLE (default 1): k_trace walks the tree with the wave-bundle test in batches (trace_segment)
 // instead of one node at a time with each lane's slab test (0; rim waves whose bundle is wide take that walk
@@ -1855,9 +1661,6 @@ struct TraceCtr {  // wave-uniform work counters (kCount)
 // within 1 %: the walk's VALU is what overlapping frames compete for).
 #ifndef BZR_TRACE_BUNDLE
 #define BZR_TRACE_BUNDLE 1
-#endif
-#ifndef BZR_TRACE_PARK_HITS
-#define BZR_TRACE_PARK_HITS 1
 #endif
 // BZR_TRACE_SHORT (default 1; 0 = off): a Newton pass none of whose lanes can win skips the last iteration's
 // surface normal (newton_tail's hook).  The last iteration enters with the t it returns, so each lane knows its
@@ -1877,7 +1680,7 @@ struct TraceCtr {  // wave-uniform work counters (kCount)
 #define BZR_TRACE_SHORT 1
 #endif
 static_assert(BZR_TRACE_SHORT >= 0 && BZR_TRACE_SHORT <= 2, "BZR_TRACE_SHORT: 0, 1 or 2");
-constexpr uint32_t kEntries = BZR_TRACE_ENTRIES;  // collected leaves per batch: power of two, <= 64
+constexpr uint32_t kEntries = 16;  // collected leaves per batch: power of two, <= 64
 static_assert(kEntries >= 4 && kEntries <= 64 && (kEntries & (kEntries - 1)) == 0, "kEntries");
 // Words kept per lane: the winner (all of BezierIntersection for kModeHits; what refraction reads
 // otherwise: point, cos, normal) and a parked retry result (t, point, cos, normal).
@@ -1886,7 +1689,7 @@ struct TraceWords {
   static constexpr int kHit = kMode == kModeHits ? 12 : 7;
   // kModeHits parks the barycentrics too (11 words): 6.4 KB of LDS per wave, which its 6 waves per SIMD
   // (80 VGPRs) leave room for (24 waves x 6.4 KB <= 160 KB)
-  static constexpr int kPark = !BZR_TRACE_SPEC ? 0 : (kMode != kModeHits ? 8 : (BZR_TRACE_PARK_HITS ? 11 : 0));
+  static constexpr int kPark = kMode != kModeHits ? 8 : 11;
   // traversal stack entries: the bundle walk's batches push up to 64 children at once, so the refraction
   // kernels (4.6 KB of LDS per wave at 7 waves per SIMD) take twice BZR_STACK; the intersect kernel's LDS
   // (6.5 KB per wave at 6 waves per SIMD) has no room left
@@ -2071,15 +1874,12 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
   // leaves queued (L.pend) and gate-tested one by one with every active lane's own exact planar gate.
   uint32_t npend = 0, pi = 0;  // queued leaves, next to gate-test (uniform)
   const float4 *kids = near_tier ? m.kids_near : m.kids;
-  // the walk choice, per wave-segment: a bundle whose directions spread wider than BZR_BUNDLE_SPREAD (rim
+  // the walk choice, per wave-segment: a bundle whose directions spread wider than kBundleSpread (rim
   // waves of refracted rays, incoherent batches) walks per lane instead -- its hull would reach far more
   // boxes than its rays do
   bool narrow = false;  // else every node is tested per lane (the oriented-box nodes always are)
   if (next != kNo) {
-    narrow = bundle_setup_dpp(act, s, d, L.bundle, lane) <= BZR_BUNDLE_SPREAD;
-#if BZR_BUNDLE_ALWAYS_NARROW
-    narrow = true;  // (A/B knob: no per-lane walk for wide bundles)
-#endif
+    narrow = bundle_setup_dpp(act, s, d, L.bundle, lane) <= kBundleSpread;
     if (lane == 0u) L.stack[0] = 0u;
     sp = 1;
     next = kNo;
@@ -2088,9 +1888,7 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
 #endif
   for (;;) {
     uint32_t ne = 0;  // collected leaves (uniform)
-#if BZR_TRACE_PRIO
-    __builtin_amdgcn_s_setprio(BZR_TRACE_PRIO);  // the walk is latency-bound: issue it ahead of Newton passes
-#endif
+    __builtin_amdgcn_s_setprio(3);  // the walk is latency-bound: issue it ahead of Newton passes
 #if BZR_TRACE_BUNDLE
     while (bwalk && ne < kEntries) {
       if (pi < npend) {  // a queued leaf: every active lane's planar gate
@@ -2261,9 +2059,7 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
       ++scan;
     }
     // the collected leaves' passes, in order
-#if BZR_TRACE_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     if (kOrder && ne >= 2u) {
       // near side first: lane e < ne ranks entry e among the batch's keys (stable: ties keep their order) and
       // moves its index and ballot to that place; the join and park logic below sees the permuted list only
@@ -2386,39 +2182,18 @@ struct TraceJob {
   const float *weight_in;          // kModePower [n]: the power the rays start with, or null -> 1
 };
 
-// BZR_TRACE_WPE (default 6): amdgpu_waves_per_eu lower bound for k_trace.  The chain kernel needs 72 VGPRs
+// kTraceWpe: amdgpu_waves_per_eu lower bound for k_trace.  The chain kernel needs 72 VGPRs
 // (7 waves per SIMD) by itself; the intersect kernel (kModeHits: a 12-word winner) would take 82 (5 waves)
 // since the always list's bundle code, and the bound holds it at 80 (6 waves, as before) without scratch.
-#ifndef BZR_TRACE_WPE
-#define BZR_TRACE_WPE 6
-#endif
-// BZR_TRACE_WPE_CHAIN (default BZR_TRACE_WPE): the same bound for the refraction kernels (kModeRefract,
-// kModeStage), which hold 72 VGPRs = 7 waves per SIMD by themselves (7 here trades SGPRs for spills).
-#ifndef BZR_TRACE_WPE_CHAIN
-#define BZR_TRACE_WPE_CHAIN BZR_TRACE_WPE
-#endif
-#if BZR_TRACE_WPE
-#define BZR_TRACE_ATTR __attribute__((amdgpu_waves_per_eu(kMode == kModeHits ? BZR_TRACE_WPE : BZR_TRACE_WPE_CHAIN)))
-#else
-#define BZR_TRACE_ATTR
-#endif
-// Threads per k_trace block (BZR_TRACE_BLOCK): its waves share nothing but the CU, so one-wave blocks let
+constexpr int kTraceWpe = 6;
+#define BZR_TRACE_ATTR __attribute__((amdgpu_waves_per_eu(kTraceWpe)))
+// Threads per k_trace block: its waves share nothing but the CU, so one-wave blocks let
 // a finished wave be replaced at once (waves run 1-4 segments; 64 vs 256: cfg4 -3 %, cfg5 -7 %).
-#ifndef BZR_TRACE_BLOCK
-#define BZR_TRACE_BLOCK 64
-#endif
-constexpr int kTraceBlock = BZR_TRACE_BLOCK, kTraceWaves = kTraceBlock / 64;
-// Which 64-ray tile block b takes (BZR_TRACE_XCD): 0 = the dispatch order itself (XCD x gets every 8th
-// tile), 1 = xcd_contiguous (each XCD one contiguous range of the image), G > 1 = runs of G tiles dealt
-// round-robin to the XCDs.  0 is the default: a lens covers the middle of the image, so contiguous
-// ranges give the middle XCDs ~2x the work of the outer ones, and a lens's records fit every XCD's L2
-// anyway (cfg4: 6.26 ms with 1, 5.85 with 16, 5.67 with 0; cfg5 fused within 1 %).
-#ifndef BZR_TRACE_XCD
-#define BZR_TRACE_XCD 0
-#endif
-__device__ __forceinline__ uint32_t trace_tile(uint32_t b, uint32_t nblocks) {
-  return deal_blocks<BZR_TRACE_XCD>(b, nblocks);
-}
+// Block b takes 64-ray tile b, the dispatch order itself (XCD x gets every 8th tile), unless the cost order
+// below names another: a lens covers the middle of the image, so XCD-contiguous ranges give the middle XCDs
+// ~2x the work of the outer ones, and a lens's records fit every XCD's L2 anyway (cfg4: 6.26 ms contiguous,
+// 5.67 in dispatch order; cfg5 fused within 1 %).
+constexpr int kTraceBlock = 64, kTraceWaves = kTraceBlock / 64;
 // Cost-ordered dispatch (BZR_TRACE_SCHED, default on).  A frame's waves differ up to ~6x
 // in duration (rim waves meet many patches), and the hardware dispatches blocks in index order as slots free
 // up -- greedy list scheduling.  One frame alone therefore ends on whichever long waves were dispatched late.
@@ -2498,7 +2273,7 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
   __shared__ TraceLds<kMode> lds[kTraceWaves];
   const uint32_t lane = threadIdx.x & 63u;
   TraceLds<kMode> &L = lds[threadIdx.x >> 6];
-  const uint32_t tile = job.order ? job.order[blockIdx.x] : trace_tile(blockIdx.x, gridDim.x);
+  const uint32_t tile = job.order ? job.order[blockIdx.x] : uint32_t(blockIdx.x);
   const uint32_t i = tile * kTraceBlock + threadIdx.x;
   const unsigned long long t_start = (job.wave_clock || job.cost) ? __builtin_amdgcn_s_memtime() : 0ull;
   const unsigned long long r_start = (job.wave_clock && job.wave_real) ? __builtin_amdgcn_s_memrealtime() : 0ull;
@@ -2623,46 +2398,19 @@ __global__ __launch_bounds__(kBlock) void k_refract_scan(MeshView m, const float
   out_status[i] = st;
 }
 
+// The chain by the reference's brute-force scan.  kPower: with the rays' power (kModePower's brute-force form, the
+// A/B reference of the two culled paths); weight_in may be null (1) and may alias out_weight.
+template <bool kPower>
 __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const float *__restrict__ rays, uint32_t n,
                                                        float *__restrict__ out_rays, uint32_t *__restrict__ out_status,
-                                                       uint32_t *__restrict__ out_segments) {
+                                                       uint32_t *__restrict__ out_segments, const float *weight_in,
+                                                       float *out_weight) {
   uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   f3 s, d;
   load_ray(rays, n, i, s, d);
-  uint32_t st = BZR_RR_NONE, seg = 0;
-  bool alive = true;
-  for (uint32_t l = 0; l < lenses.count && alive; ++l) {
-    for (uint32_t j = 0; j < 2u && alive; ++j) {
-      f3 os, od;
-      uint32_t patch;
-      ++seg;
-      Hit h = mesh_intersect_scan(lenses.lens[l], s, d, patch);
-      st = refract_hit(h, lenses.lens[l].ri, s, d, j == 0 ? BZR_RR_INSIDE : BZR_RR_OUTSIDE, os, od);
-      if (st == BZR_RR_NONE) {
-        alive = false;
-      } else {
-        s = os;
-        d = od;
-      }
-    }
-  }
-  store_ray(out_rays, n, i, s, d);
-  out_status[i] = st;
-  if (out_segments) out_segments[i] = seg;
-}
-
-// k_chain_scan with the rays' power (kModePower's brute-force form, the A/B reference of the two culled paths):
-// weight_in may be null (1) and may alias out_weight.
-__global__ __launch_bounds__(kBlock) void k_chain_scan_power(LensSet lenses, const float *__restrict__ rays, uint32_t n,
-                                                             float *__restrict__ out_rays, uint32_t *__restrict__ out_status,
-                                                             uint32_t *__restrict__ out_segments, const float *weight_in,
-                                                             float *out_weight) {
-  uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  f3 s, d;
-  load_ray(rays, n, i, s, d);
-  float wgt = weight_in ? weight_in[i] : 1.0f;
+  float wgt = 1.0f;
+  if constexpr (kPower) wgt = weight_in ? weight_in[i] : 1.0f;
   uint32_t st = BZR_RR_NONE, seg = 0;
   bool alive = true;
   for (uint32_t l = 0; l < lenses.count && alive; ++l) {
@@ -2672,20 +2420,20 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan_power(LensSet lenses, con
       ++seg;
       Hit h = mesh_intersect_scan(lenses.lens[l], s, d, patch);
       float gain = 1.0f;
-      st = refract_hit_t<true>(h, lenses.lens[l].ri, s, d, j == 0 ? BZR_RR_INSIDE : BZR_RR_OUTSIDE, os, od, gain);
+      st = refract_hit_t<kPower>(h, lenses.lens[l].ri, s, d, j == 0 ? BZR_RR_INSIDE : BZR_RR_OUTSIDE, os, od, gain);
       if (st == BZR_RR_NONE) {
         alive = false;
       } else {
         s = os;
         d = od;
-        wgt = wgt * gain;
+        if constexpr (kPower) wgt = wgt * gain;
       }
     }
   }
   store_ray(out_rays, n, i, s, d);
   out_status[i] = st;
   if (out_segments) out_segments[i] = seg;
-  out_weight[i] = wgt;
+  if constexpr (kPower) out_weight[i] = wgt;
 }
 
 template <bool kFast>
@@ -2867,39 +2615,18 @@ uint32_t resident_blocks(bzr_ctx *ctx, K kernel) {
   return blocks;
 }
 
-// Grid of the persistent staged kernels (k_newton, k_resolve) in units of the device's resident capacity
-// (A/B knobs, environment BZR_NEWTON_GRIDX / BZR_RESOLVE_GRIDX, 1..64, read once per process).  A grid
+// Grid of the persistent staged kernel k_newton in units of the device's resident capacity.  A grid
 // of exactly the resident capacity holds every wave slot until the kernel ends, so another frame's kernels (frames
 // in flight, their own streams) cannot start beside it; k x capacity ends in k generations of blocks, between
 // which the dispatcher also takes the other streams' blocks.
-uint32_t env_scale(const char *name, uint32_t dflt = 1u) {
-  const char *e = std::getenv(name);
-  if (!e || !*e) return dflt;
-  const long v = std::strtol(e, nullptr, 10);
-  return (uint32_t)(v < 1 ? 1 : v > 64 ? 64 : v);
-}
-// k_newton: 2 x the resident capacity on meshes of at least 2^17 patches, else 1 x (BZR_NEWTON_GRIDX overrides).
+// 2 x the resident capacity on meshes of at least 2^17 patches, else 1 x.
 // Measured (profiles/r06_ab_gridx_cfg5.jsonl, same bits): cfg5 (301 056 patches, 8 M-ray chunks) k_newton 4.33 ->
 // 4.15 ms per lone frame and +0.8 to +1.5 % at bench level on three boxes, 4 x / 8 x / 16 x lose (every wave's
 // follow-list flush is an atomic on one counter); cfg3 (28 800 patches) k_newton 0.174 -> 0.205 ms lone, -1 to -2 %
 // at bench level.
 constexpr uint32_t kNewtonGrid2Patches = 1u << 17;
-uint32_t newton_gridx(uint32_t nb) {
-  static const uint32_t s = env_scale("BZR_NEWTON_GRIDX", 0u);
-  return s ? s : nb >= kNewtonGrid2Patches ? 2u : 1u;
-}
-// k_resolve's block cap: BZR_RESOLVE_BLOCKS (absolute, 64..65536) if set, else 1024 x BZR_RESOLVE_GRIDX
-uint32_t resolve_blocks() {
-  static const uint32_t s = [] {
-    const char *e = std::getenv("BZR_RESOLVE_BLOCKS");
-    if (e && *e) {
-      const long v = std::strtol(e, nullptr, 10);
-      return (uint32_t)(v < 64 ? 64 : v > 65536 ? 65536 : v);
-    }
-    return 1024u * env_scale("BZR_RESOLVE_GRIDX");
-  }();
-  return s;
-}
+uint32_t newton_gridx(uint32_t nb) { return nb >= kNewtonGrid2Patches ? 2u : 1u; }
+constexpr uint32_t kResolveBlocks = 1024u;  // k_resolve's block cap for the follow retries
 
 // Workspace of the culled path for chunks of up to `chunk` rays over meshes of up to `nb` patches.
 using SplitIt = hipcub::TransformInputIterator<unsigned long long, BucketSplit, const uint32_t *>;
@@ -2935,17 +2662,14 @@ bzr_status ensure_work(bzr_ctx *ctx, uint32_t chunk, uint32_t nb, Work &w) {
 }
 
 // Rays per chunk of the staged path, whose workspace is ~2.7 KB per ray + 0.5 KB per patch: at most
-// 2^BZR_CHUNK_LOG2 (8M rays, ~23 GB) and at most what a quarter of the device's free memory holds (at the
+// kChunk (2^23 = 8M rays, ~23 GB) and at most what a quarter of the device's free memory holds (at the
 // context's first staged call), with the
 // batch split into equal chunks (rounded to whole waves).  Measured on cfg5 (67M rays): 1M-ray chunks
 // 28.3 ms per frame, 4M 21.4, 8M 20.0, 16M 20.0 -- small chunks leave the kernels short of waves.
-#ifndef BZR_CHUNK_LOG2
-#define BZR_CHUNK_LOG2 23
-#endif
-constexpr uint32_t kChunk = 1u << BZR_CHUNK_LOG2;
+constexpr uint32_t kChunkLog2 = 23, kChunk = 1u << kChunkLog2;
 // what ensure_work takes per ray: per list slot cand, rank, slot, pair and fol; per ray count, key and ovf
 constexpr size_t kWorkBytesPerRay = (size_t)kMaxCand * (4 + 4 + 48 + 8 + 4) + (4 + 8 + 4);
-static_assert(BZR_CHUNK_LOG2 <= 26, "pair records hold a chunk's ray index in 26 bits");
+static_assert(kChunkLog2 <= 26, "pair records hold a chunk's ray index in 26 bits");
 static_assert((uint64_t)kMaxCand * kChunk + 64ull * (kStagedPatchLimit + 1) < (1ull << 32),
               "32-bit pair indices");
 static_assert(kMaxCand <= 64, "winner keys hold a list slot in 6 bits");
@@ -3013,8 +2737,8 @@ bzr_status run_culled(bzr_ctx *ctx, const MeshView &mv, const float *rays, uint3
          mv.full, w.offs + hn, w.pairs, rays, ld, off, n, w.slot, w.key, w.fol, w.ctr);
   {  // follow retries + overflow rays (whose keys the Newton stage left untouched: their lists are empty)
     const uint64_t items = (uint64_t)n * ((nb + kOvfSlice - 1) / kOvfSlice);
-    const uint32_t grid = std::max(std::min<uint32_t>(grid_for(n / 8 + 1), resolve_blocks()),
-                                   (uint32_t)std::min<uint64_t>(items, BZR_OVERFLOW_BLOCKS));
+    const uint32_t grid = std::max(std::min<uint32_t>(grid_for(n / 8 + 1), kResolveBlocks),
+                                   (uint32_t)std::min<uint64_t>(items, kOverflowBlocks));
     launch(ctx, BZR_KERNEL_FOLLOW, k_resolve<kFast>, dim3(std::max<uint32_t>(grid, 1u)), mv, rays, ld, off, n, w);
   }
   if (ctx->counting && ctx->counters)  // before k_finish, which clears the counters
@@ -3307,7 +3031,7 @@ extern "C" bzr_status bzr_mesh_create(bzr_ctx *ctx, const void *patches, uint32_
     return k;
   };
   const std::vector<float4> kids = kids_of(bvh), kids_near = kids_of(bvh_near);
-  // two levels per node (k_traverse's bundle walk, BZR_TRAV_WIDE; three with 2): slot 4 c + g of node i is
+  // two levels per node (k_traverse's bundle walk): slot 4 c + g of node i is
   // grandchild g of its child c when that child is an axis-aligned inner node, else (a leaf, an oriented-box
   // node) slot 4 c is the child itself and 4 c + 1..3 are empty.  A walk over these slots skips the children's own boxes,
   // so it reaches a superset of the leaves the 4-wide walk reaches (every leaf still takes its exact gate).
@@ -3318,27 +3042,26 @@ extern "C" bzr_status bzr_mesh_create(bzr_ctx *ctx, const void *patches, uint32_
     std::memcpy(&empty, &e, 4);
     std::vector<float4> k(t.nodes4.size() * 2 * S, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
     for (size_t s = 0; s < k.size(); s += 2) k[s].w = empty;
-    // slots [base, base + span) of node i's record: child c of nd, expanded while span > 1 and it is an
-    // axis-aligned inner node, else in the range's first slot
-    std::function<void(size_t, uint32_t, uint32_t, const bzr_host::Bvh4Node &, int)> fill =
-        [&](size_t i, uint32_t base, uint32_t span, const bzr_host::Bvh4Node &nd, int c) {
-          const uint32_t ch = nd.child[c];
-          const bool inner = ch != bzr_host::kEmptyChild && !(ch & (bzr_host::kLeafFlag | bzr_host::kObbFlag));
-          if (!inner || span == 1u) {
-            float ref;
-            std::memcpy(&ref, &nd.child[c], 4);
-            k[2 * (S * i + base)] = make_float4(nd.lo[0][c], nd.lo[1][c], nd.lo[2][c], ref);
-            k[2 * (S * i + base) + 1] = make_float4(nd.hi[0][c], nd.hi[1][c], nd.hi[2][c], 0.0f);
-            return;
-          }
-          for (int g = 0; g < 4; ++g) fill(i, base + g * (span / 4u), span / 4u, t.nodes4[ch], g);
-        };
+    auto put = [&](size_t slot, const bzr_host::Bvh4Node &nd, int c) {  // child c of nd into a slot
+      float ref;
+      std::memcpy(&ref, &nd.child[c], 4);
+      k[2 * slot] = make_float4(nd.lo[0][c], nd.lo[1][c], nd.lo[2][c], ref);
+      k[2 * slot + 1] = make_float4(nd.hi[0][c], nd.hi[1][c], nd.hi[2][c], 0.0f);
+    };
     for (size_t i = 0; i < t.nodes4.size(); ++i)
-      for (int c = 0; c < 4; ++c) fill(i, c * (S / 4u), S / 4u, t.nodes4[i], c);
+      for (int c = 0; c < 4; ++c) {
+        const bzr_host::Bvh4Node &nd = t.nodes4[i];
+        const uint32_t ch = nd.child[c];
+        const bool inner = ch != bzr_host::kEmptyChild && !(ch & (bzr_host::kLeafFlag | bzr_host::kObbFlag));
+        if (!inner) {
+          put(S * i + 4 * c, nd, c);
+          continue;
+        }
+        for (int g = 0; g < 4; ++g) put(S * i + 4 * c + g, t.nodes4[ch], g);
+      }
     return k;
   };
-  const std::vector<float4> wide = BZR_TRAV_WIDE ? wide_of(bvh) : std::vector<float4>(),
-                            wide_near = BZR_TRAV_WIDE ? wide_of(bvh_near) : std::vector<float4>();
+  const std::vector<float4> wide = wide_of(bvh), wide_near = wide_of(bvh_near);
   // the always list: the same patches in both tiers (whether a gate region is proven does not depend on
   // the tier's origin radius)
   if (bvh.always != bvh_near.always) return set_error(BZR_ERR_INVALID_ARGUMENT, "BVH tiers disagree on the always list");
@@ -3675,10 +3398,7 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     d_rays = r;
   }
   if (use_scan(flags)) {
-    if constexpr (kPower)
-      launch(ctx, BZR_KERNEL_CHAIN_SCAN, k_chain_scan_power, dim3(grid_for(n)), set, d_rays, n, d_out, d_st, d_seg, d_win, d_w);
-    else
-      launch(ctx, BZR_KERNEL_CHAIN_SCAN, k_chain_scan, dim3(grid_for(n)), set, d_rays, n, d_out, d_st, d_seg);
+    launch(ctx, BZR_KERNEL_CHAIN_SCAN, k_chain_scan<kPower>, dim3(grid_for(n)), set, d_rays, n, d_out, d_st, d_seg, d_win, d_w);
     BZR_HIP(hipGetLastError());
   } else if (!use_staged(flags, n, max_patches(set))) {
     TraceJob job{};
@@ -3915,72 +3635,6 @@ extern "C" bzr_status bzr_mesh_interpolate(bzr_ctx *ctx, const bzr_mesh *mesh, i
 
 // ------------------------------------------------------------ illumination
 namespace {
-// Rays first .. first+n-1 of the emitter into rays [6][ld].  With `status`: rays that cannot meet the
-// first lens's bounding sphere (over its proven gate regions) and pass none of its always-listed patches'
-// planar gates start as NONE (culled, never traced), the others INSIDE (the chain's first refraction
-// expects to enter the lens); stats[EMITTED], stats[CULLED] count them.
-__global__ __launch_bounds__(kBlock) void k_emit(bzr_emitter em, BeltTable bt, uint64_t first, uint32_t n, uint32_t ld,
-                                                 float *__restrict__ rays, uint32_t *__restrict__ patch,
-                                                 uint32_t *__restrict__ status, uint32_t *__restrict__ segments,
-                                                 float4 sphere, const float4 *__restrict__ always, uint32_t n_always,
-                                                 unsigned long long *__restrict__ stats) {
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  bool culled = false;
-  f3 o = mk(0.0f, 0.0f, 0.0f), d = o;
-  if (i < n) {
-    uint32_t p;
-    emit_ray(em, bt, first + i, o, d, p);
-    store_ray(rays, ld, i, o, d);
-    if (patch) patch[i] = p;
-    if (status) {
-      const float sp[4] = {sphere.x, sphere.y, sphere.z, sphere.w};
-      culled = !may_hit_sphere(o, d, sp);
-    }
-  }
-  if (status) {
-    // the always list has no box inside the sphere: a ray outside it is kept if any of those gates passes
-    for (uint32_t k = 0; k < n_always && __any(culled); ++k) {
-      uint32_t b;
-      if (always_gate(always, k, culled, o, d, b)) culled = false;
-    }
-    if (i < n) {
-      status[i] = culled ? BZR_RR_NONE : BZR_RR_INSIDE;
-      if (segments) segments[i] = 0u;
-    }
-  }
-  if (stats) {
-    const unsigned long long made = __ballot(i < n), cut = __ballot(culled);
-    if ((threadIdx.x & 63u) == 0u) {
-      if (made) atomicAdd(&stats[BZR_ILLUM_EMITTED], (unsigned long long)__popcll(made));
-      if (cut) atomicAdd(&stats[BZR_ILLUM_CULLED], (unsigned long long)__popcll(cut));
-    }
-  }
-}
-
-// Rays that left the last lens (status OUTSIDE) meet the target plane: one count per landed ray.
-__global__ __launch_bounds__(kBlock) void k_land(bzr_target tg, float4 plane, float cell_u, float cell_v,
-                                                 const float *__restrict__ rays, uint32_t ld, uint32_t n,
-                                                 const uint32_t *__restrict__ status, uint32_t *__restrict__ hist,
-                                                 unsigned long long *__restrict__ stats) {
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  bool exited = false, landed = false;
-  if (i < n && status[i] == BZR_RR_OUTSIDE) {
-    exited = true;
-    f3 s, d;
-    load_ray(rays, ld, i, s, d);
-    const int32_t cell = target_cell(tg, mk(plane.x, plane.y, plane.z), plane.w, cell_u, cell_v, s, d);
-    if (cell >= 0) {
-      landed = true;
-      atomicAdd(&hist[cell], 1u);
-    }
-  }
-  const unsigned long long ex = __ballot(exited), la = __ballot(landed);
-  if ((threadIdx.x & 63u) == 0u) {
-    if (ex) atomicAdd(&stats[BZR_ILLUM_EXITED], (unsigned long long)__popcll(ex));
-    if (la) atomicAdd(&stats[BZR_ILLUM_LANDED], (unsigned long long)__popcll(la));
-  }
-}
-
 // Ray power as unsigned 64-bit fixed point with 32 fraction bits: q(w) = trunc(w x 2^32) for w in [0, 1] (the
 // product is exact in binary32, the conversion truncates).  Integer sums do not depend on the order of arrival.
 __device__ __forceinline__ unsigned long long power_q32(float w) {
@@ -3992,15 +3646,20 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
   return v;
 }
 
-// k_emit for bzr_illuminate_power: the batch's rays with their status and segments as k_emit writes them, plus each
-// ray's initial power w0 (1, or with `lambert` the direction's x component: cos to the emitter's +x normal) and
-// power[EMITTED], power[CULLED] = the sums of q(w0), reduced over the wave first.
-__global__ __launch_bounds__(kBlock) void k_emit_power(bzr_emitter em, BeltTable bt, uint64_t first, uint32_t n, uint32_t ld,
-                                                       float *__restrict__ rays, uint32_t *__restrict__ status,
-                                                       uint32_t *__restrict__ segments, float *__restrict__ weight,
-                                                       uint32_t lambert, float4 sphere, const float4 *__restrict__ always,
-                                                       uint32_t n_always, unsigned long long *__restrict__ stats,
-                                                       unsigned long long *__restrict__ power) {
+// Rays first .. first+n-1 of the emitter into rays [6][ld].  With `status`: rays that cannot meet the
+// first lens's bounding sphere (over its proven gate regions) and pass none of its always-listed patches'
+// planar gates start as NONE (culled, never traced), the others INSIDE (the chain's first refraction
+// expects to enter the lens); stats[EMITTED], stats[CULLED] count them.
+// kPower (bzr_illuminate_power: status, segments and stats are given, patch is not read): plus each ray's initial
+// power w0 (1, or with `lambert` the direction's x component: cos to the emitter's +x normal) and power[EMITTED],
+// power[CULLED] = the sums of q(w0), reduced over the wave first.
+template <bool kPower>
+__global__ __launch_bounds__(kBlock) void k_emit(bzr_emitter em, BeltTable bt, uint64_t first, uint32_t n, uint32_t ld,
+                                                 float *__restrict__ rays, uint32_t *__restrict__ patch,
+                                                 uint32_t *__restrict__ status, uint32_t *__restrict__ segments,
+                                                 float4 sphere, const float4 *__restrict__ always, uint32_t n_always,
+                                                 unsigned long long *__restrict__ stats, float *__restrict__ weight,
+                                                 uint32_t lambert, unsigned long long *__restrict__ power) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   bool culled = false;
   f3 o = mk(0.0f, 0.0f, 0.0f), d = o;
@@ -4008,62 +3667,83 @@ __global__ __launch_bounds__(kBlock) void k_emit_power(bzr_emitter em, BeltTable
     uint32_t p;
     emit_ray(em, bt, first + i, o, d, p);
     store_ray(rays, ld, i, o, d);
-    const float sp[4] = {sphere.x, sphere.y, sphere.z, sphere.w};
-    culled = !may_hit_sphere(o, d, sp);
+    if (!kPower && patch) patch[i] = p;
+    if (kPower || status) {
+      const float sp[4] = {sphere.x, sphere.y, sphere.z, sphere.w};
+      culled = !may_hit_sphere(o, d, sp);
+    }
   }
-  for (uint32_t k = 0; k < n_always && __any(culled); ++k) {
-    uint32_t b;
-    if (always_gate(always, k, culled, o, d, b)) culled = false;
+  float w0 = 1.0f;
+  if (kPower || status) {
+    // the always list has no box inside the sphere: a ray outside it is kept if any of those gates passes
+    for (uint32_t k = 0; k < n_always && __any(culled); ++k) {
+      uint32_t b;
+      if (always_gate(always, k, culled, o, d, b)) culled = false;
+    }
+    if constexpr (kPower) w0 = lambert ? d.x : 1.0f;
+    if (i < n) {
+      status[i] = culled ? BZR_RR_NONE : BZR_RR_INSIDE;
+      if (kPower || segments) segments[i] = 0u;
+      if constexpr (kPower) weight[i] = w0;
+    }
   }
-  const float w0 = lambert ? d.x : 1.0f;
-  if (i < n) {
-    status[i] = culled ? BZR_RR_NONE : BZR_RR_INSIDE;
-    segments[i] = 0u;
-    weight[i] = w0;
-  }
-  const unsigned long long made = __ballot(i < n), cut = __ballot(culled);
-  const unsigned long long q = i < n ? power_q32(w0) : 0ull;
-  const unsigned long long qe = wave_sum_u64(q), qc = wave_sum_u64(culled ? q : 0ull);
-  if ((threadIdx.x & 63u) == 0u) {
-    if (made) atomicAdd(&stats[BZR_ILLUM_EMITTED], (unsigned long long)__popcll(made));
-    if (cut) atomicAdd(&stats[BZR_ILLUM_CULLED], (unsigned long long)__popcll(cut));
-    if (qe) atomicAdd(&power[BZR_ILLUM_EMITTED], qe);
-    if (qc) atomicAdd(&power[BZR_ILLUM_CULLED], qc);
+  if (kPower || stats) {
+    const unsigned long long made = __ballot(i < n), cut = __ballot(culled);
+    unsigned long long qe = 0ull, qc = 0ull;
+    if constexpr (kPower) {
+      const unsigned long long q = i < n ? power_q32(w0) : 0ull;
+      qe = wave_sum_u64(q);
+      qc = wave_sum_u64(culled ? q : 0ull);
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+      if (made) atomicAdd(&stats[BZR_ILLUM_EMITTED], (unsigned long long)__popcll(made));
+      if (cut) atomicAdd(&stats[BZR_ILLUM_CULLED], (unsigned long long)__popcll(cut));
+      if constexpr (kPower) {
+        if (qe) atomicAdd(&power[BZR_ILLUM_EMITTED], qe);
+        if (qc) atomicAdd(&power[BZR_ILLUM_CULLED], qc);
+      }
+    }
   }
 }
 
-// k_land for bzr_illuminate_power: each landed ray adds q(its weight) to its cell of flux (64-bit atomic) and, with
-// `hist`, one count as k_land does; stats as k_land's, power[EXITED], power[LANDED] = the sums of q(w), one atomic
-// per wave and counter.
-__global__ __launch_bounds__(kBlock) void k_land_power(bzr_target tg, float4 plane, float cell_u, float cell_v,
-                                                       const float *__restrict__ rays, uint32_t ld, uint32_t n,
-                                                       const uint32_t *__restrict__ status,
-                                                       const float *__restrict__ weight,
-                                                       unsigned long long *__restrict__ flux, uint32_t *__restrict__ hist,
-                                                       unsigned long long *__restrict__ stats,
-                                                       unsigned long long *__restrict__ power) {
+// Rays that left the last lens (status OUTSIDE) meet the target plane: one count per landed ray.
+// kPower (bzr_illuminate_power): each landed ray also adds q(its weight) to its cell of flux (64-bit atomic), the
+// count only with `hist`; power[EXITED], power[LANDED] = the sums of q(w), one atomic per wave and counter.
+template <bool kPower>
+__global__ __launch_bounds__(kBlock) void k_land(bzr_target tg, float4 plane, float cell_u, float cell_v,
+                                                 const float *__restrict__ rays, uint32_t ld, uint32_t n,
+                                                 const uint32_t *__restrict__ status, uint32_t *__restrict__ hist,
+                                                 unsigned long long *__restrict__ stats, const float *__restrict__ weight,
+                                                 unsigned long long *__restrict__ flux,
+                                                 unsigned long long *__restrict__ power) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   bool exited = false, landed = false;
   unsigned long long q = 0ull;
   if (i < n && status[i] == BZR_RR_OUTSIDE) {
     exited = true;
-    q = power_q32(weight[i]);
+    if constexpr (kPower) q = power_q32(weight[i]);
     f3 s, d;
     load_ray(rays, ld, i, s, d);
     const int32_t cell = target_cell(tg, mk(plane.x, plane.y, plane.z), plane.w, cell_u, cell_v, s, d);
     if (cell >= 0) {
       landed = true;
-      atomicAdd(&flux[cell], q);
-      if (hist) atomicAdd(&hist[cell], 1u);
+      if constexpr (kPower) atomicAdd(&flux[cell], q);
+      if (!kPower || hist) atomicAdd(&hist[cell], 1u);
     }
   }
   const unsigned long long ex = __ballot(exited), la = __ballot(landed);
-  const unsigned long long qx = wave_sum_u64(q), ql = wave_sum_u64(landed ? q : 0ull);
+  unsigned long long qx = 0ull, ql = 0ull;
+  if constexpr (kPower) {
+    qx = wave_sum_u64(q);
+    ql = wave_sum_u64(landed ? q : 0ull);
+  }
   if ((threadIdx.x & 63u) == 0u) {
     if (ex) atomicAdd(&stats[BZR_ILLUM_EXITED], (unsigned long long)__popcll(ex));
     if (la) atomicAdd(&stats[BZR_ILLUM_LANDED], (unsigned long long)__popcll(la));
-    if (qx) atomicAdd(&power[BZR_ILLUM_EXITED], qx);
-    if (ql) atomicAdd(&power[BZR_ILLUM_LANDED], ql);
+    if constexpr (kPower) {
+      if (qx) atomicAdd(&power[BZR_ILLUM_EXITED], qx);
+      if (ql) atomicAdd(&power[BZR_ILLUM_LANDED], ql);
+    }
   }
 }
 
@@ -4135,9 +3815,9 @@ extern "C" bzr_status bzr_emit(bzr_ctx *ctx, const bzr_emitter *em, uint64_t fir
   if (bzr_status s = upload_belts(ctx, em, st, bt, cos_lo, count, firsts)) return s;
   float *d_rays = host ? st.take<float>((size_t)n * 6) : rays_soa;
   uint32_t *d_patch = host ? (patch_index ? st.take<uint32_t>(n) : nullptr) : patch_index;
-  hipLaunchKernelGGL(k_emit, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, *em, bt, first, n, n, d_rays, d_patch,
-                     (uint32_t *)nullptr, (uint32_t *)nullptr, make_float4(0.0f, 0.0f, 0.0f, 0.0f),
-                     (const float4 *)nullptr, 0u, (unsigned long long *)nullptr);
+  hipLaunchKernelGGL(k_emit<false>, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, *em, bt, first, n, n, d_rays, d_patch,
+                     (uint32_t *)nullptr, (uint32_t *)nullptr, make_float4(0.0f, 0.0f, 0.0f, 0.0f), (const float4 *)nullptr,
+                     0u, (unsigned long long *)nullptr, (float *)nullptr, 0u, (unsigned long long *)nullptr);
   BZR_HIP(hipGetLastError());
   if (host) {
     BZR_HIP(hipMemcpyAsync(rays_soa, d_rays, rb, hipMemcpyDeviceToHost, ctx->stream));
@@ -4228,12 +3908,13 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   for (uint64_t first = 0; first < total_rays; first += B) {
     const uint32_t m = (uint32_t)std::min<uint64_t>(B, total_rays - first);
     if (with_power)
-      hipLaunchKernelGGL(k_emit_power, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays, d_st,
-                         d_seg, d_w, rad->emission == BZR_EMISSION_LAMBERT ? 1u : 0u, sphere, set.lens[0].always,
-                         set.lens[0].n_always, d_stats, d_power);
+      hipLaunchKernelGGL(k_emit<true>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays,
+                         (uint32_t *)nullptr, d_st, d_seg, sphere, set.lens[0].always, set.lens[0].n_always, d_stats, d_w,
+                         rad->emission == BZR_EMISSION_LAMBERT ? 1u : 0u, d_power);
     else
-      hipLaunchKernelGGL(k_emit, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays,
-                         (uint32_t *)nullptr, d_st, d_seg, sphere, set.lens[0].always, set.lens[0].n_always, d_stats);
+      hipLaunchKernelGGL(k_emit<false>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays,
+                         (uint32_t *)nullptr, d_st, d_seg, sphere, set.lens[0].always, set.lens[0].n_always, d_stats,
+                         (float *)nullptr, 0u, (unsigned long long *)nullptr);
     if (!staged) {  // the chain in place over the batch; culled rays (status NONE) are skipped
       TraceJob job{};
       job.rays = d_rays;
@@ -4263,12 +3944,13 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
         }
     }
     if (with_power)
-      hipLaunchKernelGGL(k_land_power, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg,
-                         make_float4(pn.x, pn.y, pn.z, pc), cell_u, cell_v, d_rays, B, m, d_st, d_w, d_flux, d_hist, d_stats,
+      hipLaunchKernelGGL(k_land<true>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg,
+                         make_float4(pn.x, pn.y, pn.z, pc), cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats, d_w, d_flux,
                          d_power);
     else
-      hipLaunchKernelGGL(k_land, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg, make_float4(pn.x, pn.y, pn.z, pc),
-                         cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats);
+      hipLaunchKernelGGL(k_land<false>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg,
+                         make_float4(pn.x, pn.y, pn.z, pc), cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats,
+                         (const float *)nullptr, (unsigned long long *)nullptr, (unsigned long long *)nullptr);
     BZR_HIP(hipGetLastError());
   }
   unsigned long long hs[4];

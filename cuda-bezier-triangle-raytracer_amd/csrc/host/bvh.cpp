@@ -904,7 +904,7 @@ extern "C" int32_t bzr_debug_gate_boxes(const void *patches, uint32_t n, uint32_
 
 namespace {
 float safe_inv_h(float x) { return 1.0f / (std::fabs(x) < 1e-20f ? std::copysign(1e-20f, x) : x); }
-// same operation order as the device slab() in trace.hip (BZR_SLAB_FMA: fma(lo, inv, -s*inv))
+// same operation order as the device slab() in trace.hip (fma(lo, inv, -s*inv))
 bool slab_h(const float lo[3], const float hi[3], const float s[3], const float inv[3]) {
   float a[3], b[3];
   for (int k = 0; k < 3; ++k) {
@@ -1086,7 +1086,7 @@ bool bundle_box_h(const BundleH &b, const float lo[3], const float hi[3]) {
 }
 }  // namespace
 
-// Host mirror of the device planar gate (trace.hip planar_gate, BZR_GATE_FLAT; built with -ffp-contract=off
+// Host mirror of the device planar gate (trace.hip planar_gate, the branch-free form; built with -ffp-contract=off
 // like the device code, so the same float operations in the same order): q = the 16-float planar record.
 bool planar_gate_h(const float q[16], const float s[3], const float d[3]) {
   const float cs = d[0] * q[0] + (d[1] * q[1] + d[2] * q[2]);

@@ -61,7 +61,7 @@ int32_t bzr_debug_div_heights(void *ctx, const float *a, uint32_t n, float *out)
  * Asynchronous on the context's stream. */
 int32_t bzr_debug_fast_unit(void *ctx, const float *a, uint32_t n, float *out);
 /* The staged path's chunking rule as pure host arithmetic (no device): *cap = the rays-per-chunk cap for a device with
- * `free_bytes` free (whole waves, at least 64, at most 2^BZR_CHUNK_LOG2 = 8 M; a quarter of the free memory at the
+ * `free_bytes` free (whole waves, at least 64, at most 2^23 = 8 M; a quarter of the free memory at the
  * workspace's bytes per ray; free_bytes == 0 means unknown and gives the ceiling), *chunk = the chunk length for a
  * batch of n rays under that cap (n itself when it fits, else equal pieces rounded up to whole waves, never above
  * the cap; the last chunk is ragged). */

@@ -4,11 +4,11 @@ on the cfg2 lens, emitter just behind it (inside the lens's bounding sphere, so 
 every ray is traced).  Prints one JSON line: emitted rays / s and the landed fraction.
 
 usage: bench_illum.py [total_rays] [--power]
---power times bzr_illuminate_power (Lambert emitter, Fresnel surfaces: k_emit_power -> chain with weights ->
-k_land_power, 64-bit flux cells) beside bzr_illuminate on the same rays, alternating, and prints one more JSON line
+--power times bzr_illuminate_power (Lambert emitter, Fresnel surfaces: k_emit<true> -> chain with weights ->
+k_land<true>, 64-bit flux cells) beside bzr_illuminate on the same rays, alternating, and prints one more JSON line
 with both; the chain kernels' share comes from the context's event timing in a separate pass, the rest of a call is
-its emit and landing kernels and the host's part.  Per-kernel durations of k_land / k_land_power: run this under a
-kernel-trace profiler."""
+its emit and landing kernels and the host's part.  Per-kernel durations of k_land<false> / k_land<true>: run this
+under a kernel-trace profiler."""
 import json
 import statistics
 import sys

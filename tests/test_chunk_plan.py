@@ -10,7 +10,7 @@ import ctypes
 import pytest
 
 WAVE = 64
-CEILING = 1 << 23                                       # trace.hip kChunk (BZR_CHUNK_LOG2 = 23)
+CEILING = 1 << 23                                       # trace.hip kChunk (kChunkLog2 = 23)
 MAX_CAND = 40                                           # trace.hip kMaxCand
 RAY_BYTES = MAX_CAND * (4 + 4 + 48 + 8 + 4) + (4 + 8 + 4)  # trace.hip kWorkBytesPerRay: per list slot cand, rank, slot,
 #                                                         pair, fol; per ray count, key, ovf

@@ -26,7 +26,7 @@ from bzr_amd.configs import CONFIGS, build_lens, grid_rays
 
 pytestmark = pytest.mark.gpu
 
-MAX_CAND = 40     # trace.hip kMaxCand (BZR_MAX_CAND's default)
+MAX_CAND = 40     # trace.hip kMaxCand
 N_BASE = 126      # patches of cfg1's lens, Lens("ellipsoid", 3, 7)
 COPIES, PART = 20, 63
 SHELLS = 24
