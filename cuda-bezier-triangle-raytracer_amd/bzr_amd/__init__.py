@@ -77,6 +77,8 @@ _SIGS = {
     "bzr_refract": [_P, _P, _F, _P, _P, _U32, _U32, _P, _P, _U32],
     "bzr_trace_chain": [_P, _P, _P, _U32, _P, _U32, _P, _P, _P, _U32],
     "bzr_trace_chain_power": [_P, _P, _P, _U32, _P, _P, _U32, _P, _P, _P, _P, _U32],
+    "bzr_trace_chain_spectral": [_P, _P, _P, _U32, _U32, _P, _P, _P, _U32, _P, _P, _P, _P, _U32],
+    "bzr_dispersion_index": [_I32, _P, _U32, _P, _U32, _P],
     "bzr_trace_tiled": [_P, _U32, _P, _P, _U32, _P, _U32, _U32, _P, _P, _P, _U32],
     "bzr_tiled_create": [_P, _U32, _U32, _U32, _U32, _I32, ctypes.POINTER(_P)],
     "bzr_tiled_destroy": [_P],
@@ -92,6 +94,7 @@ _SIGS = {
     "bzr_emit": [_P, _P, ctypes.c_uint64, _U32, _P, _P, _U32],
     "bzr_illuminate": [_P, _P, _P, _U32, _P, ctypes.c_uint64, _P, _P, _P, _U32],
     "bzr_illuminate_power": [_P, _P, _P, _U32, _P, ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _U32],
+    "bzr_illuminate_spectral": [_P, _P, _P, _U32, _U32, _P, ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _U32],
     "bzr_mesh_bounding_sphere": [_P, _P],
     "bzr_trimesh_create": [ctypes.POINTER(_P)],
     "bzr_trimesh_destroy": [_P],
@@ -123,7 +126,8 @@ _SIGS = {
     "bzr_debug_fresnel": [_P, _P, _U32, _P],
 }
 # entry points added without an ABI bump: an explicitly chosen earlier build (BZR_LIBRARY) may lack them
-_ADDED = ("bzr_trace_chain_power", "bzr_illuminate_power")
+_ADDED = ("bzr_trace_chain_power", "bzr_illuminate_power", "bzr_trace_chain_spectral", "bzr_illuminate_spectral",
+          "bzr_dispersion_index")
 _RET = {"bzr_last_error": ctypes.c_char_p, "bzr_abi_version": _I32}
 
 _lib = None
@@ -193,7 +197,7 @@ class _Buf:
             if not x.is_contiguous():
                 raise BzrError("tensor arguments must be contiguous")
             want = {np.float32: "torch.float32", np.uint32: "torch.uint32", np.int32: "torch.int32",
-                    np.uint64: "torch.uint64"}
+                    np.uint64: "torch.uint64", np.uint8: "torch.uint8"}
             same_bits = {np.uint32: "torch.int32", np.uint64: "torch.int64"}
             if str(x.dtype) not in (want[dtype], same_bits.get(dtype, want[dtype])):
                 raise BzrError(f"tensor dtype {x.dtype} where {want[dtype]} is expected")
@@ -444,6 +448,53 @@ def trace_chain_power(ctx: Context, lenses, ri, rays, weight=None, out_rays=None
     return out_rays, out_weight, out_status, out_segments
 
 
+MAX_CHANNELS = 64  # BZR_MAX_CHANNELS
+DISPERSION_CAUCHY, DISPERSION_SELLMEIER = 0, 1  # BZR_DISPERSION_*
+
+
+def _ri_table(ri_table, nl):
+    """The index table as C-contiguous float32 [nlens, nchan] -> (array, nchan)."""
+    t = np.ascontiguousarray(ri_table, dtype=np.float32)
+    if t.ndim != 2 or t.shape[0] != nl:
+        raise BzrError(f"ri_table must be [nlens = {nl}, nchan], got {t.shape}")
+    return t, int(t.shape[1])
+
+
+def trace_chain_spectral(ctx: Context, lenses, ri_table, rays, channel, weight=None, out_rays=None, out_weight=None,
+                         out_status=None, out_segments=None, mode=MODE_PARITY):
+    """trace_chain_power with one index per ray and lens -> (rays, weight [n], status [n], segments [n]).  ri_table
+    [nlens, nchan] float32 (host) is lens l's index for channel c, channel [n] uint8 the rays' channels (host or
+    device as the rays); ray i refracts at lens l with ri_table[l, channel[i]].  A ray whose channel is nchan or more
+    comes back with status NONE, one segment, its ray and weight unchanged (bzr.h bzr_trace_chain_spectral)."""
+    n = _n_of(rays, mode)
+    nl = len(lenses)
+    handles = (_P * nl)(*[m.handle for m in lenses])
+    table, nchan = _ri_table(ri_table, nl)
+    out_rays = _empty_like(rays, 6, np.float32, mode) if out_rays is None else out_rays
+    out_weight = _empty_like(rays, 0, np.float32, mode) if out_weight is None else out_weight
+    out_status = _empty_like(rays, 0, np.uint32, mode) if out_status is None else out_status
+    out_segments = _empty_like(rays, 0, np.uint32, mode) if out_segments is None else out_segments
+    r, c, wi = _Buf(rays, np.float32), _Buf(channel, np.uint8), _Buf(weight, np.float32)
+    o, w = _Buf(out_rays, np.float32, True), _Buf(out_weight, np.float32, True)
+    s, g = _Buf(out_status, np.uint32, True), _Buf(out_segments, np.uint32, True)
+    res = _residency(r, c, o, w, s, g, wi)
+    with _stream_for(ctx, res):
+        _check(lib().bzr_trace_chain_spectral(ctx.handle, ctypes.cast(handles, _P), table.ctypes.data if table.size else None,
+                                              nl, nchan, r.ptr, c.ptr, wi.ptr, n, o.ptr, w.ptr, s.ptr, g.ptr, res | mode))
+    return out_rays, out_weight, out_status, out_segments
+
+
+def dispersion_index(model: int, coeff, wavelength_um) -> np.ndarray:
+    """Refractive index at each wavelength (micrometres) from a dispersion formula, float32: DISPERSION_CAUCHY
+    (coeff A, B[, C]: n = A + B / l^2 + C / l^4) or DISPERSION_SELLMEIER (coeff B1, C1, B2, C2, ...:
+    n^2 = 1 + sum B_k l^2 / (l^2 - C_k)).  Host only (bzr.h bzr_dispersion_index)."""
+    c = np.ascontiguousarray(coeff, np.float64).ravel()
+    lam = np.ascontiguousarray(wavelength_um, np.float64)
+    out = np.empty(lam.shape, np.float32)
+    _check(lib().bzr_dispersion_index(int(model), c.ctypes.data, c.size, lam.ctypes.data, lam.size, out.ctypes.data))
+    return out
+
+
 PACK_IMAGE, PACK_RAYS, PACK_COMPACT = 0, 1, 2  # BZR_PACK_*
 PACK_LAYOUTS = {"image": PACK_IMAGE, "rays": PACK_RAYS, "compact": PACK_COMPACT}
 
@@ -684,6 +735,39 @@ def illuminate_power(ctx: Context, lenses, ri, em: Emitter, total_rays: int, tar
                                           ctypes.byref(target), ctypes.byref(rad), f.ptr, h.ptr, stats, power, res | mode))
     return (flux, hist, dict(zip(ILLUM_STATS, [int(x) for x in stats])),
             dict(zip(ILLUM_STATS, [int(x) for x in power])))
+
+
+def illuminate_spectral(ctx: Context, lenses, ri_table, em: Emitter, total_rays: int, target: Target,
+                        emission=EMISSION_LAMBERT, surface=SURFACE_FRESNEL, flux=None, hist=None, mode=MODE_PARITY):
+    """illuminate_power per spectral channel: emitter ray i is in channel i mod nchan and refracts at lens l with
+    ri_table[l, i mod nchan] (ri_table [nlens, nchan] float32, host).  Returns (flux uint64 [nchan, bins_v, bins_u] in
+    32.32 fixed point, accumulated into `flux` if given; hist uint32 of the same shape, accumulated into `hist` if given;
+    stats: a list of nchan dicts; power: a list of nchan dicts, in the same fixed point).  No source spectrum is
+    taken: scale channel c's map by the source's power in that channel."""
+    nl = len(lenses)
+    handles = (_P * nl)(*[m.handle for m in lenses])
+    table, nchan = _ri_table(ri_table, nl)
+    shape = (nchan, target.bins_v, target.bins_u)
+    if flux is None:
+        flux = np.zeros(shape, np.uint64)
+    if hist is None:
+        if _is_tensor(flux):
+            import torch
+
+            hist = torch.zeros(shape, dtype=torch.int32, device=flux.device)
+        else:
+            hist = np.zeros(shape, np.uint32)
+    f, h = _Buf(flux, np.uint64, True), _Buf(hist, np.uint32, True)
+    rad = Radiometry(int(emission), int(surface))
+    rows = max(nchan, 1)
+    stats, power = (ctypes.c_uint64 * (4 * rows))(), (ctypes.c_uint64 * (4 * rows))()
+    res = _residency(f, h)
+    with _stream_for(ctx, res):
+        _check(lib().bzr_illuminate_spectral(ctx.handle, handles, table.ctypes.data if table.size else None, nl, nchan,
+                                             ctypes.byref(em), int(total_rays), ctypes.byref(target), ctypes.byref(rad),
+                                             f.ptr, h.ptr, stats, power, res | mode))
+    return (flux, hist, [dict(zip(ILLUM_STATS, [int(x) for x in stats[4 * c:4 * c + 4]])) for c in range(nchan)],
+            [dict(zip(ILLUM_STATS, [int(x) for x in power[4 * c:4 * c + 4]])) for c in range(nchan)])
 
 
 def flux_to_float(flux) -> np.ndarray:

@@ -47,6 +47,11 @@ struct bzr_ctx {
   uint32_t sched_waves = 0;  // waves of the call whose order is ready (0: none)
   uint32_t sched_calls = 0;  // calls since the order was first built for this size (rebuilt every BZR_TRACE_SCHED_REFRESH)
   uint64_t sched_key = 0;    // the order's call: lens set and mode (a different call of the same size rebuilds it)
+  // kModeSpectral's index table [nlens][nchan] on the device, with the host copy of what it holds.  A buffer of
+  // its own, not part of `scratch`: a device-pointer call returns with its kernels still queued, and the table
+  // must outlive them whatever the next call stages (trace.hip upload_ri_table).
+  float *ri_table = nullptr;
+  std::vector<float> ri_table_host;
 };
 
 // BZR_RAYS_AOS (frame_pack.hip): n rays between the reference's [n][6] records and the kernels' [6][n] rows,

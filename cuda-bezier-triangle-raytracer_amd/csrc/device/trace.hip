@@ -434,8 +434,12 @@ constexpr uint32_t kSlotWords = 12;  // t, point, cos, bary, normal, source patc
 // kModePower: kModeStage plus the ray's power -- one weight per ray, multiplied by the Fresnel transmittance
 // (patch_math_body.inc fresnel_t) of each successful refraction.  A mode of its own, not a run-time branch of
 // kModeStage: the instantiations of the other three modes compile to the code they had.
-enum OutMode { kModeHits = 0, kModeRefract = 1, kModeStage = 2, kModePower = 3 };
-constexpr bool is_stage(int mode) { return mode == kModeStage || mode == kModePower; }
+// kModeSpectral: kModePower with the refractive index read per lane -- ray i carries channel[i], lens l refracts it
+// with ri_table[l][channel[i]].  A channel at or above nchan ends the ray at its first surface like a miss (NONE,
+// one segment, ray and weight as they came).  Again a mode of its own: the other four compile to the code they had.
+enum OutMode { kModeHits = 0, kModeRefract = 1, kModeStage = 2, kModePower = 3, kModeSpectral = 4 };
+constexpr bool is_stage(int mode) { return mode == kModeStage || mode == kModePower || mode == kModeSpectral; }
+constexpr bool has_power(int mode) { return mode == kModePower || mode == kModeSpectral; }
 struct Out {
   float *hits;               // kModeHits: SoA [13][ld]
   float *rays;               // kModeRefract: output rays; kModeStage: rays in flight (in place)
@@ -448,6 +452,10 @@ struct Out {
                              // from the caller's rays and its ray / status / segments are all written here
   float *weight;             // kModePower: the weights in flight [ld] (as rays: in place)
   const float *weight_in;    // kModePower, first stage: the caller's weights, or null -> 1
+  const uint8_t *channel;    // kModeSpectral: the rays' channels [ld] (indexed like status and weight)
+  const float *ri_row;       // kModeSpectral: this lens's row of the index table [nchan] (device memory)
+  uint32_t nchan;
+  uint32_t lossless;         // kModeSpectral: the weights stay as they are (the gain counts as 1)
 };
 
 template <int kMode>
@@ -457,7 +465,18 @@ __device__ __forceinline__ void emit(const Out &o, uint32_t ld, uint32_t gi, f3 
   } else {
     f3 os, od;
     float gain = 1.0f;
-    uint32_t st = refract_hit_t<kMode == kModePower>(h, o.ri, s, d, o.expected ? o.expected[gi] : o.expected_all, os, od, gain);
+    float ri = o.ri;
+    bool in_table = true;
+    if constexpr (kMode == kModeSpectral) {
+      const uint32_t ch = o.channel[gi];
+      in_table = ch < o.nchan;
+      ri = o.ri_row[in_table ? ch : 0u];
+    }
+    uint32_t st = refract_hit_t<has_power(kMode)>(h, ri, s, d, o.expected ? o.expected[gi] : o.expected_all, os, od, gain);
+    if constexpr (kMode == kModeSpectral) {
+      if (!in_table) st = BZR_RR_NONE;
+      if (o.lossless) gain = 1.0f;
+    }
     if (kMode == kModeRefract || st != BZR_RR_NONE || (is_stage(kMode) && o.first)) {
       if (st == BZR_RR_NONE) {
         os = s;
@@ -467,7 +486,7 @@ __device__ __forceinline__ void emit(const Out &o, uint32_t ld, uint32_t gi, f3 
     }
     o.status[gi] = st;
     if (is_stage(kMode) && o.segments) o.segments[gi] = o.first ? 1u : o.segments[gi] + 1u;
-    if constexpr (kMode == kModePower) {  // the first stage writes every ray's weight, later ones the refracted rays'
+    if constexpr (has_power(kMode)) {  // the first stage writes every ray's weight, later ones the refracted rays'
       if (o.first || st != BZR_RR_NONE) {
         float w = o.first ? (o.weight_in ? o.weight_in[gi] : 1.0f) : o.weight[gi];
         if (st != BZR_RR_NONE) w = w * gain;
@@ -2162,7 +2181,8 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
 // Trace job of one launch.  Modes: kModeHits (one BezierMesh::intersect per ray -> hits), kModeRefract
 // (one BezierLens::refract -> ray', status), kModeStage (the chain over lenses [0, count): refract(INSIDE)
 // then refract(OUTSIDE) per lens, a NONE ends the ray -- reference/test.cpp:376-401), kModePower (kModeStage with
-// the rays' power: wherever kModeStage is named below, kModePower's fields are the same).
+// the rays' power: wherever kModeStage is named below, kModePower's fields are the same), kModeSpectral (kModePower
+// with each lens's index taken per ray from ri_table by the ray's channel).
 struct TraceJob {
   const float *rays;         // input [6][n]
   float *hits;               // kModeHits [13][n]
@@ -2180,6 +2200,10 @@ struct TraceJob {
   uint32_t *cost;                  // optional: per tile, its cost bin (sched_bin of the block's duration)
   float *weight;                   // kModePower [n]: the traced rays' power (may alias weight_in)
   const float *weight_in;          // kModePower [n]: the power the rays start with, or null -> 1
+  const uint8_t *channel;          // kModeSpectral [n]: the rays' channels
+  const float *ri_table;           // kModeSpectral [count][nchan]: lens l's index for channel c (device memory)
+  uint32_t nchan;
+  uint32_t lossless;               // kModeSpectral: the weights stay as they are (the gain counts as 1)
 };
 
 // kTraceWpe: amdgpu_waves_per_eu lower bound for k_trace.  The chain kernel needs 72 VGPRs
@@ -2303,7 +2327,7 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
     // The caller's weight is first needed by the first refraction.  Loaded here, its register is not live across
     // the first (longest) walk; loaded with the ray, the non-counting kernels came out with 36 B of scratch
     // reserved (never accessed), here with none.
-    if constexpr (kMode == kModePower)
+    if constexpr (has_power(kMode))
       if (k == 0u && i < n && job.weight_in) wgt = job.weight_in[i];
     Hit h = no_hit();
     uint32_t patch = 0xFFFFFFFFu;
@@ -2315,7 +2339,20 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
                                                       : ((k & 1u) ? uint32_t(BZR_RR_OUTSIDE) : uint32_t(BZR_RR_INSIDE));
       f3 os, od;
       float gain = 1.0f;
-      const uint32_t r = refract_hit_t<kMode == kModePower>(h, m.ri, s, d, expected, os, od, gain);
+      float ri = m.ri;
+      bool in_table = true;
+      // kModeSpectral: the lane's channel is read again from the row behind each segment's passes (a byte, cached
+      // since the first segment), so no register holds it across the walks (DESIGN (a), "Spectral channels")
+      if constexpr (kMode == kModeSpectral) {
+        const uint32_t ch = i < n ? job.channel[i] : 0u;
+        in_table = ch < job.nchan;
+        ri = job.ri_table[(k >> 1) * job.nchan + (in_table ? ch : 0u)];
+      }
+      uint32_t r = refract_hit_t<has_power(kMode)>(h, ri, s, d, expected, os, od, gain);
+      if constexpr (kMode == kModeSpectral) {
+        if (!in_table) r = BZR_RR_NONE;
+        if (job.lossless) gain = 1.0f;
+      }
       if (alive) {
         ++seg;
         st = r;
@@ -2323,7 +2360,7 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
         else {
           s = os;
           d = od;
-          if constexpr (kMode == kModePower) wgt = wgt * gain;
+          if constexpr (has_power(kMode)) wgt = wgt * gain;
         }
       }
     }
@@ -2332,7 +2369,7 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
     store_ray(job.out_rays, job.ld, i, s, d);
     job.status[i] = st;
     if (is_stage(kMode) && job.segments) job.segments[i] = seg;
-    if constexpr (kMode == kModePower) job.weight[i] = wgt;
+    if constexpr (has_power(kMode)) job.weight[i] = wgt;
   }
   if (job.cost && threadIdx.x == 0u) job.cost[tile] = sched_bin(__builtin_amdgcn_s_memtime() - t_start);
   if (job.wave_clock && lane == 0u) {  // the wave's tile (ray index / 64): start tick and duration
@@ -2398,19 +2435,29 @@ __global__ __launch_bounds__(kBlock) void k_refract_scan(MeshView m, const float
   out_status[i] = st;
 }
 
-// The chain by the reference's brute-force scan.  kPower: with the rays' power (kModePower's brute-force form, the
-// A/B reference of the two culled paths); weight_in may be null (1) and may alias out_weight.
-template <bool kPower>
+// The chain by the reference's brute-force scan.  kScan 1: with the rays' power (kModePower's brute-force form, the
+// A/B reference of the two culled paths); weight_in may be null (1) and may alias out_weight.  kScan 2: kModeSpectral's
+// form, the index from ri_table[l][channel[i]].  (An int, not an enum: instantiations 0 and 1 keep their names.)
+template <int kScan>
 __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const float *__restrict__ rays, uint32_t n,
                                                        float *__restrict__ out_rays, uint32_t *__restrict__ out_status,
                                                        uint32_t *__restrict__ out_segments, const float *weight_in,
-                                                       float *out_weight) {
+                                                       float *out_weight, const uint8_t *__restrict__ channel,
+                                                       const float *__restrict__ ri_table, uint32_t nchan) {
+  constexpr bool kPower = kScan != 0, kSpectral = kScan == 2;
   uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   f3 s, d;
   load_ray(rays, n, i, s, d);
   float wgt = 1.0f;
   if constexpr (kPower) wgt = weight_in ? weight_in[i] : 1.0f;
+  uint32_t ch = 0u;
+  bool in_table = true;
+  if constexpr (kSpectral) {
+    ch = channel[i];
+    in_table = ch < nchan;
+    if (!in_table) ch = 0u;
+  }
   uint32_t st = BZR_RR_NONE, seg = 0;
   bool alive = true;
   for (uint32_t l = 0; l < lenses.count && alive; ++l) {
@@ -2420,7 +2467,11 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
       ++seg;
       Hit h = mesh_intersect_scan(lenses.lens[l], s, d, patch);
       float gain = 1.0f;
-      st = refract_hit_t<kPower>(h, lenses.lens[l].ri, s, d, j == 0 ? BZR_RR_INSIDE : BZR_RR_OUTSIDE, os, od, gain);
+      float ri = lenses.lens[l].ri;
+      if constexpr (kSpectral) ri = ri_table[l * nchan + ch];
+      st = refract_hit_t<kPower>(h, ri, s, d, j == 0 ? BZR_RR_INSIDE : BZR_RR_OUTSIDE, os, od, gain);
+      if constexpr (kSpectral)
+        if (!in_table) st = BZR_RR_NONE;
       if (st == BZR_RR_NONE) {
         alive = false;
       } else {
@@ -2817,6 +2868,28 @@ bzr_status run_fused(bzr_ctx *ctx, const LensSet &set, const TraceJob &job, uint
   return BZR_OK;
 }
 
+// kModeSpectral's index table into the context's device copy.  The copy is rewritten only when the table differs
+// from what it holds, and then only after everything queued on the stream has finished (kernels of an earlier
+// device-pointer call may still read the old one); the copy itself is synchronous, so the caller's table is not
+// read after the call returns.  A frame loop with one table therefore uploads it once.
+constexpr uint32_t kMaxChannels = BZR_MAX_CHANNELS;
+bzr_status upload_ri_table(bzr_ctx *ctx, const float *table, uint32_t nlens, uint32_t nchan) {
+  const size_t count = (size_t)nlens * nchan;
+  if (!ctx->ri_table) BZR_HIP(hipMalloc(&ctx->ri_table, (size_t)kMaxLenses * kMaxChannels * sizeof(float)));
+  if (ctx->ri_table_host.size() == count && std::memcmp(ctx->ri_table_host.data(), table, count * sizeof(float)) == 0)
+    return BZR_OK;
+  BZR_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->ri_table_host.clear();
+  BZR_HIP(hipMemcpy(ctx->ri_table, table, count * sizeof(float), hipMemcpyHostToDevice));
+  ctx->ri_table_host.assign(table, table + count);
+  return BZR_OK;
+}
+bzr_status check_channels(const float *ri_table, uint32_t nchan) {
+  if (nchan == 0 || nchan > kMaxChannels) return set_error(BZR_ERR_INVALID_ARGUMENT, "nchan must be 1..64");
+  if (!ri_table) return set_error(BZR_ERR_INVALID_ARGUMENT, "null ri_table");
+  return BZR_OK;
+}
+
 uint32_t max_patches(const LensSet &set) {
   uint32_t nb = 0;
   for (uint32_t l = 0; l < set.count; ++l) nb = std::max(nb, set.lens[l].n);
@@ -2942,6 +3015,7 @@ extern "C" bzr_status bzr_ctx_destroy(bzr_ctx *ctx) {
   if (ctx->counters) (void)hipFree(ctx->counters);
   if (ctx->pack) (void)hipFree(ctx->pack);
   if (ctx->sched) (void)hipFree(ctx->sched);
+  if (ctx->ri_table) (void)hipFree(ctx->ri_table);
   (void)hipStreamDestroy(ctx->own);
   delete ctx;
   return BZR_OK;
@@ -3348,21 +3422,28 @@ extern "C" bzr_status bzr_refract(bzr_ctx *ctx, const bzr_mesh *mesh, float ri, 
 }
 
 // bzr_trace_chain (kModeStage) and bzr_trace_chain_power (kModePower: + weight_in, may be null, and out_weight,
-// plain [n] rows in either ray layout).
+// plain [n] rows in either ray layout); bzr_trace_chain_spectral (kModeSpectral: kModePower with `ri` the index
+// table [nlens][nchan] and `channel` one byte per ray, a plain [n] row, host or device memory as the rays).
 template <int kMode>
 static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
                               const float *rays, const float *weight_in, uint32_t n, float *out_rays, float *out_weight,
-                              uint32_t *out_status, uint32_t *out_segments, uint32_t flags) {
-  constexpr bool kPower = kMode == kModePower;
+                              uint32_t *out_status, uint32_t *out_segments, uint32_t flags,
+                              const uint8_t *channel = nullptr, uint32_t nchan = 0) {
+  constexpr bool kPower = has_power(kMode), kSpectral = kMode == kModeSpectral;
   if (bzr_status s = check_flags(flags, true)) return s;
   if (!ctx) return set_error(BZR_ERR_INVALID_ARGUMENT, "null context");
   if (nlens == 0 || nlens > kMaxLenses) return set_error(BZR_ERR_INVALID_ARGUMENT, "nlens must be 1..8");
+  if (kSpectral) {
+    if (bzr_status s = check_channels(ri, nchan)) return s;
+    if (!channel) return set_error(BZR_ERR_INVALID_ARGUMENT, "null channel row");
+    if (!out_weight) return set_error(BZR_ERR_INVALID_ARGUMENT, "null out_weight");
+  }
   if (!lenses || !ri) return set_error(BZR_ERR_INVALID_ARGUMENT, "null lens list");
   LensSet set{};
   set.count = nlens;
   for (uint32_t l = 0; l < nlens; ++l) {
     if (bzr_status s = check_ctx_mesh(ctx, lenses[l])) return s;
-    set.lens[l] = view_of(lenses[l], ri[l]);
+    set.lens[l] = view_of(lenses[l], kSpectral ? 1.0f : ri[l]);
   }
   if (n == 0) return BZR_OK;
   if (!rays || !out_rays || !out_status || (kPower && !out_weight)) return set_error(BZR_ERR_INVALID_ARGUMENT, "null buffer");
@@ -3373,13 +3454,16 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
   uint32_t *d_st = out_status, *d_seg = out_segments;
   const float *d_win = weight_in;
   float *d_w = out_weight;
+  const uint8_t *d_ch = channel;
   const bool host = !(flags & BZR_DEVICE_PTRS), aos = (flags & BZR_RAYS_AOS) != 0;
+  if (kSpectral)
+    if (bzr_status s = upload_ri_table(ctx, ri, nlens, nchan)) return s;
   float *tmp = nullptr;  // host + AoS: the records on the device, in and out
   if (host || aos) {
     size_t rb = (size_t)n * 24, ib = (size_t)n * 4;
     if (bzr_status s = ensure_buffer(ctx->scratch, ctx->scratch_bytes,
                                      2 * round256(rb) + (host ? (kPower ? 3 : 2) * round256(ib) : 0) +
-                                         (host && aos ? round256(rb) : 0)))
+                                         (host && aos ? round256(rb) : 0) + (host && kSpectral ? round256(n) : 0)))
       return s;
     Staging st{static_cast<char *>(ctx->scratch)};
     float *r = st.take<float>((size_t)n * 6);
@@ -3392,13 +3476,19 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
         if (weight_in) BZR_HIP(hipMemcpyAsync(d_w, weight_in, ib, hipMemcpyHostToDevice, ctx->stream));
         d_win = weight_in ? d_w : nullptr;
       }
+      if (kSpectral) {
+        uint8_t *c = st.take<uint8_t>(n);
+        BZR_HIP(hipMemcpyAsync(c, channel, n, hipMemcpyHostToDevice, ctx->stream));
+        d_ch = c;
+      }
     }
     if (host && aos) tmp = st.take<float>((size_t)n * 6);
     if (bzr_status s = rays_in(ctx, rays, r, n, host, aos, tmp)) return s;
     d_rays = r;
   }
   if (use_scan(flags)) {
-    launch(ctx, BZR_KERNEL_CHAIN_SCAN, k_chain_scan<kPower>, dim3(grid_for(n)), set, d_rays, n, d_out, d_st, d_seg, d_win, d_w);
+    launch(ctx, BZR_KERNEL_CHAIN_SCAN, k_chain_scan<kSpectral ? 2 : (kPower ? 1 : 0)>, dim3(grid_for(n)), set, d_rays, n, d_out,
+           d_st, d_seg, d_win, d_w, d_ch, (const float *)ctx->ri_table, nchan);
     BZR_HIP(hipGetLastError());
   } else if (!use_staged(flags, n, max_patches(set))) {
     TraceJob job{};
@@ -3409,6 +3499,9 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     job.n = job.ld = n;
     job.weight = d_w;
     job.weight_in = d_win;
+    job.channel = d_ch;
+    job.ri_table = ctx->ri_table;
+    job.nchan = nchan;
     if (bzr_status s = run_fused<kMode>(ctx, set, job, flags)) return s;
   } else {
     // stage by stage: out_rays holds the rays in flight, out_status != NONE marks them alive
@@ -3432,6 +3525,9 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
           o.first = (l == 0 && j == 0) ? 1u : 0u;
           o.weight = d_w;
           o.weight_in = d_win;
+          o.channel = d_ch;
+          o.ri_row = kSpectral ? ctx->ri_table + (size_t)l * nchan : nullptr;
+          o.nchan = nchan;
           if (bzr_status s = run_segment<kMode>(use_fast(flags), ctx, set.lens[l], o.first ? d_rays : d_out, n, off,
                                                      m, o.first ? nullptr : d_st, o, w))
             return s;
@@ -3463,6 +3559,14 @@ extern "C" bzr_status bzr_trace_chain_power(bzr_ctx *ctx, const bzr_mesh *const 
                                             uint32_t flags) {
   return trace_chain<kModePower>(ctx, lenses, ri, nlens, rays, weight_in, n, out_rays, out_weight, out_status,
                                  out_segments, flags);
+}
+
+extern "C" bzr_status bzr_trace_chain_spectral(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                               uint32_t nlens, uint32_t nchan, const float *rays, const uint8_t *channel,
+                                               const float *weight_in, uint32_t n, float *out_rays, float *out_weight,
+                                               uint32_t *out_status, uint32_t *out_segments, uint32_t flags) {
+  return trace_chain<kModeSpectral>(ctx, lenses, ri_table, nlens, rays, weight_in, n, out_rays, out_weight, out_status,
+                                    out_segments, flags, channel, nchan);
 }
 
 // ------------------------------------------------------------ test hook: normalized()
@@ -3646,6 +3750,29 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
   return v;
 }
 
+// Per-channel form of the two kernels' wave reductions.  The lanes of a wave hold mixed channels, so the wave loops
+// over the channels present among its `valid` lanes (the lowest such lane names the next one); per channel, the
+// lanes of that channel reduce two counts (`a`, `b`: ballots) and the two sums of q over them, and lane 0 adds the
+// four to the channel's row: ctr[4 c], ctr[4 c + 1], sum[4 c], sum[4 c + 1].  One atomic per wave, channel and
+// counter; the loop's trip count is wave-uniform.
+__device__ __forceinline__ void channel_rows(bool valid, uint32_t ch, bool a, bool b, unsigned long long q,
+                                             unsigned long long *__restrict__ ctr, unsigned long long *__restrict__ sum) {
+  unsigned long long todo = __ballot(valid);
+  while (todo) {
+    const uint32_t c = __shfl(ch, (int)__ffsll((long long)todo) - 1, 64);
+    const bool mine = valid && ch == c;
+    const unsigned long long na = __ballot(mine && a), nb = __ballot(mine && b);
+    const unsigned long long qa = wave_sum_u64(mine && a ? q : 0ull), qb = wave_sum_u64(mine && b ? q : 0ull);
+    if ((threadIdx.x & 63u) == 0u) {
+      if (na) atomicAdd(&ctr[4u * c], (unsigned long long)__popcll(na));
+      if (nb) atomicAdd(&ctr[4u * c + 1u], (unsigned long long)__popcll(nb));
+      if (qa) atomicAdd(&sum[4u * c], qa);
+      if (qb) atomicAdd(&sum[4u * c + 1u], qb);
+    }
+    todo &= ~__ballot(mine);
+  }
+}
+
 // Rays first .. first+n-1 of the emitter into rays [6][ld].  With `status`: rays that cannot meet the
 // first lens's bounding sphere (over its proven gate regions) and pass none of its always-listed patches'
 // planar gates start as NONE (culled, never traced), the others INSIDE (the chain's first refraction
@@ -3653,13 +3780,18 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 // kPower (bzr_illuminate_power: status, segments and stats are given, patch is not read): plus each ray's initial
 // power w0 (1, or with `lambert` the direction's x component: cos to the emitter's +x normal) and power[EMITTED],
 // power[CULLED] = the sums of q(w0), reduced over the wave first.
-template <bool kPower>
+// kIllum 2 (bzr_illuminate_spectral): kIllum 1 with ray first + i in channel (first + i) mod nchan, written to
+// `channel`; stats and power are [nchan][4], each lane's share goes to its channel's row (channel_rows below).
+// (kIllum is an int, not an enum: instantiations 0 and 1 keep the names they had as <false> and <true>.)
+template <int kIllum>
 __global__ __launch_bounds__(kBlock) void k_emit(bzr_emitter em, BeltTable bt, uint64_t first, uint32_t n, uint32_t ld,
                                                  float *__restrict__ rays, uint32_t *__restrict__ patch,
                                                  uint32_t *__restrict__ status, uint32_t *__restrict__ segments,
                                                  float4 sphere, const float4 *__restrict__ always, uint32_t n_always,
                                                  unsigned long long *__restrict__ stats, float *__restrict__ weight,
-                                                 uint32_t lambert, unsigned long long *__restrict__ power) {
+                                                 uint32_t lambert, unsigned long long *__restrict__ power,
+                                                 uint8_t *__restrict__ channel, uint32_t nchan) {
+  constexpr bool kPower = kIllum != 0, kSpectral = kIllum == 2;
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   bool culled = false;
   f3 o = mk(0.0f, 0.0f, 0.0f), d = o;
@@ -3687,7 +3819,12 @@ __global__ __launch_bounds__(kBlock) void k_emit(bzr_emitter em, BeltTable bt, u
       if constexpr (kPower) weight[i] = w0;
     }
   }
-  if (kPower || stats) {
+  if constexpr (kSpectral) {
+    const uint32_t ch = i < n ? (uint32_t)((first + i) % nchan) : 0u;
+    if (i < n) channel[i] = (uint8_t)ch;
+    const unsigned long long q = i < n ? power_q32(w0) : 0ull;
+    channel_rows(i < n, ch, i < n, culled, q, stats + BZR_ILLUM_EMITTED, power + BZR_ILLUM_EMITTED);
+  } else if (kPower || stats) {
     const unsigned long long made = __ballot(i < n), cut = __ballot(culled);
     unsigned long long qe = 0ull, qc = 0ull;
     if constexpr (kPower) {
@@ -3709,27 +3846,38 @@ __global__ __launch_bounds__(kBlock) void k_emit(bzr_emitter em, BeltTable bt, u
 // Rays that left the last lens (status OUTSIDE) meet the target plane: one count per landed ray.
 // kPower (bzr_illuminate_power): each landed ray also adds q(its weight) to its cell of flux (64-bit atomic), the
 // count only with `hist`; power[EXITED], power[LANDED] = the sums of q(w), one atomic per wave and counter.
-template <bool kPower>
+// kIllum 2 (bzr_illuminate_spectral): flux and hist are [nchan][cells], a ray of channel c lands in cell
+// c * cells + cell; stats and power are [nchan][4], reduced per channel (channel_rows).
+template <int kIllum>
 __global__ __launch_bounds__(kBlock) void k_land(bzr_target tg, float4 plane, float cell_u, float cell_v,
                                                  const float *__restrict__ rays, uint32_t ld, uint32_t n,
                                                  const uint32_t *__restrict__ status, uint32_t *__restrict__ hist,
                                                  unsigned long long *__restrict__ stats, const float *__restrict__ weight,
                                                  unsigned long long *__restrict__ flux,
-                                                 unsigned long long *__restrict__ power) {
+                                                 unsigned long long *__restrict__ power,
+                                                 const uint8_t *__restrict__ channel, uint32_t cells) {
+  constexpr bool kPower = kIllum != 0, kSpectral = kIllum == 2;
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   bool exited = false, landed = false;
   unsigned long long q = 0ull;
+  uint32_t ch = 0u;
   if (i < n && status[i] == BZR_RR_OUTSIDE) {
     exited = true;
     if constexpr (kPower) q = power_q32(weight[i]);
+    if constexpr (kSpectral) ch = channel[i];
     f3 s, d;
     load_ray(rays, ld, i, s, d);
     const int32_t cell = target_cell(tg, mk(plane.x, plane.y, plane.z), plane.w, cell_u, cell_v, s, d);
     if (cell >= 0) {
       landed = true;
-      if constexpr (kPower) atomicAdd(&flux[cell], q);
-      if (!kPower || hist) atomicAdd(&hist[cell], 1u);
+      const size_t at = kSpectral ? (size_t)ch * cells + (uint32_t)cell : (size_t)cell;
+      if constexpr (kPower) atomicAdd(&flux[at], q);
+      if (!kPower || hist) atomicAdd(&hist[at], 1u);
     }
+  }
+  if constexpr (kSpectral) {
+    channel_rows(exited, ch, exited, landed, q, stats + BZR_ILLUM_EXITED, power + BZR_ILLUM_EXITED);
+    return;
   }
   const unsigned long long ex = __ballot(exited), la = __ballot(landed);
   unsigned long long qx = 0ull, ql = 0ull;
@@ -3815,9 +3963,10 @@ extern "C" bzr_status bzr_emit(bzr_ctx *ctx, const bzr_emitter *em, uint64_t fir
   if (bzr_status s = upload_belts(ctx, em, st, bt, cos_lo, count, firsts)) return s;
   float *d_rays = host ? st.take<float>((size_t)n * 6) : rays_soa;
   uint32_t *d_patch = host ? (patch_index ? st.take<uint32_t>(n) : nullptr) : patch_index;
-  hipLaunchKernelGGL(k_emit<false>, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, *em, bt, first, n, n, d_rays, d_patch,
+  hipLaunchKernelGGL(k_emit<0>, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, *em, bt, first, n, n, d_rays, d_patch,
                      (uint32_t *)nullptr, (uint32_t *)nullptr, make_float4(0.0f, 0.0f, 0.0f, 0.0f), (const float4 *)nullptr,
-                     0u, (unsigned long long *)nullptr, (float *)nullptr, 0u, (unsigned long long *)nullptr);
+                     0u, (unsigned long long *)nullptr, (float *)nullptr, 0u, (unsigned long long *)nullptr,
+                     (uint8_t *)nullptr, 0u);
   BZR_HIP(hipGetLastError());
   if (host) {
     BZR_HIP(hipMemcpyAsync(rays_soa, d_rays, rb, hipMemcpyDeviceToHost, ctx->stream));
@@ -3828,12 +3977,18 @@ extern "C" bzr_status bzr_emit(bzr_ctx *ctx, const bzr_emitter *em, uint64_t fir
 }
 
 // bzr_illuminate (rad and flux null: counts only) and bzr_illuminate_power (rad and flux given, hist optional).
+// bzr_illuminate_spectral: nchan > 0, `ri` is the index table [nlens][nchan], and flux, hist, stats and power hold
+// nchan maps / rows of four, one per channel (NC below is 1 otherwise).
 static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
                              const bzr_emitter *em, uint64_t total_rays, const bzr_target *tg, const bzr_radiometry *rad,
-                             uint64_t *flux, uint32_t *hist, uint64_t stats[4], uint64_t power[4], uint32_t flags) {
+                             uint64_t *flux, uint32_t *hist, uint64_t *stats, uint64_t *power, uint32_t flags,
+                             bool spectral = false, uint32_t nchan = 0) {
   const bool with_power = rad != nullptr;
   if (!ctx) return set_error(BZR_ERR_INVALID_ARGUMENT, "null context");
   if (nlens == 0 || nlens > kMaxLenses) return set_error(BZR_ERR_INVALID_ARGUMENT, "nlens must be 1..8");
+  if (spectral)
+    if (bzr_status s = check_channels(ri, nchan)) return s;
+  const uint32_t NC = spectral ? nchan : 1u;
   if (!lenses || !ri || !tg || (!with_power && !hist)) return set_error(BZR_ERR_INVALID_ARGUMENT, "null argument");
   if (with_power) {
     if (!flux) return set_error(BZR_ERR_INVALID_ARGUMENT, "null flux_q32");
@@ -3851,10 +4006,12 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   uint32_t nb = 0;
   for (uint32_t l = 0; l < nlens; ++l) {
     if (bzr_status s = check_ctx_mesh(ctx, lenses[l])) return s;
-    set.lens[l] = view_of(lenses[l], ri[l]);
+    set.lens[l] = view_of(lenses[l], spectral ? 1.0f : ri[l]);
     nb = std::max(nb, set.lens[l].n);
   }
   DeviceGuard g(ctx->device);
+  if (spectral)
+    if (bzr_status s = upload_ri_table(ctx, ri, nlens, nchan)) return s;
   // target plane (normal = axis_u x axis_v normalised, constant = n . origin) and cell sizes, in the
   // oracle's operation order
   const float *au = tg->axis_u, *av = tg->axis_v;
@@ -3869,13 +4026,16 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   const float pc = pn.x * tg->origin[0] + (pn.y * tg->origin[1] + pn.z * tg->origin[2]);
   const float cell_u = tg->size_u / (float)tg->bins_u, cell_v = tg->size_v / (float)tg->bins_v;
   const size_t cells = (size_t)tg->bins_u * tg->bins_v;
+  if (spectral && cells >= (1ull << 32)) return set_error(BZR_ERR_INVALID_ARGUMENT, "target of 2^32 cells or more");
+  const size_t maps = cells * NC;  // cells of all the channels' maps
   const bool host = !(flags & BZR_DEVICE_PTRS);
   const uint32_t B = chunk_for(ctx, total_rays);
   if (bzr_status s = ensure_buffer(ctx->scratch, ctx->scratch_bytes,
                                    belt_bytes(em->belts) + round256((size_t)B * 24) + 2 * round256((size_t)B * 4) +
-                                       round256(32) + (host && hist ? round256(cells * 4) : 0) +
-                                       (with_power ? round256((size_t)B * 4) + round256(32) + (host ? round256(cells * 8) : 0)
-                                                   : 0)))
+                                       round256(32 * NC) + (host && hist ? round256(maps * 4) : 0) +
+                                       (with_power ? round256((size_t)B * 4) + round256(32 * NC) + (host ? round256(maps * 8) : 0)
+                                                   : 0) +
+                                       (spectral ? round256(B) : 0)))
     return s;
   Staging st{static_cast<char *>(ctx->scratch)};
   BeltTable bt;
@@ -3884,21 +4044,22 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   if (bzr_status s = upload_belts(ctx, em, st, bt, cos_lo, count, firsts)) return s;
   float *d_rays = st.take<float>((size_t)B * 6);
   uint32_t *d_st = st.take<uint32_t>(B), *d_seg = st.take<uint32_t>(B);
-  unsigned long long *d_stats = st.take<unsigned long long>(4);
-  uint32_t *d_hist = host && hist ? st.take<uint32_t>(cells) : hist;
-  BZR_HIP(hipMemsetAsync(d_stats, 0, 32, ctx->stream));
-  if (host && hist) BZR_HIP(hipMemsetAsync(d_hist, 0, cells * 4, ctx->stream));
+  unsigned long long *d_stats = st.take<unsigned long long>(4 * NC);
+  uint32_t *d_hist = host && hist ? st.take<uint32_t>(maps) : hist;
+  BZR_HIP(hipMemsetAsync(d_stats, 0, 32 * NC, ctx->stream));
+  if (host && hist) BZR_HIP(hipMemsetAsync(d_hist, 0, maps * 4, ctx->stream));
   float *d_w = nullptr;  // the batch's ray power, its four sums and the flux cells
   unsigned long long *d_power = nullptr, *d_flux = reinterpret_cast<unsigned long long *>(flux);
   if (with_power) {
     d_w = st.take<float>(B);
-    d_power = st.take<unsigned long long>(4);
-    BZR_HIP(hipMemsetAsync(d_power, 0, 32, ctx->stream));
+    d_power = st.take<unsigned long long>(4 * NC);
+    BZR_HIP(hipMemsetAsync(d_power, 0, 32 * NC, ctx->stream));
     if (host) {
-      d_flux = st.take<unsigned long long>(cells);
-      BZR_HIP(hipMemsetAsync(d_flux, 0, cells * 8, ctx->stream));
+      d_flux = st.take<unsigned long long>(maps);
+      BZR_HIP(hipMemsetAsync(d_flux, 0, maps * 8, ctx->stream));
     }
   }
+  uint8_t *d_ch = spectral ? st.take<uint8_t>(B) : nullptr;  // the batch's channel row
   Work w;
   const bool staged = use_staged(flags, B, nb);
   if (staged)
@@ -3907,14 +4068,18 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
                                     lenses[0]->sphere[3]);
   for (uint64_t first = 0; first < total_rays; first += B) {
     const uint32_t m = (uint32_t)std::min<uint64_t>(B, total_rays - first);
-    if (with_power)
-      hipLaunchKernelGGL(k_emit<true>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays,
+    if (spectral)
+      hipLaunchKernelGGL(k_emit<2>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays,
                          (uint32_t *)nullptr, d_st, d_seg, sphere, set.lens[0].always, set.lens[0].n_always, d_stats, d_w,
-                         rad->emission == BZR_EMISSION_LAMBERT ? 1u : 0u, d_power);
+                         rad->emission == BZR_EMISSION_LAMBERT ? 1u : 0u, d_power, d_ch, nchan);
+    else if (with_power)
+      hipLaunchKernelGGL(k_emit<1>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays,
+                         (uint32_t *)nullptr, d_st, d_seg, sphere, set.lens[0].always, set.lens[0].n_always, d_stats, d_w,
+                         rad->emission == BZR_EMISSION_LAMBERT ? 1u : 0u, d_power, (uint8_t *)nullptr, 0u);
     else
-      hipLaunchKernelGGL(k_emit<false>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays,
+      hipLaunchKernelGGL(k_emit<0>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays,
                          (uint32_t *)nullptr, d_st, d_seg, sphere, set.lens[0].always, set.lens[0].n_always, d_stats,
-                         (float *)nullptr, 0u, (unsigned long long *)nullptr);
+                         (float *)nullptr, 0u, (unsigned long long *)nullptr, (uint8_t *)nullptr, 0u);
     if (!staged) {  // the chain in place over the batch; culled rays (status NONE) are skipped
       TraceJob job{};
       job.rays = d_rays;
@@ -3926,7 +4091,13 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
       job.ld = B;
       job.weight = d_w;  // (a lossless surface leaves the weights as emitted: the plain chain)
       job.weight_in = d_w;
-      if (bzr_status s = fresnel ? run_fused<kModePower>(ctx, set, job, flags) : run_fused<kModeStage>(ctx, set, job, flags))
+      job.channel = d_ch;  // (the spectral chain refracts per channel with a lossless surface too: its run-time flag)
+      job.ri_table = ctx->ri_table;
+      job.nchan = nchan;
+      job.lossless = fresnel ? 0u : 1u;
+      if (bzr_status s = spectral  ? run_fused<kModeSpectral>(ctx, set, job, flags)
+                         : fresnel ? run_fused<kModePower>(ctx, set, job, flags)
+                                   : run_fused<kModeStage>(ctx, set, job, flags))
         return s;
     } else {
       for (uint32_t l = 0; l < nlens; ++l)
@@ -3938,40 +4109,50 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
           o.segments = d_seg;
           o.ri = set.lens[l].ri;
           o.weight = d_w;
-          if (bzr_status s = fresnel ? run_segment<kModePower>(use_fast(flags), ctx, set.lens[l], d_rays, B, 0, m, d_st, o, w)
-                                     : run_segment<kModeStage>(use_fast(flags), ctx, set.lens[l], d_rays, B, 0, m, d_st, o, w))
+          o.channel = d_ch;
+          o.ri_row = spectral ? ctx->ri_table + (size_t)l * nchan : nullptr;
+          o.nchan = nchan;
+          o.lossless = fresnel ? 0u : 1u;
+          if (bzr_status s = spectral  ? run_segment<kModeSpectral>(use_fast(flags), ctx, set.lens[l], d_rays, B, 0, m, d_st, o, w)
+                             : fresnel ? run_segment<kModePower>(use_fast(flags), ctx, set.lens[l], d_rays, B, 0, m, d_st, o, w)
+                                       : run_segment<kModeStage>(use_fast(flags), ctx, set.lens[l], d_rays, B, 0, m, d_st, o, w))
             return s;
         }
     }
-    if (with_power)
-      hipLaunchKernelGGL(k_land<true>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg,
+    if (spectral)
+      hipLaunchKernelGGL(k_land<2>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg,
                          make_float4(pn.x, pn.y, pn.z, pc), cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats, d_w, d_flux,
-                         d_power);
+                         d_power, (const uint8_t *)d_ch, (uint32_t)cells);
+    else if (with_power)
+      hipLaunchKernelGGL(k_land<1>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg,
+                         make_float4(pn.x, pn.y, pn.z, pc), cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats, d_w, d_flux,
+                         d_power, (const uint8_t *)nullptr, 0u);
     else
-      hipLaunchKernelGGL(k_land<false>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg,
+      hipLaunchKernelGGL(k_land<0>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg,
                          make_float4(pn.x, pn.y, pn.z, pc), cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats,
-                         (const float *)nullptr, (unsigned long long *)nullptr, (unsigned long long *)nullptr);
+                         (const float *)nullptr, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                         (const uint8_t *)nullptr, 0u);
     BZR_HIP(hipGetLastError());
   }
-  unsigned long long hs[4];
-  BZR_HIP(hipMemcpyAsync(hs, d_stats, 32, hipMemcpyDeviceToHost, ctx->stream));
-  std::vector<uint32_t> hh(host && hist ? cells : 0);
-  if (host && hist) BZR_HIP(hipMemcpyAsync(hh.data(), d_hist, cells * 4, hipMemcpyDeviceToHost, ctx->stream));
-  unsigned long long hp[4] = {0, 0, 0, 0};
-  std::vector<unsigned long long> hf(host && with_power ? cells : 0);
+  unsigned long long hs[4 * kMaxChannels];
+  BZR_HIP(hipMemcpyAsync(hs, d_stats, 32 * NC, hipMemcpyDeviceToHost, ctx->stream));
+  std::vector<uint32_t> hh(host && hist ? maps : 0);
+  if (host && hist) BZR_HIP(hipMemcpyAsync(hh.data(), d_hist, maps * 4, hipMemcpyDeviceToHost, ctx->stream));
+  unsigned long long hp[4 * kMaxChannels] = {};
+  std::vector<unsigned long long> hf(host && with_power ? maps : 0);
   if (with_power) {
-    BZR_HIP(hipMemcpyAsync(hp, d_power, 32, hipMemcpyDeviceToHost, ctx->stream));
-    if (host) BZR_HIP(hipMemcpyAsync(hf.data(), d_flux, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
+    BZR_HIP(hipMemcpyAsync(hp, d_power, 32 * NC, hipMemcpyDeviceToHost, ctx->stream));
+    if (host) BZR_HIP(hipMemcpyAsync(hf.data(), d_flux, maps * 8, hipMemcpyDeviceToHost, ctx->stream));
   }
   BZR_HIP(hipStreamSynchronize(ctx->stream));
   if (host && hist)
-    for (size_t k = 0; k < cells; ++k) hist[k] += hh[k];
+    for (size_t k = 0; k < maps; ++k) hist[k] += hh[k];
   if (host && with_power)
-    for (size_t k = 0; k < cells; ++k) flux[k] += hf[k];
+    for (size_t k = 0; k < maps; ++k) flux[k] += hf[k];
   if (stats)
-    for (int k = 0; k < 4; ++k) stats[k] = hs[k];
+    for (uint32_t k = 0; k < 4 * NC; ++k) stats[k] = hs[k];
   if (power)
-    for (int k = 0; k < 4; ++k) power[k] = hp[k];
+    for (uint32_t k = 0; k < 4 * NC; ++k) power[k] = hp[k];
   return BZR_OK;
 }
 
@@ -3987,4 +4168,13 @@ extern "C" bzr_status bzr_illuminate_power(bzr_ctx *ctx, const bzr_mesh *const *
                                            uint64_t power_q32[4], uint32_t flags) {
   if (!rad) return set_error(BZR_ERR_INVALID_ARGUMENT, "null radiometry");
   return illuminate(ctx, lenses, ri, nlens, em, total_rays, tg, rad, flux_q32, hist, stats, power_q32, flags);
+}
+
+extern "C" bzr_status bzr_illuminate_spectral(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                              uint32_t nlens, uint32_t nchan, const bzr_emitter *em, uint64_t total_rays,
+                                              const bzr_target *tg, const bzr_radiometry *rad, uint64_t *flux_q32,
+                                              uint32_t *hist, uint64_t *stats, uint64_t *power_q32, uint32_t flags) {
+  if (!rad) return set_error(BZR_ERR_INVALID_ARGUMENT, "null radiometry");
+  return illuminate(ctx, lenses, ri_table, nlens, em, total_rays, tg, rad, flux_q32, hist, stats, power_q32, flags, true,
+                    nchan);
 }

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <stdexcept>
 #include <type_traits>
 
 #include "bzr/bzr.hpp"
@@ -95,6 +96,25 @@ void traceChainPower(std::vector<BezierLens const *> const &lenses, Ray const *r
                                 records(rays + off), weights ? weights + off : nullptr, static_cast<uint32_t>(m),
                                 records(outRays + off), outWeights + off, words(outStatus + off),
                                 outSegments ? outSegments + off : nullptr, BZR_HOST_PTRS | BZR_RAYS_AOS));
+  }
+}
+
+void traceChainSpectral(std::vector<BezierLens const *> const &lenses, std::vector<float> const &riTable, Ray const *rays,
+                        uint8_t const *channels, float const *weights, std::size_t n, Ray *outRays, float *outWeights,
+                        RefractionResult *outStatus, uint32_t *outSegments, Context *ctx) {
+  if (lenses.empty() || riTable.size() % lenses.size()) throw std::invalid_argument("riTable must be [lenses][nchan]");
+  Context &c = ctx ? *ctx : defaultContext();
+  std::vector<bzr_mesh const *> meshes;
+  for (auto const *l : lenses) meshes.push_back(l->getMesh().device(c));
+  const uint32_t nchan = static_cast<uint32_t>(riTable.size() / lenses.size());
+  std::lock_guard<std::mutex> hold(c.lock());
+  for (std::size_t off = 0; off < n; off += kMaxBatch) {
+    const std::size_t m = std::min(kMaxBatch, n - off);
+    check(bzr_trace_chain_spectral(c.get(), meshes.data(), riTable.data(), static_cast<uint32_t>(meshes.size()), nchan,
+                                   records(rays + off), channels ? channels + off : nullptr,
+                                   weights ? weights + off : nullptr, static_cast<uint32_t>(m), records(outRays + off),
+                                   outWeights + off, words(outStatus + off), outSegments ? outSegments + off : nullptr,
+                                   BZR_HOST_PTRS | BZR_RAYS_AOS));
   }
 }
 

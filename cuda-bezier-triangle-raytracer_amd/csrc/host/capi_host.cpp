@@ -2,9 +2,11 @@
 // Every entry point catches what the drop-in classes throw (the reference throws
 // char const* and std::out_of_range, reference/mesh.cpp:204, bezierMesh.cpp:17-18)
 // and reports it as a status code + bzr_last_error() text.
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "bzr/bzr.hpp"
 #include "single_ray.hpp"
@@ -203,6 +205,41 @@ int32_t bzr_debug_newton_short(const void *patches, uint32_t n, uint32_t stride,
 int32_t bzr_debug_fresnel(const float *eta, const float *cs, uint32_t n, float *t_out) {
   if ((!eta || !cs || !t_out) && n) return bad("null argument");
   bzr_host::fresnel_pairs(eta, cs, n, t_out);
+  return BZR_OK;
+}
+
+// Every value is computed before the first is written: a rejected call leaves out_ri as it was.
+bzr_status bzr_dispersion_index(int32_t model, const double *coeff, uint32_t ncoeff, const double *wavelength_um,
+                                uint32_t n, float *out_ri) {
+  if (model != BZR_DISPERSION_CAUCHY && model != BZR_DISPERSION_SELLMEIER) return bad("unknown dispersion model");
+  if (model == BZR_DISPERSION_CAUCHY ? (ncoeff != 2 && ncoeff != 3) : (ncoeff != 2 && ncoeff != 4 && ncoeff != 6))
+    return bad("ncoeff: 2 or 3 (Cauchy), 2, 4 or 6 (Sellmeier)");
+  if (!coeff || ((!wavelength_um || !out_ri) && n)) return bad("null argument");
+  std::vector<float> ri;
+  try {
+    ri.resize(n);
+  } catch (std::bad_alloc const &) {
+    bzr_internal_set_error("out of memory");
+    return BZR_ERR_OUT_OF_MEMORY;
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    const double l = wavelength_um[i];
+    if (!std::isfinite(l) || !(l > 0.0)) return bad("wavelength must be finite and positive");
+    const double l2 = l * l;
+    double v;
+    if (model == BZR_DISPERSION_CAUCHY) {
+      v = coeff[0] + coeff[1] / l2;
+      if (ncoeff == 3) v += coeff[2] / (l2 * l2);
+    } else {
+      double n2 = 1.0;
+      for (uint32_t k = 0; k < ncoeff; k += 2) n2 += coeff[k] * l2 / (l2 - coeff[k + 1]);
+      if (!(n2 > 0.0)) return bad("Sellmeier n^2 is not positive");
+      v = std::sqrt(n2);
+    }
+    ri[i] = static_cast<float>(v);
+    if (!std::isfinite(v) || !std::isfinite(ri[i])) return bad("index is not finite");
+  }
+  if (n) std::memcpy(out_ri, ri.data(), (std::size_t)n * sizeof(float));
   return BZR_OK;
 }
 

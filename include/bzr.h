@@ -246,6 +246,35 @@ bzr_status bzr_trace_chain_power(bzr_ctx *ctx, const bzr_mesh *const *lenses, co
                                  uint32_t nlens, const float *rays_soa, const float *weight_in, uint32_t n,
                                  float *out_rays_soa, float *out_weight, uint32_t *out_status, uint32_t *out_segments,
                                  uint32_t flags);
+/* ---- spectral channels ----
+ * A channel is an index c in [0, nchan), 1 <= nchan <= BZR_MAX_CHANNELS: one wavelength sample.
+ * ri_table[nlens][nchan] (row-major float32, host memory always, like refractive_index) gives lens l's index
+ * for channel c; bzr_dispersion_index fills a row from a glass's dispersion formula. */
+#define BZR_MAX_CHANNELS 64
+/* bzr_trace_chain_power with one refractive index per ray and lens.  channel [n], one uint8_t per ray, is a plain
+ * row in either ray layout, host or device memory as the rays.  Ray i is traced exactly as bzr_trace_chain_power
+ * traces it with refractive_index[l] = ri_table[l][channel[i]]: the same eta = 1/ri division on the device, the
+ * same Fresnel term (exact under BZR_MODE_FAST too), the same bits in out_rays, out_weight, out_status and
+ * out_segments.  weight_in may be NULL and may be out_weight; out_weight is required.  A ray whose channel[i] is at
+ * or above nchan is handled like a ray with a non-finite component: status NONE, one segment, its ray and weight
+ * unchanged, and no other ray is affected -- on every pipeline, for host rows as for device rows (which cannot be
+ * validated), so it is no error.  nchan of 0 or above BZR_MAX_CHANNELS, a NULL ri_table, channel or out_weight and
+ * bzr_trace_chain's nlens rules return BZR_ERR_INVALID_ARGUMENT before any output is touched.  Flags,
+ * BZR_RAYS_AOS, the pipeline choice and chunking are bzr_trace_chain_power's.  The multi-GPU plan (bzr_trace_tiled,
+ * bzr_tiled_*, bzr_pack_frame) takes no channels, and bzr_refract stays single-index. */
+bzr_status bzr_trace_chain_spectral(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table, uint32_t nlens,
+                                    uint32_t nchan, const float *rays_soa, const uint8_t *channel,
+                                    const float *weight_in, uint32_t n, float *out_rays_soa, float *out_weight,
+                                    uint32_t *out_status, uint32_t *out_segments, uint32_t flags);
+/* Refractive index from a dispersion formula, on the host (no context, no device): evaluated in binary64 and
+ * rounded once to float.  wavelength_um [n] in micrometres, out_ri [n].
+ *   BZR_DISPERSION_CAUCHY     n = A + B / l^2 + C / l^4           coeff = A, B[, C]             ncoeff 2 or 3
+ *   BZR_DISPERSION_SELLMEIER  n^2 = 1 + sum_k B_k l^2 / (l^2 - C_k)   coeff = B1, C1, B2, C2, ...  ncoeff 2, 4 or 6
+ * An unknown model, another ncoeff, a wavelength that is not finite and positive, a result that is not finite or a
+ * Sellmeier n^2 that is not positive return BZR_ERR_INVALID_ARGUMENT with nothing written. */
+enum { BZR_DISPERSION_CAUCHY = 0, BZR_DISPERSION_SELLMEIER = 1 };
+bzr_status bzr_dispersion_index(int32_t model, const double *coeff, uint32_t ncoeff, const double *wavelength_um,
+                                uint32_t n, float *out_ri);
 /* Multi-GPU refraction chain in ONE process (C/C++ hosts without torch.distributed):
  * image-plane tiles are dealt round-robin to the contexts, one per device.  Tile k is the rays
  * [k * tile_rays, (k + 1) * tile_rays) of the SoA input (callers order rays tile-major, e.g. 64x64-pixel
@@ -379,6 +408,19 @@ bzr_status bzr_illuminate_power(bzr_ctx *ctx, const bzr_mesh *const *lenses, con
                                 uint32_t nlens, const bzr_emitter *em, uint64_t total_rays, const bzr_target *target,
                                 const bzr_radiometry *rad, uint64_t *flux_q32, uint32_t *hist, uint64_t stats[4],
                                 uint64_t power_q32[4], uint32_t flags);
+/* bzr_illuminate_power per spectral channel: the same emitter stream, sphere cull, batching rule, 32.32 fixed point
+ * and accumulation into the outputs, with global ray i (the emitter's 64-bit ray number) in channel i mod nchan and
+ * refracted with ri_table[l][i mod nchan].  Kept per channel: flux_q32 [nchan][bins_v][bins_u], hist (may be NULL)
+ * of the same shape, stats [nchan][4] and power_q32 [nchan][4] (each may be NULL).  Summed over the channels, the
+ * EMITTED and CULLED counts and power sums do not depend on the table and equal bzr_illuminate_power's for the same
+ * emitter (the cull happens before the first refraction).  rad->surface == BZR_SURFACE_LOSSLESS keeps the weights
+ * as emitted; the rays still refract with their channel's index.  No source spectrum is taken: the maps are linear
+ * in it, so a caller scales channel c's map by the source's power in that channel on the host.  The argument checks
+ * are bzr_illuminate_power's, plus nchan in 1..BZR_MAX_CHANNELS and a non-NULL ri_table. */
+bzr_status bzr_illuminate_spectral(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table, uint32_t nlens,
+                                   uint32_t nchan, const bzr_emitter *em, uint64_t total_rays, const bzr_target *target,
+                                   const bzr_radiometry *rad, uint64_t *flux_q32, uint32_t *hist, uint64_t *stats,
+                                   uint64_t *power_q32, uint32_t flags);
 /* The bounding sphere bzr_illuminate culls with: center xyz, radius. */
 bzr_status bzr_mesh_bounding_sphere(const bzr_mesh *mesh, float out[4]);
 

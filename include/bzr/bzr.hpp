@@ -458,6 +458,12 @@ void traceChain(std::vector<BezierLens const *> const &lenses, Ray const *rays, 
 void traceChainPower(std::vector<BezierLens const *> const &lenses, Ray const *rays, float const *weights, std::size_t n,
                      Ray *outRays, float *outWeights, RefractionResult *outStatus, uint32_t *outSegments = nullptr,
                      Context *ctx = nullptr);
+// traceChainPower with one refractive index per ray and lens (bzr_trace_chain_spectral): riTable [lenses.size()][nchan]
+// row-major is lens l's index for channel c, channels[i] < nchan the channel of ray i.  The lenses' own
+// refractive index is not read.  Throws if riTable.size() is not a multiple of lenses.size().
+void traceChainSpectral(std::vector<BezierLens const *> const &lenses, std::vector<float> const &riTable, Ray const *rays,
+                        uint8_t const *channels, float const *weights, std::size_t n, Ray *outRays, float *outWeights,
+                        RefractionResult *outStatus, uint32_t *outSegments = nullptr, Context *ctx = nullptr);
 // The same chain over several devices from one process (bzr_trace_tiled): tiles of tileRays
 // consecutive rays dealt round-robin to `ctxs` (one per device, distinct), results in input order.
 void traceChainTiled(std::vector<Context *> const &ctxs, std::vector<BezierLens const *> const &lenses,
