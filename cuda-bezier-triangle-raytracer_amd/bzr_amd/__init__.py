@@ -78,6 +78,7 @@ _SIGS = {
     "bzr_trace_chain": [_P, _P, _P, _U32, _P, _U32, _P, _P, _P, _U32],
     "bzr_trace_chain_power": [_P, _P, _P, _U32, _P, _P, _U32, _P, _P, _P, _P, _U32],
     "bzr_trace_chain_spectral": [_P, _P, _P, _U32, _U32, _P, _P, _P, _U32, _P, _P, _P, _P, _U32],
+    "bzr_trace_chain_tir": [_P, _P, _P, _U32, _U32, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _U32],
     "bzr_dispersion_index": [_I32, _P, _U32, _P, _U32, _P],
     "bzr_trace_tiled": [_P, _U32, _P, _P, _U32, _P, _U32, _U32, _P, _P, _P, _U32],
     "bzr_tiled_create": [_P, _U32, _U32, _U32, _U32, _I32, ctypes.POINTER(_P)],
@@ -127,7 +128,7 @@ _SIGS = {
 }
 # entry points added without an ABI bump: an explicitly chosen earlier build (BZR_LIBRARY) may lack them
 _ADDED = ("bzr_trace_chain_power", "bzr_illuminate_power", "bzr_trace_chain_spectral", "bzr_illuminate_spectral",
-          "bzr_dispersion_index")
+          "bzr_dispersion_index", "bzr_trace_chain_tir")
 _RET = {"bzr_last_error": ctypes.c_char_p, "bzr_abi_version": _I32}
 
 _lib = None
@@ -482,6 +483,36 @@ def trace_chain_spectral(ctx: Context, lenses, ri_table, rays, channel, weight=N
         _check(lib().bzr_trace_chain_spectral(ctx.handle, ctypes.cast(handles, _P), table.ctypes.data if table.size else None,
                                               nl, nchan, r.ptr, c.ptr, wi.ptr, n, o.ptr, w.ptr, s.ptr, g.ptr, res | mode))
     return out_rays, out_weight, out_status, out_segments
+
+
+MAX_BOUNCES = 8  # BZR_MAX_BOUNCES
+
+
+def trace_chain_tir(ctx: Context, lenses, ri_table, rays, channel=None, weight=None, max_bounces=4, out_rays=None,
+                    out_weight=None, out_status=None, out_segments=None, out_bounces=None, mode=MODE_PARITY):
+    """trace_chain_spectral with total internal reflection -> (rays, weight [n], status [n], segments [n], bounces [n]).
+    A ray that cannot leave a lens (s2 >= 1 at its back surface) is mirrored inside it and traced against the same lens
+    again, up to max_bounces (<= MAX_BOUNCES) times per lens; its weight is not touched.  channel None: every ray is
+    channel 0.  segments counts the bounce segments too, bounces is the ray's reflections over all lenses.  With
+    max_bounces = 0 the result is trace_chain_spectral's (bzr.h bzr_trace_chain_tir)."""
+    n = _n_of(rays, mode)
+    nl = len(lenses)
+    handles = (_P * nl)(*[m.handle for m in lenses])
+    table, nchan = _ri_table(ri_table, nl)
+    out_rays = _empty_like(rays, 6, np.float32, mode) if out_rays is None else out_rays
+    out_weight = _empty_like(rays, 0, np.float32, mode) if out_weight is None else out_weight
+    out_status = _empty_like(rays, 0, np.uint32, mode) if out_status is None else out_status
+    out_segments = _empty_like(rays, 0, np.uint32, mode) if out_segments is None else out_segments
+    out_bounces = _empty_like(rays, 0, np.uint32, mode) if out_bounces is None else out_bounces
+    r, c, wi = _Buf(rays, np.float32), _Buf(channel, np.uint8), _Buf(weight, np.float32)
+    o, w = _Buf(out_rays, np.float32, True), _Buf(out_weight, np.float32, True)
+    s, g, b = _Buf(out_status, np.uint32, True), _Buf(out_segments, np.uint32, True), _Buf(out_bounces, np.uint32, True)
+    res = _residency(r, c, o, w, s, g, b, wi)
+    with _stream_for(ctx, res):
+        _check(lib().bzr_trace_chain_tir(ctx.handle, ctypes.cast(handles, _P), table.ctypes.data if table.size else None,
+                                         nl, nchan, r.ptr, c.ptr, wi.ptr, n, int(max_bounces), o.ptr, w.ptr, s.ptr, g.ptr,
+                                         b.ptr, res | mode))
+    return out_rays, out_weight, out_status, out_segments, out_bounces
 
 
 def dispersion_index(model: int, coeff, wavelength_um) -> np.ndarray:

@@ -310,6 +310,26 @@ __device__ __forceinline__ uint32_t refract_hit(const Hit &h, float ri, f3 s, f3
   return refract_hit_t<false>(h, ri, s, d, expected, o_s, o_d, gain);
 }
 
+// Snell's step with total internal reflection (kModeTir).  A ray that leaves glass (expected OUTSIDE, cs >= 0) with
+// s2 = ri^2 (1 - cs^2) >= 1 cannot refract: when `may_reflect` (the ray's channel is in the table and its bounce
+// budget in this lens is not spent) it is mirrored at the hit -- k = 2 cs, r = d - n k per component, o_d =
+// normalized(r), o_s = the hit's point -- and the step returns kReflected, a status only the chain drivers see:
+// the ray stays inside and meets the same lens again.  Everything else is refract_hit_t: s2 < 0.99 refracts,
+// 0.99 <= s2 < 1 (the reference's grazing limit), a NaN s2 and a refused reflection return NONE.
+constexpr uint32_t kReflected = 3u;
+template <bool kGain>
+__device__ __forceinline__ uint32_t tir_hit_t(const Hit &h, float ri, f3 s, f3 d, uint32_t expected, bool may_reflect,
+                                              f3 &o_s, f3 &o_d, float &gain) {
+  const float s2 = ri * ri * (1.0f - h.cs * h.cs);
+  if (expected == BZR_RR_OUTSIDE && may_reflect && h.what == kIntersect && h.cs >= 0.0f && s2 >= 1.0f) {
+    const float k = 2.0f * h.cs;
+    o_d = normalized(sub(d, scale(h.normal, k)));
+    o_s = h.point;
+    return kReflected;
+  }
+  return refract_hit_t<kGain>(h, ri, s, d, expected, o_s, o_d, gain);
+}
+
 __device__ __forceinline__ void load_ray(const float *__restrict__ r, uint32_t n, uint32_t i, f3 &s, f3 &d) {
   s = mk(r[i], r[(size_t)n + i], r[(size_t)2 * n + i]);
   d = mk(r[(size_t)3 * n + i], r[(size_t)4 * n + i], r[(size_t)5 * n + i]);
@@ -437,9 +457,14 @@ constexpr uint32_t kSlotWords = 12;  // t, point, cos, bary, normal, source patc
 // kModeSpectral: kModePower with the refractive index read per lane -- ray i carries channel[i], lens l refracts it
 // with ri_table[l][channel[i]].  A channel at or above nchan ends the ray at its first surface like a miss (NONE,
 // one segment, ray and weight as they came).  Again a mode of its own: the other four compile to the code they had.
-enum OutMode { kModeHits = 0, kModeRefract = 1, kModeStage = 2, kModePower = 3, kModeSpectral = 4 };
-constexpr bool is_stage(int mode) { return mode == kModeStage || mode == kModePower || mode == kModeSpectral; }
-constexpr bool has_power(int mode) { return mode == kModePower || mode == kModeSpectral; }
+// kModeTir: kModeSpectral with total internal reflection (tir_hit_t) -- a ray that cannot leave a lens is mirrored
+// and traced against the same lens again, up to max_bounces times per lens.  A mode of its own once more.
+enum OutMode { kModeHits = 0, kModeRefract = 1, kModeStage = 2, kModePower = 3, kModeSpectral = 4, kModeTir = 5 };
+constexpr bool is_stage(int mode) {
+  return mode == kModeStage || mode == kModePower || mode == kModeSpectral || mode == kModeTir;
+}
+constexpr bool has_power(int mode) { return mode == kModePower || mode == kModeSpectral || mode == kModeTir; }
+constexpr bool has_channels(int mode) { return mode == kModeSpectral || mode == kModeTir; }
 struct Out {
   float *hits;               // kModeHits: SoA [13][ld]
   float *rays;               // kModeRefract: output rays; kModeStage: rays in flight (in place)
@@ -456,6 +481,13 @@ struct Out {
   const float *ri_row;       // kModeSpectral: this lens's row of the index table [nchan] (device memory)
   uint32_t nchan;
   uint32_t lossless;         // kModeSpectral: the weights stay as they are (the gain counts as 1)
+  // kModeTir (channel may be null: every ray is channel 0).  An OUTSIDE stage marks the rays it reflected in `pend`
+  // (their status stays INSIDE); a lens's first OUTSIDE stage traces the rays whose status is not NONE, each later
+  // one (`bounce_stage`) only the rays whose pend word is set.  The chain's first stage clears both rows.
+  uint32_t *pend;            // [ld] 1: reflected by the last OUTSIDE stage, to be traced against this lens again
+  uint32_t *bounces;         // [ld] optional: the ray's reflections so far
+  uint32_t bounce_stage;     // this stage traces the pending rays only
+  uint32_t may_reflect;      // the rays this stage traces have bounce budget left in this lens
 };
 
 template <int kMode>
@@ -467,15 +499,26 @@ __device__ __forceinline__ void emit(const Out &o, uint32_t ld, uint32_t gi, f3 
     float gain = 1.0f;
     float ri = o.ri;
     bool in_table = true;
-    if constexpr (kMode == kModeSpectral) {
-      const uint32_t ch = o.channel[gi];
+    if constexpr (has_channels(kMode)) {
+      const uint32_t ch = (kMode == kModeTir && !o.channel) ? 0u : o.channel[gi];
       in_table = ch < o.nchan;
       ri = o.ri_row[in_table ? ch : 0u];
     }
-    uint32_t st = refract_hit_t<has_power(kMode)>(h, ri, s, d, o.expected ? o.expected[gi] : o.expected_all, os, od, gain);
-    if constexpr (kMode == kModeSpectral) {
+    uint32_t st;
+    if constexpr (kMode == kModeTir)
+      st = tir_hit_t<true>(h, ri, s, d, o.expected_all, in_table && o.may_reflect, os, od, gain);
+    else
+      st = refract_hit_t<has_power(kMode)>(h, ri, s, d, o.expected ? o.expected[gi] : o.expected_all, os, od, gain);
+    if constexpr (has_channels(kMode)) {
       if (!in_table) st = BZR_RR_NONE;
       if (o.lossless) gain = 1.0f;
+    }
+    bool reflected = false;
+    if constexpr (kMode == kModeTir) {  // in memory a reflected ray is inside and pending; its weight is not touched
+      reflected = st == kReflected;
+      if (o.first || o.expected_all == BZR_RR_OUTSIDE) o.pend[gi] = reflected ? 1u : 0u;
+      if (o.bounces && (o.first || reflected)) o.bounces[gi] = o.first ? 0u : o.bounces[gi] + 1u;
+      if (reflected) st = BZR_RR_INSIDE;
     }
     if (kMode == kModeRefract || st != BZR_RR_NONE || (is_stage(kMode) && o.first)) {
       if (st == BZR_RR_NONE) {
@@ -487,7 +530,7 @@ __device__ __forceinline__ void emit(const Out &o, uint32_t ld, uint32_t gi, f3 
     o.status[gi] = st;
     if (is_stage(kMode) && o.segments) o.segments[gi] = o.first ? 1u : o.segments[gi] + 1u;
     if constexpr (has_power(kMode)) {  // the first stage writes every ray's weight, later ones the refracted rays'
-      if (o.first || st != BZR_RR_NONE) {
+      if (o.first || (st != BZR_RR_NONE && !reflected)) {
         float w = o.first ? (o.weight_in ? o.weight_in[gi] : 1.0f) : o.weight[gi];
         if (st != BZR_RR_NONE) w = w * gain;
         o.weight[gi] = w;
@@ -1486,6 +1529,8 @@ __global__ __launch_bounds__(kBlock) void k_finish(MeshView m, const float *rays
     return;
   }
   if (is_stage(kMode) && !o.first && o.status[gi] == BZR_RR_NONE) return;
+  if constexpr (kMode == kModeTir)  // a bounce stage: the rays that left this lens keep every word
+    if (o.bounce_stage && o.pend[gi] == 0u) return;
   // the ray is loaded unconditionally: making the load depend on w.count (an intersect chunk's hits need it
   // only for an overflow ray) serialises the two reads and measured slower (cfg3 k_finish 0.059 -> 0.069 ms,
   // profiles/r04_ab_traverse_wpe8.jsonl, variant "finish")
@@ -1714,8 +1759,17 @@ struct TraceWords {
   // (6.5 KB per wave at 6 waves per SIMD) has no room left
   static constexpr int kStackCap = (BZR_TRACE_BUNDLE && kMode != kModeHits) ? 2 * kStack : kStack;
 };
+// kModeTir keeps the lane's counters (segments | reflections << 16) and its weight here between segments: two
+// registers less across the walks.  (An empty base in every other mode: their layout is what it was.)
 template <int kMode>
-struct TraceLds {  // per wave
+struct TraceKeep {};
+template <>
+struct TraceKeep<kModeTir> {
+  uint32_t count[64];
+  float weight[64];
+};
+template <int kMode>
+struct TraceLds : TraceKeep<kMode> {  // per wave
   uint32_t stack[TraceWords<kMode>::kStackCap];
   float hit[TraceWords<kMode>::kHit][64];    // the lane's current winner (written only when it improves)
   unsigned long long emask[kEntries];        // collected leaves: gate ballot
@@ -2204,6 +2258,8 @@ struct TraceJob {
   const float *ri_table;           // kModeSpectral [count][nchan]: lens l's index for channel c (device memory)
   uint32_t nchan;
   uint32_t lossless;               // kModeSpectral: the weights stay as they are (the gain counts as 1)
+  uint32_t *bounces;               // kModeTir, optional [n]: the rays' reflections (channel may be null: channel 0)
+  uint32_t max_bounces;            // kModeTir: reflections allowed per ray and lens (<= BZR_MAX_BOUNCES)
 };
 
 // kTraceWpe: amdgpu_waves_per_eu lower bound for k_trace.  The chain kernel needs 72 VGPRs
@@ -2311,6 +2367,69 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
   float wgt = 1.0f;  // kModePower: the lane's power (loaded behind the first segment's walk, below)
   const uint32_t nseg = is_stage(kMode) ? 2u * lenses.count : 1u;
   uint32_t st = BZR_RR_NONE, seg = 0;
+  if constexpr (kMode == kModeTir) {
+    // The lens stays wave-uniform: per lens one INSIDE segment (b == 0), then up to 1 + max_bounces OUTSIDE segments
+    // over the lanes still inside it (`pend`); lanes that left the lens wait, and a wave vote ends the lens's
+    // segments when none is pending.  The last OUTSIDE segment may not reflect, so no lane leaves the loop pending.
+    // The lane's counters (segments in the low half, reflections in the high half) and its weight wait in LDS.
+    L.count[lane] = 0u;
+    L.weight[lane] = 1.0f;
+    for (uint32_t l = 0; l < lenses.count; ++l) {
+      if (!__any(alive)) break;
+      const MeshView &m = lenses.lens[l];
+      bool pend = false;
+      for (uint32_t b = 0; b < job.max_bounces + 2u; ++b) {
+        const bool act = b == 0u ? alive : pend;
+        if (!__any(act)) break;
+        unsigned long long best;
+        const uint32_t r0 = ctr.rounds, w0 = ctr.pairs + ctr.follows;
+        trace_segment<kMode, kFast, kCount>(m, s, d, act, best, L, lane, ctr);
+        if (kCount) {
+          ctr.segments += popc64(__ballot(act));
+          if (b != 0u) {  // back surfaces (odd), bounce segments included
+            ctr.rounds_odd += ctr.rounds - r0;
+            ctr.runs_odd += ctr.pairs + ctr.follows - w0;
+          }
+        }
+        // (the caller's weight behind the first walk, as below: fetched ahead of the loop, all four kernels came out
+        // with 36 B of scratch reserved)
+        if (l == 0u && b == 0u && i < n && job.weight_in) L.weight[lane] = job.weight_in[i];
+        Hit h = no_hit();
+        uint32_t patch = 0xFFFFFFFFu;
+        if (best != ~0ull) h = winner(L, lane, patch);
+        const uint32_t ch = (i < n && job.channel) ? job.channel[i] : 0u;  // (reloaded, as kModeSpectral below)
+        const bool in_table = ch < job.nchan;
+        const float ri = job.ri_table[l * job.nchan + (in_table ? ch : 0u)];
+        f3 os, od;
+        float gain = 1.0f;
+        uint32_t r = tir_hit_t<true>(h, ri, s, d, b == 0u ? uint32_t(BZR_RR_INSIDE) : uint32_t(BZR_RR_OUTSIDE),
+                                     in_table && b <= job.max_bounces, os, od, gain);
+        if (!in_table) r = BZR_RR_NONE;
+        if (job.lossless) gain = 1.0f;
+        if (act) {
+          L.count[lane] += r == kReflected ? 0x10001u : 1u;
+          if (r == kReflected) {  // stays pending; the weight is not touched
+            s = os;
+            d = od;
+          } else {
+            pend = b == 0u && r != BZR_RR_NONE;
+            if (r == BZR_RR_NONE) alive = false;
+            else {
+              s = os;
+              d = od;
+              L.weight[lane] = L.weight[lane] * gain;
+            }
+          }
+        }
+      }
+    }
+    // (no status register: a lane still alive has left every lens, any other ended NONE)
+    st = alive ? uint32_t(BZR_RR_OUTSIDE) : uint32_t(BZR_RR_NONE);
+    seg = L.count[lane];
+    wgt = L.weight[lane];
+    if (traced && job.bounces) job.bounces[i] = seg >> 16;
+    seg &= 0xFFFFu;
+  } else
   for (uint32_t k = 0; k < nseg; ++k) {
     if (!__any(alive)) break;
     const MeshView &m = lenses.lens[k >> 1];
@@ -2437,14 +2556,17 @@ __global__ __launch_bounds__(kBlock) void k_refract_scan(MeshView m, const float
 
 // The chain by the reference's brute-force scan.  kScan 1: with the rays' power (kModePower's brute-force form, the
 // A/B reference of the two culled paths); weight_in may be null (1) and may alias out_weight.  kScan 2: kModeSpectral's
-// form, the index from ri_table[l][channel[i]].  (An int, not an enum: instantiations 0 and 1 keep their names.)
+// form, the index from ri_table[l][channel[i]].  kScan 3: kModeTir's form -- per lane, a lens's OUTSIDE segment is
+// repeated while the ray reflects, up to max_bounces times per lens; channel may be null (channel 0), out_bounces
+// is optional.  (An int, not an enum: instantiations 0 to 2 keep their names.)
 template <int kScan>
 __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const float *__restrict__ rays, uint32_t n,
                                                        float *__restrict__ out_rays, uint32_t *__restrict__ out_status,
                                                        uint32_t *__restrict__ out_segments, const float *weight_in,
                                                        float *out_weight, const uint8_t *__restrict__ channel,
-                                                       const float *__restrict__ ri_table, uint32_t nchan) {
-  constexpr bool kPower = kScan != 0, kSpectral = kScan == 2;
+                                                       const float *__restrict__ ri_table, uint32_t nchan,
+                                                       uint32_t *__restrict__ out_bounces, uint32_t max_bounces) {
+  constexpr bool kPower = kScan != 0, kSpectral = kScan >= 2, kTir = kScan == 3;
   uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   f3 s, d;
@@ -2454,14 +2576,15 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
   uint32_t ch = 0u;
   bool in_table = true;
   if constexpr (kSpectral) {
-    ch = channel[i];
+    ch = (kTir && !channel) ? 0u : channel[i];
     in_table = ch < nchan;
     if (!in_table) ch = 0u;
   }
-  uint32_t st = BZR_RR_NONE, seg = 0;
+  uint32_t st = BZR_RR_NONE, seg = 0, bounces = 0;
   bool alive = true;
   for (uint32_t l = 0; l < lenses.count && alive; ++l) {
-    for (uint32_t j = 0; j < 2u && alive; ++j) {
+    // kTir: j counts the lens's segments -- INSIDE, then OUTSIDE while the ray reflects (the last may not)
+    for (uint32_t j = 0; j < (kTir ? max_bounces + 2u : 2u) && alive; ++j) {
       f3 os, od;
       uint32_t patch;
       ++seg;
@@ -2469,9 +2592,22 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
       float gain = 1.0f;
       float ri = lenses.lens[l].ri;
       if constexpr (kSpectral) ri = ri_table[l * nchan + ch];
-      st = refract_hit_t<kPower>(h, ri, s, d, j == 0 ? BZR_RR_INSIDE : BZR_RR_OUTSIDE, os, od, gain);
+      if constexpr (kTir)
+        st = tir_hit_t<true>(h, ri, s, d, j == 0 ? BZR_RR_INSIDE : BZR_RR_OUTSIDE, in_table && j <= max_bounces, os, od, gain);
+      else
+        st = refract_hit_t<kPower>(h, ri, s, d, j == 0 ? BZR_RR_INSIDE : BZR_RR_OUTSIDE, os, od, gain);
       if constexpr (kSpectral)
         if (!in_table) st = BZR_RR_NONE;
+      if constexpr (kTir) {
+        if (st == kReflected) {  // inside still: the same lens again, the weight as it is
+          s = os;
+          d = od;
+          ++bounces;
+          st = BZR_RR_INSIDE;
+          continue;
+        }
+        if (j != 0u) j = max_bounces + 2u;  // refracted out, or lost: this lens is done
+      }
       if (st == BZR_RR_NONE) {
         alive = false;
       } else {
@@ -2485,6 +2621,8 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
   out_status[i] = st;
   if (out_segments) out_segments[i] = seg;
   if constexpr (kPower) out_weight[i] = wgt;
+  if constexpr (kTir)
+    if (out_bounces) out_bounces[i] = bounces;
 }
 
 template <bool kFast>
@@ -3423,20 +3561,24 @@ extern "C" bzr_status bzr_refract(bzr_ctx *ctx, const bzr_mesh *mesh, float ri, 
 
 // bzr_trace_chain (kModeStage) and bzr_trace_chain_power (kModePower: + weight_in, may be null, and out_weight,
 // plain [n] rows in either ray layout); bzr_trace_chain_spectral (kModeSpectral: kModePower with `ri` the index
-// table [nlens][nchan] and `channel` one byte per ray, a plain [n] row, host or device memory as the rays).
+// table [nlens][nchan] and `channel` one byte per ray, a plain [n] row, host or device memory as the rays);
+// bzr_trace_chain_tir (kModeTir: kModeSpectral with a null `channel` allowed, + max_bounces and out_bounces, an
+// optional plain [n] row).  The staged kModeTir chain keeps one more word per ray, the pending row, in the scratch.
 template <int kMode>
 static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
                               const float *rays, const float *weight_in, uint32_t n, float *out_rays, float *out_weight,
                               uint32_t *out_status, uint32_t *out_segments, uint32_t flags,
-                              const uint8_t *channel = nullptr, uint32_t nchan = 0) {
-  constexpr bool kPower = has_power(kMode), kSpectral = kMode == kModeSpectral;
+                              const uint8_t *channel = nullptr, uint32_t nchan = 0, uint32_t max_bounces = 0,
+                              uint32_t *out_bounces = nullptr) {
+  constexpr bool kPower = has_power(kMode), kSpectral = has_channels(kMode), kTir = kMode == kModeTir;
   if (bzr_status s = check_flags(flags, true)) return s;
   if (!ctx) return set_error(BZR_ERR_INVALID_ARGUMENT, "null context");
   if (nlens == 0 || nlens > kMaxLenses) return set_error(BZR_ERR_INVALID_ARGUMENT, "nlens must be 1..8");
   if (kSpectral) {
     if (bzr_status s = check_channels(ri, nchan)) return s;
-    if (!channel) return set_error(BZR_ERR_INVALID_ARGUMENT, "null channel row");
+    if (!kTir && !channel) return set_error(BZR_ERR_INVALID_ARGUMENT, "null channel row");
     if (!out_weight) return set_error(BZR_ERR_INVALID_ARGUMENT, "null out_weight");
+    if (max_bounces > BZR_MAX_BOUNCES) return set_error(BZR_ERR_INVALID_ARGUMENT, "max_bounces must be 0..8");
   }
   if (!lenses || !ri) return set_error(BZR_ERR_INVALID_ARGUMENT, "null lens list");
   LensSet set{};
@@ -3451,7 +3593,7 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
   DeviceGuard g(ctx->device);
   const float *d_rays = rays;
   float *d_out = out_rays;
-  uint32_t *d_st = out_status, *d_seg = out_segments;
+  uint32_t *d_st = out_status, *d_seg = out_segments, *d_bnc = out_bounces, *d_pend = nullptr;
   const float *d_win = weight_in;
   float *d_w = out_weight;
   const uint8_t *d_ch = channel;
@@ -3459,38 +3601,46 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
   if (kSpectral)
     if (bzr_status s = upload_ri_table(ctx, ri, nlens, nchan)) return s;
   float *tmp = nullptr;  // host + AoS: the records on the device, in and out
-  if (host || aos) {
+  // kModeTir: the staged chain's pending row (one word per ray) and a host caller's bounce row, behind the rest
+  const bool staged = !use_scan(flags) && use_staged(flags, n, max_patches(set));
+  const size_t tir_rows = kTir ? (staged ? 1 : 0) + (host && out_bounces ? 1 : 0) : 0;
+  if (host || aos || tir_rows) {
     size_t rb = (size_t)n * 24, ib = (size_t)n * 4;
     if (bzr_status s = ensure_buffer(ctx->scratch, ctx->scratch_bytes,
-                                     2 * round256(rb) + (host ? (kPower ? 3 : 2) * round256(ib) : 0) +
-                                         (host && aos ? round256(rb) : 0) + (host && kSpectral ? round256(n) : 0)))
+                                     (host || aos ? 2 * round256(rb) : 0) + (host ? (kPower ? 3 : 2) * round256(ib) : 0) +
+                                         (host && aos ? round256(rb) : 0) + (host && channel ? round256(n) : 0) +
+                                         tir_rows * round256(ib)))
       return s;
     Staging st{static_cast<char *>(ctx->scratch)};
-    float *r = st.take<float>((size_t)n * 6);
-    d_out = st.take<float>((size_t)n * 6);
-    if (host) {
-      d_st = st.take<uint32_t>(n);
-      d_seg = st.take<uint32_t>(n);
-      if (kPower) {
-        d_w = st.take<float>(n);
-        if (weight_in) BZR_HIP(hipMemcpyAsync(d_w, weight_in, ib, hipMemcpyHostToDevice, ctx->stream));
-        d_win = weight_in ? d_w : nullptr;
+    if (host || aos) {
+      float *r = st.take<float>((size_t)n * 6);
+      d_out = st.take<float>((size_t)n * 6);
+      if (host) {
+        d_st = st.take<uint32_t>(n);
+        d_seg = st.take<uint32_t>(n);
+        if (kPower) {
+          d_w = st.take<float>(n);
+          if (weight_in) BZR_HIP(hipMemcpyAsync(d_w, weight_in, ib, hipMemcpyHostToDevice, ctx->stream));
+          d_win = weight_in ? d_w : nullptr;
+        }
+        if (kSpectral && channel) {
+          uint8_t *c = st.take<uint8_t>(n);
+          BZR_HIP(hipMemcpyAsync(c, channel, n, hipMemcpyHostToDevice, ctx->stream));
+          d_ch = c;
+        }
       }
-      if (kSpectral) {
-        uint8_t *c = st.take<uint8_t>(n);
-        BZR_HIP(hipMemcpyAsync(c, channel, n, hipMemcpyHostToDevice, ctx->stream));
-        d_ch = c;
-      }
+      if (host && aos) tmp = st.take<float>((size_t)n * 6);
+      if (bzr_status s = rays_in(ctx, rays, r, n, host, aos, tmp)) return s;
+      d_rays = r;
     }
-    if (host && aos) tmp = st.take<float>((size_t)n * 6);
-    if (bzr_status s = rays_in(ctx, rays, r, n, host, aos, tmp)) return s;
-    d_rays = r;
+    if (kTir && staged) d_pend = st.take<uint32_t>(n);
+    if (kTir && host && out_bounces) d_bnc = st.take<uint32_t>(n);
   }
   if (use_scan(flags)) {
-    launch(ctx, BZR_KERNEL_CHAIN_SCAN, k_chain_scan<kSpectral ? 2 : (kPower ? 1 : 0)>, dim3(grid_for(n)), set, d_rays, n, d_out,
-           d_st, d_seg, d_win, d_w, d_ch, (const float *)ctx->ri_table, nchan);
+    launch(ctx, BZR_KERNEL_CHAIN_SCAN, k_chain_scan<kTir ? 3 : (kSpectral ? 2 : (kPower ? 1 : 0))>, dim3(grid_for(n)), set,
+           d_rays, n, d_out, d_st, d_seg, d_win, d_w, d_ch, (const float *)ctx->ri_table, nchan, d_bnc, max_bounces);
     BZR_HIP(hipGetLastError());
-  } else if (!use_staged(flags, n, max_patches(set))) {
+  } else if (!staged) {
     TraceJob job{};
     job.rays = d_rays;
     job.out_rays = d_out;
@@ -3502,6 +3652,8 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     job.channel = d_ch;
     job.ri_table = ctx->ri_table;
     job.nchan = nchan;
+    job.bounces = d_bnc;
+    job.max_bounces = max_bounces;
     if (bzr_status s = run_fused<kMode>(ctx, set, job, flags)) return s;
   } else {
     // stage by stage: out_rays holds the rays in flight, out_status != NONE marks them alive
@@ -3515,10 +3667,17 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     for (uint32_t off = 0; off < n; off += ch) {
       const uint32_t m = std::min(ch, n - off);
       for (uint32_t l = 0; l < nlens; ++l) {
-        for (uint32_t j = 0; j < 2; ++j) {
+        // kModeTir: per lens the INSIDE stage, then 1 + max_bounces OUTSIDE stages -- the first over the rays whose
+        // status is not NONE, each later one over the rays the stage before it reflected (the pending row); the last
+        // may not reflect.  The stages are queued whether or not a ray is pending (no read-back decides it).
+        for (uint32_t j = 0; j < (kTir ? 2 + max_bounces : 2); ++j) {
           Out o{};
           o.rays = d_out;
           o.expected_all = j == 0 ? uint32_t(BZR_RR_INSIDE) : uint32_t(BZR_RR_OUTSIDE);
+          o.pend = d_pend;
+          o.bounces = d_bnc;
+          o.bounce_stage = (kTir && j >= 2) ? 1u : 0u;
+          o.may_reflect = (kTir && j >= 1 && j <= max_bounces) ? 1u : 0u;
           o.status = d_st;
           o.segments = d_seg;
           o.ri = set.lens[l].ri;
@@ -3529,7 +3688,7 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
           o.ri_row = kSpectral ? ctx->ri_table + (size_t)l * nchan : nullptr;
           o.nchan = nchan;
           if (bzr_status s = run_segment<kMode>(use_fast(flags), ctx, set.lens[l], o.first ? d_rays : d_out, n, off,
-                                                     m, o.first ? nullptr : d_st, o, w))
+                                                     m, o.first ? nullptr : (o.bounce_stage ? d_pend : d_st), o, w))
             return s;
         }
       }
@@ -3542,6 +3701,8 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     if (out_segments)
       BZR_HIP(hipMemcpyAsync(out_segments, d_seg, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (kPower) BZR_HIP(hipMemcpyAsync(out_weight, d_w, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (kTir && out_bounces)
+      BZR_HIP(hipMemcpyAsync(out_bounces, d_bnc, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     BZR_HIP(hipStreamSynchronize(ctx->stream));
   }
   return BZR_OK;
@@ -3567,6 +3728,15 @@ extern "C" bzr_status bzr_trace_chain_spectral(bzr_ctx *ctx, const bzr_mesh *con
                                                uint32_t *out_status, uint32_t *out_segments, uint32_t flags) {
   return trace_chain<kModeSpectral>(ctx, lenses, ri_table, nlens, rays, weight_in, n, out_rays, out_weight, out_status,
                                     out_segments, flags, channel, nchan);
+}
+
+extern "C" bzr_status bzr_trace_chain_tir(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                          uint32_t nlens, uint32_t nchan, const float *rays, const uint8_t *channel,
+                                          const float *weight_in, uint32_t n, uint32_t max_bounces, float *out_rays,
+                                          float *out_weight, uint32_t *out_status, uint32_t *out_segments,
+                                          uint32_t *out_bounces, uint32_t flags) {
+  return trace_chain<kModeTir>(ctx, lenses, ri_table, nlens, rays, weight_in, n, out_rays, out_weight, out_status,
+                               out_segments, flags, channel, nchan, max_bounces, out_bounces);
 }
 
 // ------------------------------------------------------------ test hook: normalized()

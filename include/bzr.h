@@ -266,6 +266,35 @@ bzr_status bzr_trace_chain_spectral(bzr_ctx *ctx, const bzr_mesh *const *lenses,
                                     uint32_t nchan, const float *rays_soa, const uint8_t *channel,
                                     const float *weight_in, uint32_t n, float *out_rays_soa, float *out_weight,
                                     uint32_t *out_status, uint32_t *out_segments, uint32_t flags);
+/* ---- total internal reflection ----
+ * bzr_trace_chain_spectral with reflections: a ray that cannot leave a lens is mirrored inside it and traced against
+ * the same lens again, until it leaves or has reflected max_bounces times in that lens (max_bounces <=
+ * BZR_MAX_BOUNCES).  In a refract(OUTSIDE) segment whose winning hit has cs >= 0, for a ray whose channel is in the
+ * table, with s2 = ri^2 (1 - cs^2) as Snell's step has it:
+ *   s2 < 0.99        the ray refracts out of the lens, with the Fresnel gain (bzr_trace_chain_power);
+ *   0.99 <= s2 < 1   NONE, as in every other chain: the reference's grazing limit (T is near 0 there anyway);
+ *   s2 >= 1          total internal reflection, if the ray has reflected fewer than max_bounces times in this lens:
+ *                      k = 2 cs   r = d - normal k (per component: one multiply, one subtract)
+ *                      direction = r / sqrt(r.r) (r.r = r0 r0 + (r1 r1 + r2 r2); r itself if r.r is not > 0)
+ *                      origin = the hit's point
+ *                    in IEEE binary32 without contraction, under BZR_MODE_FAST too (it belongs to Snell's step).  The
+ *                    weight is not touched, the ray stays inside and meets the same lens again with expected OUTSIDE.
+ *                    With the lens's budget spent it is NONE: ray and weight stay as the last reflection left them.
+ * A NaN s2 is NONE, and a refract(INSIDE) segment never reflects.  out_status is OUTSIDE or NONE as before; out_rays is
+ * the ray after its last successful refraction or reflection; out_segments counts every BezierMesh::intersect made for
+ * the ray, bounce segments included (at most nlens (2 + max_bounces)); out_bounces [n] (may be NULL, a plain row like
+ * out_segments) is the ray's reflections summed over the lenses.  channel may be NULL: every ray is channel 0 (with
+ * nchan = 1 the single-index form).  With max_bounces = 0 every output is bzr_trace_chain_spectral's bit for bit and
+ * out_bounces is all zero.  max_bounces above BZR_MAX_BOUNCES returns BZR_ERR_INVALID_ARGUMENT before any output is
+ * touched; everything else -- the table and nlens rules, weight_in NULL or aliasing out_weight, out_weight required,
+ * a channel at or above nchan and a non-finite ray (NONE after one segment, unchanged), flags, BZR_RAYS_AOS, host and
+ * device pointers, the pipeline choice and chunking -- is bzr_trace_chain_spectral's.  The illumination entry
+ * points, the multi-GPU plan and bzr_refract do not reflect. */
+#define BZR_MAX_BOUNCES 8
+bzr_status bzr_trace_chain_tir(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table, uint32_t nlens,
+                               uint32_t nchan, const float *rays_soa, const uint8_t *channel, const float *weight_in,
+                               uint32_t n, uint32_t max_bounces, float *out_rays_soa, float *out_weight,
+                               uint32_t *out_status, uint32_t *out_segments, uint32_t *out_bounces, uint32_t flags);
 /* Refractive index from a dispersion formula, on the host (no context, no device): evaluated in binary64 and
  * rounded once to float.  wavelength_um [n] in micrometres, out_ri [n].
  *   BZR_DISPERSION_CAUCHY     n = A + B / l^2 + C / l^4           coeff = A, B[, C]             ncoeff 2 or 3

@@ -464,6 +464,13 @@ void traceChainPower(std::vector<BezierLens const *> const &lenses, Ray const *r
 void traceChainSpectral(std::vector<BezierLens const *> const &lenses, std::vector<float> const &riTable, Ray const *rays,
                         uint8_t const *channels, float const *weights, std::size_t n, Ray *outRays, float *outWeights,
                         RefractionResult *outStatus, uint32_t *outSegments = nullptr, Context *ctx = nullptr);
+// traceChainSpectral with total internal reflection (bzr_trace_chain_tir): a ray that cannot leave a lens is mirrored
+// inside it and meets the same lens again, up to maxBounces (<= BZR_MAX_BOUNCES) times per lens.  channels may be
+// null (every ray is channel 0); outSegments counts the bounce segments too, outBounces the ray's reflections.
+void traceChainTir(std::vector<BezierLens const *> const &lenses, std::vector<float> const &riTable, Ray const *rays,
+                   uint8_t const *channels, float const *weights, std::size_t n, uint32_t maxBounces, Ray *outRays,
+                   float *outWeights, RefractionResult *outStatus, uint32_t *outSegments = nullptr,
+                   uint32_t *outBounces = nullptr, Context *ctx = nullptr);
 // The same chain over several devices from one process (bzr_trace_tiled): tiles of tileRays
 // consecutive rays dealt round-robin to `ctxs` (one per device, distinct), results in input order.
 void traceChainTiled(std::vector<Context *> const &ctxs, std::vector<BezierLens const *> const &lenses,
