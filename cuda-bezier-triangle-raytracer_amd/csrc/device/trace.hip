@@ -75,6 +75,9 @@ struct bzr_mesh {
   float4 *kids_near; // per-lane child records (kids_of), and the near tree's
   float4 *wide;      // two levels per node for k_traverse's bundle walk (wide_of): node i's 16
   float4 *wide_near; // grandchild slots, 2 float4 each as in kids
+  float4 *swide;      // the same records of the trees with split leaf boxes (bvh.hpp build_bvh split), which the
+  float4 *swide_near; // fused refract and chain kernels' bundle walk takes (empty when the mesh is not split)
+  uint32_t split;     // strips per narrow patch in those trees (1: not split)
   float4 *always;   // 8 float4 per always-tested patch (bvh.hpp Bvh::always): planar record with the patch index
                     // in its last word, then the wedge pre-test (always_wedge: w.xyz L H B C 0) and 8 pad words
   uint32_t n_always;
@@ -181,6 +184,9 @@ struct MeshView {
   float s_max;
   float s_near;
   float ri;
+  uint32_t split;                        // > 1: swide's leaves name a slot several times (TraceLds seen)
+  const float4 *__restrict__ swide;      // wide / wide_near of the split trees (the unsplit ones when split == 1)
+  const float4 *__restrict__ swide_near;
 };
 struct LensSet {
   MeshView lens[kMaxLenses];
@@ -808,10 +814,14 @@ __device__ __forceinline__ bool bundle_box(const float *B, float4 lo, float4 hi)
 // child (those subtrees are dropped: the caller sends its active lanes to the full scan).
 // kSlots = 16: the same over the two-level records `wide` (4 nodes per batch, lane 16 q + s taking slot s of
 // node q), so a batch descends two levels of the tree.
+// seen (uniform; null for a tree without split leaf boxes): the wave-segment's bit set over leaf slots.  A split
+// tree names a slot once per cell box, and a bundle that straddles cells reaches it more than once: a hit leaf is
+// queued only if its bit was clear (LDS atomic or with return, so of two lanes of one batch naming the same slot
+// exactly one keeps it).  Slots are below kSplitSlotCap (build_bvh splits no larger mesh).
 template <int kCap, uint32_t kSlots = 4>
 __device__ __forceinline__ uint32_t bundle_batch(const float4 *kids, uint32_t *stk, int &sp, uint32_t *pend,
                                                  const float *B, uint32_t lane, bool &full, uint32_t &knodes,
-                                                 uint32_t base = 0u) {
+                                                 uint32_t base = 0u, uint32_t *seen = nullptr) {
   // (the lane index laundered: lane-derived addresses hoisted out of the walk stayed live across the Newton
   // passes of k_trace and cost it a wave of occupancy)
   asm volatile("" : "+v"(lane));
@@ -831,7 +841,12 @@ __device__ __forceinline__ uint32_t bundle_batch(const float4 *kids, uint32_t *s
   const uint32_t ref = __float_as_uint(lo.w);
   const bool hit = slot && ref != bzr_host::kEmptyChild && bundle_box(B, lo, hi);
   const bool isleaf = (ref & bzr_host::kLeafFlag) != 0u;
-  const unsigned long long lm = __ballot(hit && isleaf), im = __ballot(hit && !isleaf);
+  bool fresh = hit && isleaf;
+  if (seen) {
+    const uint32_t sl = ref & ~bzr_host::kLeafFlag, bit = 1u << (sl & 31u);
+    if (fresh && sl < bzr_host::kSplitSlotCap) fresh = (atomicOr(&seen[sl >> 5], bit) & bit) == 0u;
+  }
+  const unsigned long long lm = __ballot(fresh), im = __ballot(hit && !isleaf);
   knodes = k;
   sp -= (int)k;
   const int below = (int)lanes_below(im);
@@ -839,7 +854,7 @@ __device__ __forceinline__ uint32_t bundle_batch(const float4 *kids, uint32_t *s
   const int ni = (int)popc64_(im);
   full = sp + ni > kCap;
   sp = full ? kCap : sp + ni;
-  if (hit && isleaf) pend[base + lanes_below(lm)] = ref & ~bzr_host::kLeafFlag;
+  if (fresh) pend[base + lanes_below(lm)] = ref & ~bzr_host::kLeafFlag;
   return popc64_(lm);
 }
 // Interval of n.x over x in [lo, hi] (n fixed).
@@ -1768,8 +1783,21 @@ struct TraceKeep<kModeTir> {
   uint32_t count[64];
   float weight[64];
 };
+// The bundle walk's set of leaf slots already queued in this wave-segment (bundle_batch `seen`), one bit per
+// slot: the refract and chain kernels walk the trees with split leaf boxes (MeshView swide).  The intersect
+// kernel's 6.7 KB per wave leave no room for it (24 waves x 7.7 KB > 160 KB), and the power, spectral and TIR
+// kernels sit at their 80-VGPR budget, where the set's few instructions in the walk cost them 12 to 44 bytes of
+// scratch per lane: those four walk the unsplit tree.
 template <int kMode>
-struct TraceLds : TraceKeep<kMode> {  // per wave
+constexpr bool kSplitWalk = BZR_TRACE_BUNDLE && BZR_TRACE_WIDE && (kMode == kModeRefract || kMode == kModeStage);
+template <bool kOn>
+struct TraceSeen {};
+template <>
+struct TraceSeen<true> {
+  alignas(16) uint32_t seen[bzr_host::kSplitSlotCap / 32];
+};
+template <int kMode>
+struct TraceLds : TraceKeep<kMode>, TraceSeen<kSplitWalk<kMode>> {  // per wave
   uint32_t stack[TraceWords<kMode>::kStackCap];
   float hit[TraceWords<kMode>::kHit][64];    // the lane's current winner (written only when it improves)
   unsigned long long emask[kEntries];        // collected leaves: gate ballot
@@ -1953,6 +1981,10 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
   bool narrow = false;  // else every node is tested per lane (the oriented-box nodes always are)
   if (next != kNo) {
     narrow = bundle_setup_dpp(act, s, d, L.bundle, lane) <= kBundleSpread;
+    if constexpr (kSplitWalk<kMode>) {  // a narrow wave walks the split tree: no slot queued yet
+      static_assert(sizeof(L.seen) == 64 * sizeof(uint4), "one uint4 per lane clears the slot set");
+      if (narrow && m.split > 1u) reinterpret_cast<uint4 *>(L.seen)[lane] = make_uint4(0u, 0u, 0u, 0u);
+    }
     if (lane == 0u) L.stack[0] = 0u;
     sp = 1;
     next = kNo;
@@ -2020,7 +2052,13 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
       bool full;
       uint32_t k;
 #if BZR_TRACE_WIDE
-      npend = bundle_batch<kCap, 16>(near_tier ? m.wide_near : m.wide, L.stack, sp, L.pend, L.bundle, lane, full, k);
+      // (a wave walks one tree for the whole segment: the split one in batches when it is narrow, else -- no
+      // oriented-box node exists in a split build -- the unsplit one per lane above; both start at node 0)
+      if constexpr (kSplitWalk<kMode>)
+        npend = bundle_batch<kCap, 16>(near_tier ? m.swide_near : m.swide, L.stack, sp, L.pend, L.bundle, lane, full, k,
+                                       0u, m.split > 1u ? L.seen : nullptr);
+      else
+        npend = bundle_batch<kCap, 16>(near_tier ? m.wide_near : m.wide, L.stack, sp, L.pend, L.bundle, lane, full, k);
 #else
       npend = bundle_batch<kCap>(kids, L.stack, sp, L.pend, L.bundle, lane, full, k);
 #endif
@@ -2659,7 +2697,8 @@ struct DeviceGuard {
 
 MeshView view_of(const bzr_mesh *m, float ri = 1.0f) {
   return MeshView{m->planar, m->full, m->nodes, m->leaf, m->nodes_near, m->leaf_near, m->obb, m->obb_near,
-                  m->always, m->kids, m->kids_near, m->wide, m->wide_near, m->n_always, m->n, m->s_max, m->s_near, ri};
+                  m->always, m->kids, m->kids_near, m->wide, m->wide_near, m->n_always, m->n, m->s_max, m->s_near, ri, m->split,
+                  m->split > 1u ? m->swide : m->wide, m->split > 1u ? m->swide_near : m->wide_near};
 }
 unsigned grid_for(uint32_t n) { return (n + kBlock - 1) / kBlock; }
 size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
@@ -3274,6 +3313,25 @@ extern "C" bzr_status bzr_mesh_create(bzr_ctx *ctx, const void *patches, uint32_
     return k;
   };
   const std::vector<float4> wide = wide_of(bvh), wide_near = wide_of(bvh_near);
+  // the same two tiers with split leaf boxes, for the fused refract and chain kernels' bundle walk: same slots (order,
+  // leaf records, always list), more leaf references
+  std::vector<float4> swide, swide_near;
+  uint32_t split = 1;
+  if (bzr_host::kSplitDefault > 1 && n - bvh.always.size() <= bzr_host::kSplitSlotCap) {
+    try {
+      const bzr_host::Bvh sb = bzr_host::build_bvh(full.data(), n, rec::kWords, bzr_host::kTierFar, bzr_host::kSplitDefault);
+      const bzr_host::Bvh sn = bzr_host::build_bvh(full.data(), n, rec::kWords, bzr_host::kTierNear, bzr_host::kSplitDefault);
+      if (sb.order != bvh.order || sn.order != bvh_near.order || sb.split != sn.split)
+        return set_error(BZR_ERR_INVALID_ARGUMENT, "split BVH disagrees with the unsplit one on the leaf slots");
+      if (sb.split > 1) {
+        swide = wide_of(sb);
+        swide_near = wide_of(sn);
+        split = sb.split;
+      }
+    } catch (std::exception const &e) {
+      return set_error(BZR_ERR_OUT_OF_MEMORY, std::string("BVH build: ") + e.what());
+    }
+  }
   // the always list: the same patches in both tiers (whether a gate region is proven does not depend on
   // the tier's origin radius)
   if (bvh.always != bvh_near.always) return set_error(BZR_ERR_INVALID_ARGUMENT, "BVH tiers disagree on the always list");
@@ -3290,6 +3348,8 @@ extern "C" bzr_status bzr_mesh_create(bzr_ctx *ctx, const void *patches, uint32_
   mesh->n = n;
   mesh->nnodes = static_cast<uint32_t>(bvh.nodes4.size());
   mesh->n_always = static_cast<uint32_t>(bvh.always.size());
+  mesh->split = split;
+  mesh->swide = mesh->swide_near = nullptr;
   mesh->s_max = bvh.s_max;
   mesh->s_near = std::min(bvh_near.s_max, bvh.s_max);
   for (int k = 0; k < 4; ++k) mesh->sphere[k] = bvh.sphere[k];
@@ -3313,6 +3373,8 @@ extern "C" bzr_status bzr_mesh_create(bzr_ctx *ctx, const void *patches, uint32_
       {reinterpret_cast<void **>(&mesh->kids_near), kids_near.data(), kids_near.size() * sizeof(float4)},
       {reinterpret_cast<void **>(&mesh->wide), wide.data(), wide.size() * sizeof(float4)},
       {reinterpret_cast<void **>(&mesh->wide_near), wide_near.data(), wide_near.size() * sizeof(float4)},
+      {reinterpret_cast<void **>(&mesh->swide), swide.data(), swide.size() * sizeof(float4)},
+      {reinterpret_cast<void **>(&mesh->swide_near), swide_near.data(), swide_near.size() * sizeof(float4)},
   };
   hipError_t e = hipSuccess;
   for (auto &u : ups) {
@@ -3346,6 +3408,8 @@ extern "C" bzr_status bzr_mesh_destroy(bzr_mesh *mesh) {
   (void)hipFree(mesh->kids_near);
   (void)hipFree(mesh->wide);
   (void)hipFree(mesh->wide_near);
+  (void)hipFree(mesh->swide);
+  (void)hipFree(mesh->swide_near);
   delete mesh;
   return BZR_OK;
 }

@@ -88,7 +88,78 @@ struct Region {       // the gate region's extreme points (double) and the ray-p
   bool proven = false;     // the region is a proven bound (else: the patch goes to the always list)
   std::vector<d3> pts;
   double pad = 0.0;
+  // what gate_region_box cut the region from (finite proven regions only; split_cells cuts it again):
+  // M's rows, Q = M^-1's columns, the barycentric slack, the unit plane, the slab half-width, an in-plane
+  // frame and the half-side of the square every slab slice is clipped from
+  d3 row[3], q[3], nu, u, v;
+  double slack[3] = {0, 0, 0}, cu = 0.0, eps = 0.0, e = 0.0;
 };
+
+// Extreme points of { x : lo_k <= M_k x <= hi_k } cut by the slab |nu.x - cu| <= eps: the two slab-face
+// slices and the parallelepiped's vertices inside the slab (a convex set: its AABB is theirs).  With a finite
+// cl or ch the set is also cut to cl <= x[axis] <= ch: the faces and vertices above are cut alike, and every
+// other vertex of the cut set lies on a cut plane, so that plane's own slice of the set is added.
+std::vector<d3> slab_slice_points(Region const &r, const double lo[3], const double hi[3], int axis = 0,
+                                  double cl = -HUGE_VAL, double ch = HUGE_VAL) {
+  std::vector<d3> pts;
+  d3 ea{0, 0, 0};
+  ea[axis] = 1.0;
+  const d3 nea{-ea[0], -ea[1], -ea[2]};
+  auto clip_gate = [&](std::vector<d3> poly) {
+    for (int i = 0; i < 3 && !poly.empty(); ++i) {
+      poly = clip(poly, r.row[i], -lo[i]);                                                      // M_i x >= lo
+      if (!poly.empty()) poly = clip(poly, {-r.row[i][0], -r.row[i][1], -r.row[i][2]}, hi[i]);  // <= hi
+    }
+    return poly;
+  };
+  for (double off : {-r.eps, r.eps}) {
+    d3 x0 = {r.nu[0] * (r.cu + off), r.nu[1] * (r.cu + off), r.nu[2] * (r.cu + off)};
+    std::vector<d3> poly = clip_gate({addm(addm(x0, r.u, -r.e), r.v, -r.e), addm(addm(x0, r.u, r.e), r.v, -r.e),
+                                      addm(addm(x0, r.u, r.e), r.v, r.e), addm(addm(x0, r.u, -r.e), r.v, r.e)});
+    if (cl > -HUGE_VAL && !poly.empty()) poly = clip(poly, ea, -cl);
+    if (ch < HUGE_VAL && !poly.empty()) poly = clip(poly, nea, ch);
+    pts.insert(pts.end(), poly.begin(), poly.end());
+  }
+  for (int corner = 0; corner < 8; ++corner) {
+    d3 b;
+    for (int k = 0; k < 3; ++k) b[k] = (corner >> k) & 1 ? hi[k] : lo[k];
+    d3 p{0, 0, 0};
+    for (int k = 0; k < 3; ++k) p = addm(p, r.q[k], b[k]);
+    if (std::fabs(dotd(r.nu, p) - r.cu) <= r.eps && p[axis] >= cl && p[axis] <= ch) pts.push_back(p);
+  }
+  for (double t : {cl, ch}) {
+    if (!std::isfinite(t)) continue;
+    // the cut plane x[axis] = t: a square about (t on the axis) that holds the whole set -- every point of it is
+    // within e / 2 of the origin -- clipped to the gate's parallelepiped and to the slab
+    d3 x0{0, 0, 0}, a1{0, 0, 0}, a2{0, 0, 0};
+    x0[axis] = t;
+    a1[(axis + 1) % 3] = 1.0;
+    a2[(axis + 2) % 3] = 1.0;
+    const double e = 2.0 * r.e;
+    std::vector<d3> poly = clip_gate({addm(addm(x0, a1, -e), a2, -e), addm(addm(x0, a1, e), a2, -e),
+                                      addm(addm(x0, a1, e), a2, e), addm(addm(x0, a1, -e), a2, e)});
+    if (!poly.empty()) poly = clip(poly, r.nu, -(r.cu - r.eps));
+    if (!poly.empty()) poly = clip(poly, {-r.nu[0], -r.nu[1], -r.nu[2]}, r.cu + r.eps);
+    pts.insert(pts.end(), poly.begin(), poly.end());
+  }
+  return pts;
+}
+
+// The float box of a set of region points: padded by the ray-point allowance and rounded outward.
+Box padded_box(std::vector<d3> const &pts, double pad) {
+  d3 lo{HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi{-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+  for (auto const &p : pts)
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = std::min(lo[a], p[a]);
+      hi[a] = std::max(hi[a], p[a]);
+    }
+  Box bx;
+  for (int a = 0; a < 3; ++a) {
+    bx.lo[a] = static_cast<float>(std::nextafter(lo[a] - pad, -HUGE_VAL));
+    bx.hi[a] = static_cast<float>(std::nextafter(hi[a] + pad, HUGE_VAL));
+  }
+  return bx;
+}
 
 Box gate_region_box(const float *rec, double s_max, Region *region = nullptr) {
   d3 n{rec[0], rec[1], rec[2]};
@@ -187,41 +258,21 @@ Box gate_region_box(const float *rec, double s_max, Region *region = nullptr) {
   for (int k = 0; k < 3; ++k)
     slack[k] = kSlack * (std::fabs(row[k][0]) * P[0] + std::fabs(row[k][1]) * P[1] + std::fabs(row[k][2]) * P[2] + 1.0);
   const double eps = kEps * (X + s_max);  // off-plane distance of the float plane point
-  std::vector<d3> pts;
   // the initial square must contain the whole slab slice of the slack-inflated parallelepiped
   double qn = 0.0, smax_slack = std::max({slack[0], slack[1], slack[2]});
   for (int k = 0; k < 3; ++k) qn += normd(q[k]);
-  const double e = 2.0 * (qn * (1.0 + 2.0 * smax_slack) + std::fabs(cu) + eps);
-  for (double off : {-eps, eps}) {
-    d3 x0 = {nu[0] * (cu + off), nu[1] * (cu + off), nu[2] * (cu + off)};
-    std::vector<d3> poly = {addm(addm(x0, u, -e), v, -e), addm(addm(x0, u, e), v, -e),
-                            addm(addm(x0, u, e), v, e), addm(addm(x0, u, -e), v, e)};
-    for (int i = 0; i < 3 && !poly.empty(); ++i) {
-      poly = clip(poly, row[i], slack[i]);                                                   // M_i x >= -slack
-      if (!poly.empty()) poly = clip(poly, {-row[i][0], -row[i][1], -row[i][2]}, 1.0 + slack[i]);  // <= 1+slack
-    }
-    pts.insert(pts.end(), poly.begin(), poly.end());
-  }
-  for (int corner = 0; corner < 8; ++corner) {
-    d3 b;
-    for (int k = 0; k < 3; ++k) b[k] = (corner >> k) & 1 ? 1.0 + slack[k] : -slack[k];
-    d3 p{0, 0, 0};
-    for (int k = 0; k < 3; ++k) p = addm(p, q[k], b[k]);
-    if (std::fabs(dotd(nu, p) - cu) <= eps) pts.push_back(p);
-  }
-  d3 lo{HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi{-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-  bool any = false;
-  for (auto const &p : pts) {
-    any = true;
-    if (region) region->pts.push_back(p);
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = std::min(lo[a], p[a]);
-      hi[a] = std::max(hi[a], p[a]);
-    }
-  }
-  Box bx;
+  Region whole;
+  Region &r = region ? *region : whole;
+  for (int k = 0; k < 3; ++k) r.row[k] = row[k], r.q[k] = q[k], r.slack[k] = slack[k];
+  r.nu = nu, r.u = u, r.v = v, r.cu = cu, r.eps = eps;
+  r.e = 2.0 * (qn * (1.0 + 2.0 * smax_slack) + std::fabs(cu) + eps);
+  const double blo[3] = {-slack[0], -slack[1], -slack[2]}, bhi[3] = {1.0 + slack[0], 1.0 + slack[1], 1.0 + slack[2]};
+  const std::vector<d3> pts = slab_slice_points(r, blo, bhi);
+  const bool any = !pts.empty();
+  if (region) region->pts = pts;
   if (region) region->kind = any ? Region::kFinite : Region::kEmpty;
   if (!any) {  // no point of the slab passes the gate even with slack: never a candidate
+    Box bx;
     bx.lo = {1.0f, 1.0f, 1.0f};
     bx.hi = {0.0f, 0.0f, 0.0f};
     bx.empty = true;
@@ -229,11 +280,43 @@ Box gate_region_box(const float *rec, double s_max, Region *region = nullptr) {
   }
   double pad = kPad * (X + s_max) + 1e-6;  // ray-line distance of the plane point and slab-test rounding
   if (region) region->pad = pad;
-  for (int a = 0; a < 3; ++a) {
-    bx.lo[a] = static_cast<float>(std::nextafter(lo[a] - pad, -HUGE_VAL));
-    bx.hi[a] = static_cast<float>(std::nextafter(hi[a] + pad, HUGE_VAL));
+  return padded_box(pts, pad);
+}
+
+// The gate region of one narrow patch cut into g strips across the longest axis of its box: cell c is the
+// region between the planes x[axis] = lo + (hi - lo) c / g and ... (c + 1) / g, the first and last cell open
+// outward, each boxed exactly as the whole region is (same points, pad and rounding).  The strips tile space,
+// so their slices cover the region: a passing float plane point lies in at least one cell, and the ray through
+// it meets that cell's padded box (the whole box's argument, cell by cell).  A thin oblique triangle fills
+// half of its box at best; the union of g strip boxes tends to the triangle itself (1/2 + 1/(2g) of the box for
+// a right triangle), and strips do not overlap along the axis, so a narrow bundle reaches few cells of one
+// patch.  (Cells along the patch's barycentric axes -- the g^2 sub-triangles of the midpoint subdivision -- have
+// boxes that overlap pairwise and cover (g + 1) / (2g) of the box with g^2 references: measured, 9 of them cut
+// cfg4's leaf fetches as 3 strips do and cost twice the added node visits; DESIGN.md Appendix A.)
+std::vector<Box> split_cells(Region const &r, int g) {
+  d3 lo{HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi{-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+  for (auto const &p : r.pts)
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = std::min(lo[a], p[a]);
+      hi[a] = std::max(hi[a], p[a]);
+    }
+  int axis = 0;
+  for (int a = 1; a < 3; ++a)
+    if (hi[a] - lo[a] > hi[axis] - lo[axis]) axis = a;
+  const double blo[3] = {-r.slack[0], -r.slack[1], -r.slack[2]};
+  const double bhi[3] = {1.0 + r.slack[0], 1.0 + r.slack[1], 1.0 + r.slack[2]};
+  const double w = hi[axis] - lo[axis];
+  std::vector<Box> out;
+  if (!(w > 0.0) || !std::isfinite(w)) {
+    out.push_back(padded_box(r.pts, r.pad));
+    return out;
   }
-  return bx;
+  for (int c = 0; c < g; ++c) {
+    const double cl = c == 0 ? -HUGE_VAL : lo[axis] + w * c / g, ch = c == g - 1 ? HUGE_VAL : lo[axis] + w * (c + 1) / g;
+    const std::vector<d3> pts = slab_slice_points(r, blo, bhi, axis, cl, ch);
+    if (!pts.empty()) out.push_back(padded_box(pts, r.pad));
+  }
+  return out;
 }
 
 #ifndef BZR_BVH_SAH
@@ -688,7 +771,7 @@ void always_wedge(const float *rec, float out[8]) {
 constexpr float kWideRatio = 64.0f;
 constexpr uint32_t kWideMinPatches = 64;
 
-Bvh build_bvh(const float *records, uint32_t n, uint32_t stride_words, int tier) {
+Bvh build_bvh(const float *records, uint32_t n, uint32_t stride_words, int tier, int split) {
   Bvh out;
   std::vector<Box> box(n);
   Builder bld{box, std::vector<std::array<float, 3>>(n), out.order, out.nodes};
@@ -779,7 +862,54 @@ Bvh build_bvh(const float *records, uint32_t n, uint32_t stride_words, int tier)
     ob.region = &region;
     ob.order = &out.order;
     ob.obb = &out.obb;
-    collapse(out.nodes, 0, out.nodes4, ob);
+    // Split leaf boxes (bvh.hpp kSplitDefault): the device tree is collapsed from a second binary tree, built
+    // over one reference per cell of every narrow patch (split_cells) and one per wide patch, in the same
+    // (narrow, wide) shape.  All references of a patch name its one slot, so order, nodes and patch_box are
+    // those of the unsplit build.  Meshes over kSplitSlotCap slots, and builds with oriented boxes, keep one
+    // reference per patch and collapse the unsplit tree itself.
+    int g = split < 1 ? kSplitDefault : split;
+    if (n_tree > kSplitSlotCap || ob.wide_first != 0xFFFFFFFFu) g = 1;
+    out.split = static_cast<uint32_t>(g);
+    if (g > 1) {
+      std::vector<Box> rbox;
+      std::vector<uint32_t> rslot, rorder;
+      uint32_t nref_narrow = 0;
+      for (uint32_t k = 0; k < n_tree; ++k) {
+        const uint32_t p = out.order[k];
+        if (k < n_narrow && region[p].kind == Region::kFinite) {
+          for (Box const &b : split_cells(region[p], g)) rbox.push_back(b), rslot.push_back(k);
+        } else {
+          rbox.push_back(box[p]), rslot.push_back(k);
+        }
+        if (k + 1 == n_narrow) nref_narrow = static_cast<uint32_t>(rbox.size());
+      }
+      const uint32_t nref = static_cast<uint32_t>(rbox.size());
+      std::vector<BvhNode> rnodes;
+      Builder rb{rbox, std::vector<std::array<float, 3>>(nref), rorder, rnodes};
+      for (uint32_t i = 0; i < nref; ++i)
+        for (int a = 0; a < 3; ++a) rb.centre[i][a] = rbox[i].empty ? 0.0f : 0.5f * (rbox[i].lo[a] + rbox[i].hi[a]);
+      rorder.resize(nref);
+      std::iota(rorder.begin(), rorder.end(), 0u);
+      if (nref_narrow > 0 && nref_narrow < nref) {
+        rnodes.push_back({});
+        const uint32_t l = rb.build(0, nref_narrow), r = rb.build(nref_narrow, nref - nref_narrow);
+        BvhNode root;
+        for (int a = 0; a < 3; ++a) {
+          root.lo[a] = std::min(rnodes[l].lo[a], rnodes[r].lo[a]);
+          root.hi[a] = std::max(rnodes[l].hi[a], rnodes[r].hi[a]);
+        }
+        root.a = l;
+        root.b = r;
+        rnodes[0] = root;
+      } else {
+        rb.build(0, nref);
+      }
+      for (BvhNode &nd : rnodes)  // a leaf holds one reference: name its patch's slot
+        if (nd.b & kLeafFlag) nd.a = rslot[rorder[nd.a]];
+      collapse(rnodes, 0, out.nodes4, ob);
+    } else {
+      collapse(out.nodes, 0, out.nodes4, ob);
+    }
     // Exact by construction: every leaf the device can reach holds a patch with a proven gate region.
     std::vector<uint32_t> todo{0u};
     while (!todo.empty()) {
@@ -1162,13 +1292,29 @@ bool bundle_gate_keep_h(const BundleH &b, const float dl[3], const float dh[3], 
 // compared with the per-lane walk of bzr_debug_traverse.  stats: [0] waves, [1] bundle batches, [2] bundle
 // leaves, [3] per-lane node visits, [4] per-lane leaves, [5] per-lane leaves the bundle missed (must be 0),
 // [6] child slots tested, [7] deepest work stack (nodes).  Oriented-box nodes are walked per lane in both.
-extern "C" int32_t bzr_debug_traverse_bundle(const void *patches, uint32_t n, uint32_t stride, const float *rays,
-                                             uint32_t nr, float max_spread, uint64_t stats[12]) {
+// On a split tree (split: build_bvh's argument, < 1 for kSplitDefault) a slot can be reached through several
+// leaf references; [2] and [4] count distinct slots per wave, as the device's per-wave slot set queues them,
+// and three more words follow: [12] leaf references the bundle walk reached, [13] nodes it visited, [14] the
+// tree's leaf references in the near tier, [15] in the far tier.  `slots` (may be null) receives two words per
+// wave: the distinct slots this 4-wide bundle walk queued, and the distinct slots the device's two-level walk
+// queues (trace.hip wide_of: an inner child's box is skipped and its four children are tested in its place, so a
+// superset; 0xFFFFFFFF when the tree has oriented-box nodes) -- what k_trace counts as the wave's leaf fetches.
+extern "C" int32_t bzr_debug_traverse_bundle_split(const void *patches, uint32_t n, uint32_t stride, const float *rays,
+                                                   uint32_t nr, float max_spread, int32_t split, uint64_t stats[16],
+                                                   uint32_t *slots) {
   try {
   if ((!patches && n) || (!rays && nr) || !stats || stride % 4 || stride < 264) return 1;
-  bzr_host::Bvh far = bzr_host::build_bvh(static_cast<const float *>(patches), n, stride / 4, bzr_host::kTierFar);
-  bzr_host::Bvh near = bzr_host::build_bvh(static_cast<const float *>(patches), n, stride / 4, bzr_host::kTierNear);
-  for (int k = 0; k < 12; ++k) stats[k] = 0;
+  bzr_host::Bvh far = bzr_host::build_bvh(static_cast<const float *>(patches), n, stride / 4, bzr_host::kTierFar, split);
+  bzr_host::Bvh near = bzr_host::build_bvh(static_cast<const float *>(patches), n, stride / 4, bzr_host::kTierNear, split);
+  for (int k = 0; k < 16; ++k) stats[k] = 0;
+  for (int t = 0; t < 2; ++t)
+    for (auto const &nd : (t ? far : near).nodes4)
+      for (uint32_t ch : nd.child) stats[14 + t] += ch != bzr_host::kEmptyChild && (ch & bzr_host::kLeafFlag);
+  auto distinct = [](std::vector<uint32_t> &v) {
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+  };
+  if (slots) std::fill(slots, slots + 2 * (size_t)((nr + 63) / 64), 0u);
   for (uint32_t w0 = 0; w0 < nr; w0 += 64) {
     const uint32_t lanes = std::min<uint32_t>(64, nr - w0);
     float s[64][3], d[64][3], inv[64][3];
@@ -1215,6 +1361,7 @@ extern "C" int32_t bzr_debug_traverse_bundle(const void *patches, uint32_t n, ui
         else stack.push_back(child);
       }
     }
+    distinct(lane_leaves);
     stats[4] += lane_leaves.size();
     // bundle walk in batches of up to 16 nodes (or, for a bundle wider than max_spread, the per-lane walk)
     const BundleH b = bundle_h(s, d, active, lanes);
@@ -1222,6 +1369,7 @@ extern "C" int32_t bzr_debug_traverse_bundle(const void *patches, uint32_t n, ui
       stats[8] += 1;
       stats[1] += 0;
       stats[2] += lane_leaves.size();
+      if (slots) slots[2 * (w0 / 64)] = slots[2 * (w0 / 64) + 1] = static_cast<uint32_t>(lane_leaves.size());
       continue;
     }
     std::vector<uint32_t> bundle_leaves, work{0u};
@@ -1231,6 +1379,7 @@ extern "C" int32_t bzr_debug_traverse_bundle(const void *patches, uint32_t n, ui
       std::vector<uint32_t> batch(work.end() - take, work.end());
       work.resize(work.size() - take);
       stats[1] += 1;
+      stats[13] += take;
       stats[7] = std::max<uint64_t>(stats[7], work.size() + take);
       size_t pushed = 0;
       for (uint32_t node : batch) {
@@ -1257,7 +1406,41 @@ extern "C" int32_t bzr_debug_traverse_bundle(const void *patches, uint32_t n, ui
       }
       if (work.size() > 64) stats[9] += 1;  // the device's stack would overflow here
     }
+    stats[12] += bundle_leaves.size();
+    distinct(bundle_leaves);
     stats[2] += bundle_leaves.size();
+    if (slots) {
+      slots[2 * (w0 / 64)] = static_cast<uint32_t>(bundle_leaves.size());
+      std::vector<uint32_t> wl, ws{0u};
+      bool oriented = false;
+      auto box_hit = [&](bzr_host::Bvh4Node const &nd, int c) {
+        const float lo[3] = {nd.lo[0][c], nd.lo[1][c], nd.lo[2][c]}, hi[3] = {nd.hi[0][c], nd.hi[1][c], nd.hi[2][c]};
+        return bundle_box_h(b, lo, hi);
+      };
+      while (!ws.empty() && !oriented) {
+        auto const &nd = bvh.nodes4[ws.back()];
+        ws.pop_back();
+        for (int c = 0; c < 4; ++c) {
+          const uint32_t ch = nd.child[c];
+          if (ch == bzr_host::kEmptyChild) continue;
+          if (ch & bzr_host::kObbFlag) oriented = true;
+          else if (ch & bzr_host::kLeafFlag) {
+            if (box_hit(nd, c)) wl.push_back(ch & ~bzr_host::kLeafFlag);
+          } else {
+            auto const &kid = bvh.nodes4[ch];
+            for (int g = 0; g < 4; ++g) {
+              const uint32_t gc = kid.child[g];
+              if (gc == bzr_host::kEmptyChild || !box_hit(kid, g)) continue;
+              if (gc & bzr_host::kObbFlag) oriented = true;
+              else if (gc & bzr_host::kLeafFlag) wl.push_back(gc & ~bzr_host::kLeafFlag);
+              else ws.push_back(gc);
+            }
+          }
+        }
+      }
+      distinct(wl);
+      slots[2 * (w0 / 64) + 1] = oriented ? 0xFFFFFFFFu : static_cast<uint32_t>(wl.size());
+    }
     // the leaf pre-test: which admitted leaves a bundle-level gate keeps; none whose exact gate some lane
     // passes may be rejected
     float dl[3], dh[3];
@@ -1282,6 +1465,92 @@ extern "C" int32_t bzr_debug_traverse_bundle(const void *patches, uint32_t n, ui
     std::sort(bundle_leaves.begin(), bundle_leaves.end());
     for (uint32_t x : lane_leaves) stats[5] += !std::binary_search(bundle_leaves.begin(), bundle_leaves.end(), x);
   }
+  return 0;
+  } catch (std::exception const &e) {  // build_bvh's invariant checks: a status, not a throw across the C ABI
+    bzr_internal_set_error(e.what());
+    return 2;
+  }
+}
+
+extern "C" int32_t bzr_debug_traverse_bundle(const void *patches, uint32_t n, uint32_t stride, const float *rays,
+                                             uint32_t nr, float max_spread, uint64_t stats[12]) {
+  uint64_t st[16];
+  const int32_t rc = bzr_debug_traverse_bundle_split(patches, n, stride, rays, nr, max_spread, -1, st, nullptr);
+  if (rc == 0 && stats) std::copy(st, st + 12, stats);
+  return rc;
+}
+
+// The device tree's leaf references of one tier built with `split` (build_bvh): per reference the patch it
+// names (mesh order) and its box (lo.xyz, hi.xyz).  count: the number of references; `patch` / `boxes` (null to
+// only count) must hold that many.  Also the order permutation and patch_box (8 floats per slot) when not null.
+extern "C" int32_t bzr_debug_split_boxes(const void *patches, uint32_t n, uint32_t stride, int32_t tier, int32_t split,
+                                         uint32_t *patch, float *boxes, uint32_t *count, uint32_t *order,
+                                         float *patch_box) {
+  try {
+  if ((!patches && n) || !count || stride % 4 || stride < 264) return 1;
+  if (tier != bzr_host::kTierFar && tier != bzr_host::kTierNear) return 1;
+  bzr_host::Bvh bvh = bzr_host::build_bvh(static_cast<const float *>(patches), n, stride / 4, tier, split);
+  uint32_t k = 0;
+  for (auto const &nd : bvh.nodes4)
+    for (int c = 0; c < 4; ++c) {
+      if (nd.child[c] == bzr_host::kEmptyChild || !(nd.child[c] & bzr_host::kLeafFlag)) continue;
+      if (patch && boxes) {
+        patch[k] = bvh.order[nd.child[c] & ~bzr_host::kLeafFlag];
+        for (int a = 0; a < 3; ++a) boxes[(size_t)k * 6 + a] = nd.lo[a][c], boxes[(size_t)k * 6 + 3 + a] = nd.hi[a][c];
+      }
+      ++k;
+    }
+  *count = k;
+  if (order) std::copy(bvh.order.begin(), bvh.order.end(), order);
+  if (patch_box) std::copy(bvh.patch_box.begin(), bvh.patch_box.end(), patch_box);
+  return 0;
+  } catch (std::exception const &e) {  // build_bvh's invariant checks: a status, not a throw across the C ABI
+    bzr_internal_set_error(e.what());
+    return 2;
+  }
+}
+
+// The extreme points of every proven finite gate region of one tier (gate_region_box: the slab-face polygons'
+// vertices and the parallelepiped's vertices inside the slab), in double: count of points, and per point its
+// patch (mesh order) and xyz when `patch` / `pts` are not null (they must hold `count` of a first call).
+extern "C" int32_t bzr_debug_region_points(const void *patches, uint32_t n, uint32_t stride, int32_t tier, uint32_t *patch,
+                                           double *pts, uint32_t *count) {
+  try {
+  if ((!patches && n) || !count || stride % 4 || stride < 264) return 1;
+  if (tier != bzr_host::kTierFar && tier != bzr_host::kTierNear) return 1;
+  const float *rec = static_cast<const float *>(patches);
+  const float s_max = bzr_host::build_bvh(rec, n, stride / 4, tier).s_max;
+  uint32_t k = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    bzr_host::Region r;
+    bzr_host::gate_region_box(rec + (size_t)i * (stride / 4), s_max, &r);
+    if (!r.proven || r.kind != bzr_host::Region::kFinite) continue;
+    for (auto const &p : r.pts) {
+      if (patch && pts) {
+        patch[k] = i;
+        for (int a = 0; a < 3; ++a) pts[(size_t)k * 3 + a] = p[a];
+      }
+      ++k;
+    }
+  }
+  *count = k;
+  return 0;
+  } catch (std::exception const &e) {  // build_bvh's invariant checks: a status, not a throw across the C ABI
+    bzr_internal_set_error(e.what());
+    return 2;
+  }
+}
+
+// The device tree (nodes4) of one tier built with `split`, as bytes: count of nodes, and the nodes when `out` is
+// not null (128 bytes each).
+extern "C" int32_t bzr_debug_nodes4(const void *patches, uint32_t n, uint32_t stride, int32_t tier, int32_t split,
+                                    void *out, uint32_t *count) {
+  try {
+  if ((!patches && n) || !count || stride % 4 || stride < 264) return 1;
+  if (tier != bzr_host::kTierFar && tier != bzr_host::kTierNear) return 1;
+  bzr_host::Bvh bvh = bzr_host::build_bvh(static_cast<const float *>(patches), n, stride / 4, tier, split);
+  *count = static_cast<uint32_t>(bvh.nodes4.size());
+  if (out) std::memcpy(out, bvh.nodes4.data(), bvh.nodes4.size() * sizeof(bzr_host::Bvh4Node));
   return 0;
   } catch (std::exception const &e) {  // build_bvh's invariant checks: a status, not a throw across the C ABI
     bzr_internal_set_error(e.what());

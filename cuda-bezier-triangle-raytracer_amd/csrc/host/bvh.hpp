@@ -63,6 +63,8 @@ struct Bvh {
                                    // H + B|p| + C(|s|+|p|) (inf-norms; bvh.cpp always_wedge): a proven
                                    // pre-test that skips most always-list gates
   std::vector<float> patch_box;    // per order slot: lo.xyz, 0, hi.xyz, 0 (the gate-region box)
+  uint32_t split = 1;              // strips the narrow patches' leaf boxes were cut into (1: one leaf
+                                   // reference per slot; g > 1: up to g, all naming the slot)
   float extent = 0.0f;             // max |coordinate| of any finite box
   float s_max = 0.0f;              // rays with |origin|_inf > s_max take the brute-force path
   float sphere[4] = {0, 0, 0, 0};  // Ritter sphere over the gate-region boxes: centre, radius
@@ -78,6 +80,17 @@ void ritter_sphere(std::vector<Box> const &box, float out[4]);
 // span = the largest |control-point coordinate| of the mesh.
 constexpr int kTierFar = 0, kTierNear = 1;
 // records: n patch records of stride_words floats (bzr_patch layout, 66 words)
-Bvh build_bvh(const float *records, uint32_t n, uint32_t stride_words, int tier = kTierFar);
+// split: strips each narrow patch's gate region is cut into (bvh.cpp split_cells); every strip gets
+// a leaf reference of its own in nodes4, all naming the patch's one slot.  1 (the default): the unsplit tree
+// every per-lane walk, k_traverse and the intersect kernel use; < 1: kSplitDefault, what the fused refract and
+// chain kernels' bundle walk uses (BZR_BVH_SPLIT, A/B knob; 6 measured best of 2..8 on cfg4 and cfg2).  Meshes with more than kSplitSlotCap tree slots are
+// never split (the device's per-wave slot set holds that many bits): Bvh::split tells what was built.
+#ifndef BZR_BVH_SPLIT
+#define BZR_BVH_SPLIT 6
+#endif
+constexpr int kSplitDefault = BZR_BVH_SPLIT;
+constexpr uint32_t kSplitSlotCap = 8192;
+static_assert(kSplitDefault >= 1 && kSplitDefault <= 16, "BZR_BVH_SPLIT: 1..16");
+Bvh build_bvh(const float *records, uint32_t n, uint32_t stride_words, int tier = kTierFar, int split = 1);
 
 }  // namespace bzr_host

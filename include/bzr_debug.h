@@ -47,6 +47,27 @@ int32_t bzr_debug_traverse(const void *patches, uint32_t n, uint32_t stride, con
  * rejected although some lane's exact planar gate passes (0: conservative).  Returns 0 on success. */
 int32_t bzr_debug_traverse_bundle(const void *patches, uint32_t n, uint32_t stride, const float *rays, uint32_t nr,
                                   float max_spread, uint64_t stats[12]);
+/* The same replay on trees built with `split` cells per barycentric axis of each narrow patch's gate region
+ * (bvh.hpp build_bvh; < 1: the split the fused refract and chain kernels walk).  A split tree names a leaf slot once per
+ * cell box: [2] and [4] count distinct slots per wave, as the device's per-wave slot set queues them.  Four more
+ * words: [12] leaf references the bundle walk reached, [13] nodes it visited, [14] / [15] the near / far tree's
+ * leaf references.  slots (optional, two words per wave): the distinct slots this walk queued, and the distinct
+ * slots the device's two-level walk queues (an inner child's own box skipped, its four children tested in its
+ * place: a superset; 0xFFFFFFFF with oriented-box nodes) -- the wave's leaf fetches in k_trace's counters. */
+int32_t bzr_debug_traverse_bundle_split(const void *patches, uint32_t n, uint32_t stride, const float *rays, uint32_t nr,
+                                        float max_spread, int32_t split, uint64_t stats[16], uint32_t *slots);
+/* The leaf references of one tier's device tree built with `split`: count, and per reference the patch it names
+ * (mesh order) and its box (lo xyz, hi xyz) when patch / boxes are not null; also Bvh::order (n words) and
+ * Bvh::patch_box (8 floats per slot) when not null. */
+int32_t bzr_debug_split_boxes(const void *patches, uint32_t n, uint32_t stride, int32_t tier, int32_t split,
+                              uint32_t *patch, float *boxes, uint32_t *count, uint32_t *order, float *patch_box);
+/* The extreme points (double) of every proven finite gate region of one tier: count, and per point its patch
+ * (mesh order) and xyz when patch / pts are not null. */
+int32_t bzr_debug_region_points(const void *patches, uint32_t n, uint32_t stride, int32_t tier, uint32_t *patch,
+                                double *pts, uint32_t *count);
+/* One tier's device tree (128-byte Bvh4Node records) built with `split`: count, and the nodes when out is not null. */
+int32_t bzr_debug_nodes4(const void *patches, uint32_t n, uint32_t stride, int32_t tier, int32_t split, void *out,
+                         uint32_t *count);
 /* Device check of the exact normalized() (Eigen a / sqrt(a.a)): `a` is device memory [3][n], `out` device
  * memory [6][n]: rows 0-2 the product's normalized(a), rows 3-5 the same with the compiler's correctly
  * rounded sqrt and one division per component.  Asynchronous on the context's stream.  ctx is a
