@@ -136,7 +136,7 @@ static_assert(BZR_TRAV_ABLOCK == 0 || BZR_TRAV_ABLOCK == 1, "BZR_TRAV_ABLOCK: 0 
 #endif
 constexpr uint32_t kAblockMin = 64, kAblockMax = 1024, kAblockBlock = BZR_ABLOCK_BLOCK;  // threads per pre-testing block
 constexpr int kTravBlock = 64;
-// Waves whose ray directions spread wider than this (bundle_setup_dpp) take the per-lane walk instead of the
+// Waves whose ray directions spread wider than this (bundle_setup_swap) take the per-lane walk instead of the
 // bundle walk.
 constexpr float kBundleSpread = 0.5f;
 // Slots per node of the wide records (bzr_mesh wide / wide_near: each node's grandchildren): k_traverse's
@@ -692,7 +692,7 @@ __device__ __forceinline__ float wave_maxf(float v) {
 }
 // The 12 reductions one after another (a loop that is not unrolled), each stored to the wave's LDS words as
 // soon as it is done, so only one is in registers at a time; word 12 = 1 when every box bound is finite
-// (false also for an empty bundle, whose boxes are +-inf).  Words 13..21: bundle_setup_dpp.
+// (false also for an empty bundle, whose boxes are +-inf).  Words 13..21: bundle_setup_swap.
 constexpr uint32_t kBundleWords = 22;
 __device__ __forceinline__ void bundle_to_lds(bool act, f3 s, f3 d, float *out, uint32_t lane) {
   const float inf = __builtin_inff();
@@ -710,77 +710,94 @@ __device__ __forceinline__ void bundle_to_lds(bool act, f3 s, f3 d, float *out, 
   if (lane == 0u) out[12] = m <= 1e30f ? 1.0f : 0.0f;
   __builtin_amdgcn_wave_barrier();  // the words are read back by every lane of this wave
 }
-// Wave min / max with DPP row shifts and row broadcasts (no LDS round trips): lane 63 ends with the result,
-// read back as a uniform value.  Lanes shifted in from outside a row contribute the identity.  The floats are
-// reduced as order-preserving integers (sign-magnitude flipped to two's complement): a float fminf / fmaxf
-// step costs a DPP move, two canonicalising v_max and the min (IEEE mode), an integer step is one
-// v_min_i32 / v_max_i32 with the DPP operand folded in.  NaN lanes contribute the identity (as fminf / fmaxf
-// ignore them); -0 orders below +0 (either is a valid bound).
+// Floats reduced as order-preserving integers (sign-magnitude flipped to two's complement): a float fminf / fmaxf
+// step costs a DPP move, two canonicalising v_max and the min (IEEE mode), an integer step is one v_min_i32 with
+// the DPP operand folded in.  NaN lanes contribute the identity (as fminf / fmaxf ignore them); -0 orders below +0
+// (either is a valid bound).  The map is its own inverse.
 __device__ __forceinline__ int float_order(float x) {
   const int b = __float_as_int(x);
   return b ^ ((b >> 31) & 0x7FFFFFFF);
 }
-// The 12 bundle reductions in lockstep (step k of all twelve, then step k + 1): each DPP read is then 12
-// instructions behind the write it reads, so no s_nop hazard padding between the steps.  kMaxMask bit i:
-// value i is reduced by max (else min).
-template <uint32_t kMaxMask>
-__device__ __forceinline__ void wave_reduce12_dpp(const float (&x)[12], float (&out)[12]) {
-  int v[12];
+// The whole bundle, the 12 reductions as one reduce-scatter on gfx950's half-wave swaps (no LDS round trips):
+// words 0..12 as bundle_to_lds, and for the bundle walk 13..21 -- per axis rl = 1 / Dl', rh = 1 / Dh' and mixed = 1
+// when Dl' < 0 < Dh', where Dl' <= Dl and Dh' >= Dh are the direction bounds moved away from zero (|D'| >= 1e-20: a
+// wider direction box, so a superset of the rays).  The words are, bit for bit, those of twelve separate min / max
+// reductions followed by one lane's scalar code (tests/test_gpu_bundle_setup.py holds both statements); the host
+// mirrors (bvh.cpp bundle_box_h, bundle_spread_h) predict the walk from them.
+// One ordered integer per component: max x = -min(-x) and float_order(-x) = ~float_order(x), so all twelve
+// reductions are v_min_i32 -- the maxima as minima of ~order -- and values of either kind share a register.  An
+// inactive lane contributes order(+inf) = ~order(-inf) = 0x7F800000 to both, a NaN lane INT_MAX (= ~INT_MIN) to both.
+// v_permlane32_swap on (min s_k, min d_k) and on (max s_k, max d_k), then min: the low half of a register reduces
+// the origin's bound, the high half the direction's (12 -> 6 registers).  v_permlane16_swap on the (min, max) pairs,
+// then min: register k's rows 0..3 reduce Sl_k, Sh_k, Dl_k, Dh_k -- words k, 3 + k, 6 + k, 9 + k (6 -> 3).  Four
+// row_ror steps leave every lane of a row with the row's result; the rows of maxima (1 and 3) flip the sign back.
+// The row leaders store words 0..11; word 12 is an exponent test on every lane voted into a scalar (fmaxf skips a
+// NaN bound, so only magnitudes in (1e30, inf] clear it); lanes 0..5 then read one direction bound each and write
+// its clamped, correctly rounded reciprocal, lanes 0..2 the mixed flags (lo < 0 iff !(Dl > 1e-20), hi > 0 iff
+// !(Dh < -1e-20): the clamps' own tests).
+__device__ __forceinline__ float bundle_setup_swap(bool act, f3 s, f3 d, float *out, uint32_t lane) {
+  asm volatile("" : "+v"(lane));  // (laundered, as in bundle_batch: no lane-derived constant outlives the setup)
+  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+  const float c[6] = {s.x, s.y, s.z, d.x, d.y, d.z};
+  const int idle = act ? INT_MAX : 0x7F800000;
+  int mn[6], mx[6];
 #pragma unroll
-  for (int i = 0; i < 12; ++i) {
-    const int id = ((kMaxMask >> i) & 1u) ? INT_MIN : INT_MAX;
-    v[i] = x[i] == x[i] ? float_order(x[i]) : id;
+  for (int i = 0; i < 6; ++i) {
+    const bool in = act && c[i] == c[i];
+    const int o = float_order(c[i]);
+    mn[i] = in ? o : idle;
+    mx[i] = in ? ~o : idle;
   }
-#define BZR_DPP_STEP(ctrl, rows)                                                        \
-  _Pragma("unroll") for (int i = 0; i < 12; ++i) {                                     \
-    const bool mx = (kMaxMask >> i) & 1u;                                              \
-    const int o = __builtin_amdgcn_update_dpp(mx ? INT_MIN : INT_MAX, v[i], ctrl, rows, 0xF, false); \
-    v[i] = mx ? max(v[i], o) : min(v[i], o);                                           \
+  // (the steps of the registers side by side: a swap or a DPP read then lies behind the write it reads, and the
+  // hazard recogniser pads nothing)
+  u32x2 p[6];
+  int h[6], w[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    p[k] = __builtin_amdgcn_permlane32_swap((unsigned)mn[k], (unsigned)mn[3 + k], false, false);
+    p[3 + k] = __builtin_amdgcn_permlane32_swap((unsigned)mx[k], (unsigned)mx[3 + k], false, false);
   }
-  BZR_DPP_STEP(0x111, 0xF)  // row_shr:1
-  BZR_DPP_STEP(0x112, 0xF)  // row_shr:2
-  BZR_DPP_STEP(0x114, 0xF)  // row_shr:4
-  BZR_DPP_STEP(0x118, 0xF)  // row_shr:8: lane 15 of each row holds its row's result
-  BZR_DPP_STEP(0x142, 0xA)  // row_bcast:15 into rows 1 and 3
-  BZR_DPP_STEP(0x143, 0xC)  // row_bcast:31 into rows 2 and 3: lane 63 holds the wave's result
-#undef BZR_DPP_STEP
 #pragma unroll
-  for (int i = 0; i < 12; ++i) {
-    const int r = __builtin_amdgcn_readlane(v[i], 63);
-    out[i] = __int_as_float(r ^ ((r >> 31) & 0x7FFFFFFF));  // (the map is its own inverse)
+  for (int k = 0; k < 6; ++k) h[k] = min((int)p[k][0], (int)p[k][1]);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) p[k] = __builtin_amdgcn_permlane16_swap((unsigned)h[k], (unsigned)h[3 + k], false, false);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) w[k] = min((int)p[k][0], (int)p[k][1]);
+#define BZR_ROR_STEP(ctrl)                      \
+  _Pragma("unroll") for (int k = 0; k < 3; ++k) \
+      w[k] = min(w[k], __builtin_amdgcn_update_dpp(INT_MAX, w[k], ctrl, 0xF, 0xF, false));
+  BZR_ROR_STEP(0x128)  // row_ror:8 (every lane has a source: the identity is never read)
+  BZR_ROR_STEP(0x124)  // row_ror:4
+  BZR_ROR_STEP(0x122)  // row_ror:2
+  BZR_ROR_STEP(0x121)  // row_ror:1
+#undef BZR_ROR_STEP
+  const int sign = (int)((lane & 16u) << 27);
+  int b[3];
+  bool huge = false;  // a bound with 1e30 < |x| <= inf (1e30f = 0x7149F2CA)
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    b[k] = (w[k] ^ ((w[k] >> 31) & 0x7FFFFFFF)) ^ sign;
+    huge |= ((uint32_t)(b[k] & 0x7FFFFFFF) - 0x7149F2CBu) <= 0x7F800000u - 0x7149F2CBu;
   }
-}
-// The whole bundle with the 12 reductions side by side in DPP form, written by lane 0: words 0..12 as
-// bundle_to_lds, and for the bundle walk 13..21 -- per axis rl = 1 / Dl', rh = 1 / Dh' and mixed = 1 when
-// Dl' < 0 < Dh', where Dl' <= Dl and Dh' >= Dh are the direction bounds moved away from zero (|D'| >= 1e-20:
-// a wider direction box, so a superset of the rays).
-__device__ __forceinline__ float bundle_setup_dpp(bool act, f3 s, f3 d, float *out, uint32_t lane) {
-  const float inf = __builtin_inff();
-  const float x[12] = {act ? s.x : inf,  act ? s.y : inf,  act ? s.z : inf,  act ? s.x : -inf,
-                       act ? s.y : -inf, act ? s.z : -inf, act ? d.x : inf,  act ? d.y : inf,
-                       act ? d.z : inf,  act ? d.x : -inf, act ? d.y : -inf, act ? d.z : -inf};
-  float r[12];
-  wave_reduce12_dpp<0xE38u>(x, r);  // max: values 3, 4, 5, 9, 10, 11
-  if (lane == 0u) {
-    float m = 0.0f;
+  const bool finite = __ballot(huge) == 0ull;
+  if ((lane & 15u) == 0u) {
+    float *o = out + 3u * (lane >> 4);
 #pragma unroll
-    for (int k = 0; k < 12; ++k) {
-      out[k] = r[k];
-      m = fmaxf(m, fabsf(r[k]));
-    }
-    out[12] = m <= 1e30f ? 1.0f : 0.0f;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float dl = r[6 + a], dh = r[9 + a];
-      const float lo = dl > 1e-20f ? dl : fminf(dl, -1e-20f), hi = dh < -1e-20f ? dh : fmaxf(dh, 1e-20f);
-      out[13 + a] = 1.0f / lo;
-      out[16 + a] = 1.0f / hi;
-      out[19 + a] = (lo < 0.0f && hi > 0.0f) ? 1.0f : 0.0f;
-    }
+    for (int k = 0; k < 3; ++k) o[k] = __int_as_float(b[k]);
+    if (lane == 0u) out[12] = finite ? 1.0f : 0.0f;
   }
   __builtin_amdgcn_wave_barrier();
-  // the walk choice's width measure (uniform): the widest direction interval (bvh.cpp bundle_spread_h)
-  return fmaxf(fmaxf(r[9] - r[6], r[10] - r[7]), r[11] - r[8]);
+  if (lane < 6u) {  // lane a: Dl_a -> rl_a, lane 3 + a: Dh_a -> rh_a
+    const float x = out[6u + lane];
+    const float lo = x > 1e-20f ? x : fminf(x, -1e-20f), hi = x < -1e-20f ? x : fmaxf(x, 1e-20f);
+    out[13u + lane] = 1.0f / (lane < 3u ? lo : hi);
+    if (lane < 3u) out[19u + lane] = (!(x > 1e-20f) && !(out[9u + lane] < -1e-20f)) ? 1.0f : 0.0f;
+  }
+  __builtin_amdgcn_wave_barrier();
+  // the walk choice's width measure: the widest direction interval (bvh.cpp bundle_spread_h), read back from the
+  // words (into a scalar: the walk's control flow hangs on it and must stay uniform)
+  const float spread = fmaxf(fmaxf(out[9] - out[6], out[10] - out[7]), out[11] - out[8]);
+  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(spread)));
 }
 // Wave-bundle box test (the bundle walk): false only when no ray s + t d, t >= 0, with s in [Sl, Sh] and d in
 // [Dl', Dh'] (per axis, so a superset of the wave's active rays) meets the box.  On axis a the reachable
@@ -1043,7 +1060,7 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
   bool bwalk = false;                    // the walk choice (trace_segment's)
   bool narrow = false;                   // else every node is tested per lane (as oriented-box nodes are)
   if (walk) {
-    narrow = bundle_setup_dpp(active, s, d, bl, threadIdx.x & 63u) <= kBundleSpread;
+    narrow = bundle_setup_swap(active, s, d, bl, threadIdx.x & 63u) <= kBundleSpread;
     if ((threadIdx.x & 63u) == 0u) stk[0] = 0u;
     sp = 1;
     next = 0xFFFFFFFFu;
@@ -1054,7 +1071,7 @@ __device__ __forceinline__ void traverse_rays(const MeshView &m, const float *__
   uint32_t nraw = 0;  // leaves queued in raw, not yet pre-tested
   // the always list's block pre-test (every thread of the block gets here: no early exit above)
   if constexpr (kAblock != 0) {
-    if (!walk) bundle_setup_dpp(active, s, d, bl, threadIdx.x & 63u);  // (an empty wave's bundle is the identity)
+    if (!walk) bundle_setup_swap(active, s, d, bl, threadIdx.x & 63u);  // (an empty wave's bundle is the identity)
     __syncthreads();
     if (threadIdx.x < 13u) {  // the union over the block's waves with rays (bl - wave * kBundleWords: wave 0's)
       const float *b0 = bl - (threadIdx.x >> 6) * kBundleWords;
@@ -1980,7 +1997,7 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
   // boxes than its rays do
   bool narrow = false;  // else every node is tested per lane (the oriented-box nodes always are)
   if (next != kNo) {
-    narrow = bundle_setup_dpp(act, s, d, L.bundle, lane) <= kBundleSpread;
+    narrow = bundle_setup_swap(act, s, d, L.bundle, lane) <= kBundleSpread;
     if constexpr (kSplitWalk<kMode>) {  // a narrow wave walks the split tree: no slot queued yet
       static_assert(sizeof(L.seen) == 64 * sizeof(uint4), "one uint4 per lane clears the slot set");
       if (narrow && m.split > 1u) reinterpret_cast<uint4 *>(L.seen)[lane] = make_uint4(0u, 0u, 0u, 0u);
@@ -3836,6 +3853,20 @@ __global__ __launch_bounds__(kBlock) void k_debug_div_heights(const float *__res
   out[(size_t)2 * n + i] = div_rn(hin, ic);
   out[(size_t)3 * n + i] = div_rn(hout, ic);
 }
+// The walk's bundle setup (bundle_setup_swap) on waves of 64 consecutive rays, one wave per block: row w of out =
+// the wave's 22 bundle words and the returned spread.
+__global__ __launch_bounds__(64) void k_debug_bundle_setup(const float *__restrict__ rays,
+                                                           const uint8_t *__restrict__ active, uint32_t n,
+                                                           float *__restrict__ out) {
+  __shared__ float bl[kBundleWords];
+  const uint32_t lane = threadIdx.x, i = blockIdx.x * 64u + lane;  // (i < n: n is a multiple of 64)
+  const f3 s = mk(rays[i], rays[(size_t)n + i], rays[(size_t)2 * n + i]);
+  const f3 d = mk(rays[(size_t)3 * n + i], rays[(size_t)4 * n + i], rays[(size_t)5 * n + i]);
+  const float spread = bundle_setup_swap(active[i] != 0, s, d, bl, lane);
+  float *o = out + (size_t)blockIdx.x * (kBundleWords + 1u);
+  if (lane < kBundleWords) o[lane] = bl[lane];
+  if (lane == kBundleWords) o[lane] = spread;
+}
 // BZR_MODE_FAST's primitives (patch_math.hpp namespace fast): row 0 div_rn(a0, a1), row 1 sqrt_rn(|a0|), rows 2..4
 // normalized(a).
 __global__ __launch_bounds__(kBlock) void k_debug_fast_unit(const float *__restrict__ a, uint32_t n,
@@ -3868,6 +3899,19 @@ extern "C" bzr_status bzr_debug_div_heights(void *ctxp, const float *a, uint32_t
   if (!a || !out) return set_error(BZR_ERR_INVALID_ARGUMENT, "null buffer");
   DeviceGuard g(ctx->device);
   hipLaunchKernelGGL(k_debug_div_heights, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, a, n, out);
+  BZR_HIP(hipGetLastError());
+  return BZR_OK;
+}
+
+extern "C" bzr_status bzr_debug_bundle_setup(void *ctxp, const float *rays, const uint8_t *active, uint32_t n,
+                                             float *out) {
+  bzr_ctx *ctx = static_cast<bzr_ctx *>(ctxp);
+  if (!ctx) return set_error(BZR_ERR_INVALID_ARGUMENT, "null context");
+  if (n == 0) return BZR_OK;
+  if (!rays || !active || !out) return set_error(BZR_ERR_INVALID_ARGUMENT, "null buffer");
+  if (n % 64u) return set_error(BZR_ERR_INVALID_ARGUMENT, "n must be whole waves of 64 rays");
+  DeviceGuard g(ctx->device);
+  hipLaunchKernelGGL(k_debug_bundle_setup, dim3(n / 64u), dim3(64), 0, ctx->stream, rays, active, n, out);
   BZR_HIP(hipGetLastError());
   return BZR_OK;
 }

@@ -77,6 +77,12 @@ int32_t bzr_debug_unit(void *ctx, const float *a, uint32_t n, float *out);
  * reciprocal where proven): `a` device memory [3][n] (hIn, hOut, cos), `out` device memory [4][n]: rows 0-1 the
  * product's quotients, rows 2-3 one correctly rounded division each.  Asynchronous on the context's stream. */
 int32_t bzr_debug_div_heights(void *ctx, const float *a, uint32_t n, float *out);
+/* Device check of the trace kernels' per-segment bundle setup (trace.hip bundle_setup_swap) on waves of 64
+ * consecutive rays: `rays` device memory [6][n] (origin xyz, direction xyz), `active` device memory [n] bytes (0: the
+ * lane is idle), n a multiple of 64, `out` device memory [n / 64][23]: per wave the 22 bundle words (origin box lo,
+ * hi; direction box lo, hi; finite flag; 1 / Dl', 1 / Dh'; mixed flags) and the returned direction spread.
+ * Asynchronous on the context's stream. */
+int32_t bzr_debug_bundle_setup(void *ctx, const float *rays, const uint8_t *active, uint32_t n, float *out);
 /* Device check of BZR_MODE_FAST's primitives (patch_math.hpp namespace fast): `a` device memory [3][n], `out`
  * device memory [5][n]: row 0 fast::div_rn(a0, a1), row 1 fast::sqrt_rn(|a0|), rows 2-4 fast::normalized(a).
  * Asynchronous on the context's stream. */
