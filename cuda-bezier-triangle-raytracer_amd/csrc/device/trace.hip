@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "../host/bvh.hpp"
+#include "../host/staging.hpp"
 #include "bzr.h"
 #include "ctx.hpp"
 #include "patch_math.hpp"
@@ -551,9 +552,9 @@ __device__ __forceinline__ uint32_t t_order(float t) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+__device__ __forceinline__ uint32_t popc64(unsigned long long m) { return (uint32_t)__popcll(m); }
+__device__ __forceinline__ bool lane_bit(unsigned long long m, uint32_t lane) { return ((m >> lane) & 1ull) != 0ull; }
 // Number of lanes below this one in `mask`.
-__device__ __forceinline__ uint32_t popc64_(unsigned long long m) { return (uint32_t)__popcll(m); }
-__device__ __forceinline__ bool lane_bit64(unsigned long long m, uint32_t lane) { return ((m >> lane) & 1ull) != 0ull; }
 __device__ __forceinline__ uint32_t lanes_below(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32),
                                    __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
@@ -868,11 +869,11 @@ __device__ __forceinline__ uint32_t bundle_batch(const float4 *kids, uint32_t *s
   sp -= (int)k;
   const int below = (int)lanes_below(im);
   if (hit && !isleaf && sp + below < kCap) stk[sp + below] = ref;
-  const int ni = (int)popc64_(im);
+  const int ni = (int)popc64(im);
   full = sp + ni > kCap;
   sp = full ? kCap : sp + ni;
   if (fresh) pend[base + lanes_below(lm)] = ref & ~bzr_host::kLeafFlag;
-  return popc64_(lm);
+  return popc64(lm);
 }
 // Interval of n.x over x in [lo, hi] (n fixed).
 __device__ __forceinline__ void ivdot(f3 n, f3 lo, f3 hi, float &a, float &b) {
@@ -1829,12 +1830,10 @@ struct TraceLds : TraceKeep<kMode>, TraceSeen<kSplitWalk<kMode>> {  // per wave
   float park[TraceWords<kMode>::kPark ? TraceWords<kMode>::kPark : 1][64];
 };
 
-__device__ __forceinline__ uint32_t popc64(unsigned long long m) { return (uint32_t)__popcll(m); }
 __device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) {
   const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)), lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
   return ((unsigned long long)hi << 32) | lo;  // (readfirstlane returns int: widen the unsigned halves)
 }
-__device__ __forceinline__ bool lane_bit(unsigned long long m, uint32_t lane) { return ((m >> lane) & 1ull) != 0ull; }
 
 // The lane's candidate `h` from scanned patch `scan` (the hit itself from patch `src`).
 template <int kMode>
@@ -2718,7 +2717,6 @@ MeshView view_of(const bzr_mesh *m, float ri = 1.0f) {
                   m->split > 1u ? m->swide : m->wide, m->split > 1u ? m->swide_near : m->wide_near};
 }
 unsigned grid_for(uint32_t n) { return (n + kBlock - 1) / kBlock; }
-size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
 
 bzr_status ensure_buffer(void *&buf, size_t &have, size_t bytes) {
   if (have >= bytes) return BZR_OK;
@@ -2730,16 +2728,15 @@ bzr_status ensure_buffer(void *&buf, size_t &have, size_t bytes) {
   return BZR_OK;
 }
 
-struct Staging {  // carves device buffers out of a context-owned allocation
-  char *base;
-  size_t off = 0;
-  template <typename T>
-  T *take(size_t count) {
-    T *p = reinterpret_cast<T *>(base + off);
-    off += round256(count * sizeof(T));
-    return p;
-  }
-};
+// A context-owned allocation (`buf`, `have` bytes) grown to what `layout` takes, then carved by it
+// (host/staging.hpp: the layout runs twice, so it is the one statement of what the call stages).
+using bzr_staging::Staging;
+template <typename Layout>
+bzr_status carve_buffer(void *&buf, size_t &have, Layout &&layout) {
+  const bzr_status s =
+      bzr_staging::carve(buf, [&](size_t bytes) { return ensure_buffer(buf, have, bytes); }, layout, bzr_status(-1));
+  return s == -1 ? set_error(BZR_ERR_INVALID_ARGUMENT, "staging layout took different sizes in its two passes") : s;
+}
 
 // The caller's rays into the kernels' rows `r` ([6][n] on the device): copied from host memory and/or
 // transposed from [n][6] records (BZR_RAYS_AOS; a host source lands in `tmp` first).
@@ -2875,20 +2872,10 @@ constexpr uint32_t kResolveBlocks = 1024u;  // k_resolve's block cap for the fol
 
 // Workspace of the culled path for chunks of up to `chunk` rays over meshes of up to `nb` patches.
 using SplitIt = hipcub::TransformInputIterator<unsigned long long, BucketSplit, const uint32_t *>;
-bzr_status ensure_work(bzr_ctx *ctx, uint32_t chunk, uint32_t nb, Work &w) {
-  size_t cub_bytes = 0;
+// The layout: `hist` directly behind `ctr` (run_culled clears both with one memset), the scan's `cub_bytes` last.
+constexpr void work_layout(Staging &st, Work &w, uint32_t chunk, uint32_t nb, size_t cub_bytes) {
   const uint32_t hn = nb;  // histogram slots, one per patch
-  BZR_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, SplitIt(static_cast<const uint32_t *>(nullptr), BucketSplit()),
-                                           static_cast<unsigned long long *>(nullptr), hn + 1, ctx->stream));
   const size_t cap = (size_t)kMaxCand * chunk;
-  const size_t bytes = round256(32) + round256((size_t)(hn + 1) * 4) + round256((size_t)(hn + 1) * 8) + 2 * round256(cap * 4) +
-                       round256((size_t)chunk * 4) + round256((size_t)chunk * 8) + round256(kSlotWords * cap * 4) +
-                       round256((cap + 64 * ((size_t)nb + 1)) * 8) + round256(cap * 4) +
-                       round256((size_t)chunk * 4) + round256(cub_bytes);
-  const size_t had = ctx->work_bytes;
-  if (bzr_status s = ensure_buffer(ctx->work, ctx->work_bytes, bytes)) return s;
-  if (ctx->work_bytes != had) ctx->zero_ctr = nullptr;  // reallocated (possibly at the same address)
-  Staging st{static_cast<char *>(ctx->work)};
   w.ctr = st.take<uint32_t>(8);
   w.hist = st.take<uint32_t>(hn + 1);
   w.offs = st.take<unsigned long long>(hn + 1);
@@ -2903,6 +2890,15 @@ bzr_status ensure_work(bzr_ctx *ctx, uint32_t chunk, uint32_t nb, Work &w) {
   w.cub = st.take<char>(cub_bytes ? cub_bytes : 1);
   w.cub_bytes = cub_bytes;
   w.cap = static_cast<uint32_t>(cap);
+}
+bzr_status ensure_work(bzr_ctx *ctx, uint32_t chunk, uint32_t nb, Work &w) {
+  size_t cub_bytes = 0;
+  BZR_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, SplitIt(static_cast<const uint32_t *>(nullptr), BucketSplit()),
+                                           static_cast<unsigned long long *>(nullptr), nb + 1, ctx->stream));
+  const size_t had = ctx->work_bytes;
+  if (bzr_status s = carve_buffer(ctx->work, ctx->work_bytes, [&](Staging &st) { work_layout(st, w, chunk, nb, cub_bytes); }))
+    return s;
+  if (ctx->work_bytes != had) ctx->zero_ctr = nullptr;  // reallocated (possibly at the same address)
   return BZR_OK;
 }
 
@@ -2912,8 +2908,13 @@ bzr_status ensure_work(bzr_ctx *ctx, uint32_t chunk, uint32_t nb, Work &w) {
 // batch split into equal chunks (rounded to whole waves).  Measured on cfg5 (67M rays): 1M-ray chunks
 // 28.3 ms per frame, 4M 21.4, 8M 20.0, 16M 20.0 -- small chunks leave the kernels short of waves.
 constexpr uint32_t kChunkLog2 = 23, kChunk = 1u << kChunkLog2;
-// what ensure_work takes per ray: per list slot cand, rank, slot, pair and fol; per ray count, key and ovf
-constexpr size_t kWorkBytesPerRay = (size_t)kMaxCand * (4 + 4 + 48 + 8 + 4) + (4 + 8 + 4);
+// what work_layout takes per ray (per list slot cand, rank, slot, pair and fol; per ray count, key and ovf): the
+// growth of the layout over one wave of rays, with the mesh and the scan's bytes held fixed
+constexpr size_t work_bytes(uint32_t chunk) {
+  Work w{};
+  return bzr_staging::measure([&](Staging &st) { work_layout(st, w, chunk, 0, 0); });
+}
+constexpr size_t kWorkBytesPerRay = (work_bytes(128) - work_bytes(64)) / 64;
 static_assert(kChunkLog2 <= 26, "pair records hold a chunk's ray index in 26 bits");
 static_assert((uint64_t)kMaxCand * kChunk + 64ull * (kStagedPatchLimit + 1) < (1ull << 32),
               "32-bit pair indices");
@@ -3102,6 +3103,49 @@ bzr_status run_segment(bool fast, bzr_ctx *ctx, const MeshView &mv, const float 
                        uint32_t n, const uint32_t *alive, const Out &o, Work &w) {
   return fast ? run_culled<kMode, true>(ctx, mv, rays, ld, off, n, alive, o, w)
               : run_culled<kMode, false>(ctx, mv, rays, ld, off, n, alive, o, w);
+}
+
+// The chain of `job` over `set`: one fused launch, or (`staged`) stage by stage in chunks of `ch` rays with the
+// workspace `w` (ensure_work for `ch` and the set's largest mesh): out_rays holds the rays in flight, status != NONE
+// marks them alive, `pend` is kModeTir's pending row [job.ld].  A job without alive_in starts with the chain's first
+// stage, which reads job.rays and writes every ray's ray / status / segments (no copy or fill launches).
+template <int kMode>
+bzr_status run_chain(bzr_ctx *ctx, const LensSet &set, const TraceJob &job, uint32_t flags, bool staged, uint32_t *pend,
+                     uint32_t ch, Work &w) {
+  constexpr bool kTir = kMode == kModeTir;
+  if (!staged) return run_fused<kMode>(ctx, set, job, flags);
+  for (uint32_t off = 0; off < job.n; off += ch) {
+    const uint32_t m = std::min(ch, job.n - off);
+    for (uint32_t l = 0; l < set.count; ++l) {
+      // kModeTir: per lens the INSIDE stage, then 1 + max_bounces OUTSIDE stages -- the first over the rays whose
+      // status is not NONE, each later one over the rays the stage before it reflected (the pending row); the last
+      // may not reflect.  The stages are queued whether or not a ray is pending (no read-back decides it).
+      for (uint32_t j = 0; j < (kTir ? 2 + job.max_bounces : 2); ++j) {
+        Out o{};
+        o.rays = job.out_rays;
+        o.expected_all = j == 0 ? uint32_t(BZR_RR_INSIDE) : uint32_t(BZR_RR_OUTSIDE);
+        o.pend = pend;
+        o.bounces = job.bounces;
+        o.bounce_stage = (kTir && j >= 2) ? 1u : 0u;
+        o.may_reflect = (kTir && j >= 1 && j <= job.max_bounces) ? 1u : 0u;
+        o.status = job.status;
+        o.segments = job.segments;
+        o.ri = set.lens[l].ri;
+        o.first = (l == 0 && j == 0 && !job.alive_in) ? 1u : 0u;
+        o.weight = job.weight;
+        o.weight_in = job.weight_in;
+        o.channel = job.channel;
+        o.ri_row = has_channels(kMode) ? job.ri_table + (size_t)l * job.nchan : nullptr;
+        o.nchan = job.nchan;
+        o.lossless = job.lossless;
+        if (bzr_status s = run_segment<kMode>(use_fast(flags), ctx, set.lens[l], o.first ? job.rays : job.out_rays, job.ld,
+                                              off, m, o.first ? nullptr : (o.bounce_stage ? pend : job.status), o, w))
+          return s;
+      }
+    }
+  }
+  BZR_HIP(hipGetLastError());
+  return BZR_OK;
 }
 
 }  // namespace
@@ -3475,14 +3519,13 @@ extern "C" bzr_status bzr_intersect(bzr_ctx *ctx, const bzr_mesh *mesh, const fl
   float *d_hits = hits;
   const bool host = !(flags & BZR_DEVICE_PTRS), aos = (flags & BZR_RAYS_AOS) != 0;
   if (host || aos) {
-    size_t rb = (size_t)n * 6 * sizeof(float), hb = (size_t)n * 13 * sizeof(float);
-    if (bzr_status s = ensure_buffer(ctx->scratch, ctx->scratch_bytes,
-                                     round256(rb) + (host ? round256(hb) : 0) + (host && aos ? round256(rb) : 0)))
+    float *r = nullptr, *tmp = nullptr;
+    if (bzr_status s = carve_buffer(ctx->scratch, ctx->scratch_bytes, [&](Staging &st) {
+          st.take(r, (size_t)n * 6);
+          if (host) st.take(d_hits, (size_t)n * 13);
+          if (host && aos) st.take(tmp, (size_t)n * 6);
+        }))
       return s;
-    Staging st{static_cast<char *>(ctx->scratch)};
-    float *r = st.take<float>((size_t)n * 6);
-    if (host) d_hits = st.take<float>((size_t)n * 13);
-    float *tmp = host && aos ? st.take<float>((size_t)n * 6) : nullptr;
     if (bzr_status s = rays_in(ctx, rays, r, n, host, aos, tmp)) return s;
     d_rays = r;
   }
@@ -3504,26 +3547,23 @@ extern "C" bzr_status bzr_intersect_records(bzr_ctx *ctx, const bzr_mesh *mesh, 
   const bool host = !(flags & BZR_DEVICE_PTRS), aos = (flags & BZR_RAYS_AOS) != 0;
   // staging: the rays' rows (unless the caller's device rows are used as they are), the hit rows, and for host
   // callers the records and patch words before their copies
-  const size_t rb = (size_t)n * 24, hb = (size_t)n * 52, pb = (size_t)n * 4;
+  const size_t hb = (size_t)n * 52, pb = (size_t)n * 4;
   const bool stage_rays = host || aos;
-  if (bzr_status s = ensure_buffer(ctx->scratch, ctx->scratch_bytes,
-                                   (stage_rays ? round256(rb) : 0) + (host && aos ? round256(rb) : 0) + round256(hb) +
-                                       (host ? round256(hb) + round256(pb) : 0)))
-    return s;
-  Staging st{static_cast<char *>(ctx->scratch)};
   const float *d_rays = rays;
-  if (stage_rays) {
-    float *r = st.take<float>((size_t)n * 6);
-    float *tmp = host && aos ? st.take<float>((size_t)n * 6) : nullptr;
-    if (bzr_status s = rays_in(ctx, rays, r, n, host, aos, tmp)) return s;
-    d_rays = r;
-  }
-  float *d_hits = st.take<float>((size_t)n * 13);
+  float *r = nullptr, *tmp = nullptr, *d_hits = nullptr;
   void *d_rec = records;
   uint32_t *d_patch = patch_index;
-  if (host) {
-    d_rec = st.take<uint32_t>((size_t)n * 13);
-    d_patch = patch_index ? st.take<uint32_t>(n) : nullptr;
+  if (bzr_status s = carve_buffer(ctx->scratch, ctx->scratch_bytes, [&](Staging &st) {
+        if (stage_rays) st.take(r, (size_t)n * 6);
+        if (host && aos) st.take(tmp, (size_t)n * 6);
+        st.take(d_hits, (size_t)n * 13);
+        if (host) d_rec = st.take<uint32_t>((size_t)n * 13);
+        if (host && patch_index) st.take(d_patch, n);
+      }))
+    return s;
+  if (stage_rays) {
+    if (bzr_status s = rays_in(ctx, rays, r, n, host, aos, tmp)) return s;
+    d_rays = r;
   }
   if (bzr_status s = intersect_rows(ctx, mesh, d_rays, n, d_hits, flags)) return s;
   BZR_HIP(bzr_hits_to_records(ctx->stream, d_hits, n, d_rec, d_patch));
@@ -3547,13 +3587,13 @@ extern "C" bzr_status bzr_patch_intersect(bzr_ctx *ctx, const bzr_mesh *mesh, co
   float *d_hits = hits;
   bool host = !(flags & BZR_DEVICE_PTRS);
   if (host) {
-    size_t ib = (size_t)n * 4, rb = (size_t)n * 24, hb = (size_t)n * 52;
-    if (bzr_status s = ensure_buffer(ctx->scratch, ctx->scratch_bytes, 2 * round256(ib) + round256(rb) + round256(hb)))
+    const size_t ib = (size_t)n * 4, rb = (size_t)n * 24;
+    uint32_t *a = nullptr, *b = nullptr;
+    float *r = nullptr;
+    if (bzr_status s = carve_buffer(ctx->scratch, ctx->scratch_bytes, [&](Staging &st) {
+          st.take(a, n), st.take(b, n), st.take(r, (size_t)n * 6), st.take(d_hits, (size_t)n * 13);
+        }))
       return s;
-    Staging st{static_cast<char *>(ctx->scratch)};
-    uint32_t *a = st.take<uint32_t>(n), *b = st.take<uint32_t>(n);
-    float *r = st.take<float>((size_t)n * 6);
-    d_hits = st.take<float>((size_t)n * 13);
     BZR_HIP(hipMemcpyAsync(a, idx, ib, hipMemcpyHostToDevice, ctx->stream));
     BZR_HIP(hipMemcpyAsync(b, limit, ib, hipMemcpyHostToDevice, ctx->stream));
     BZR_HIP(hipMemcpyAsync(r, rays, rb, hipMemcpyHostToDevice, ctx->stream));
@@ -3587,20 +3627,18 @@ extern "C" bzr_status bzr_refract(bzr_ctx *ctx, const bzr_mesh *mesh, float ri, 
   const bool host = !(flags & BZR_DEVICE_PTRS), aos = (flags & BZR_RAYS_AOS) != 0;
   float *tmp = nullptr;  // host + AoS: the records on the device, in and out
   if (host || aos) {
-    size_t rb = (size_t)n * 24, ib = (size_t)n * 4;
-    if (bzr_status s = ensure_buffer(ctx->scratch, ctx->scratch_bytes,
-                                     2 * round256(rb) + (host ? 2 * round256(ib) : 0) + (host && aos ? round256(rb) : 0)))
+    float *r = nullptr;
+    uint32_t *e = nullptr;
+    if (bzr_status s = carve_buffer(ctx->scratch, ctx->scratch_bytes, [&](Staging &st) {
+          st.take(r, (size_t)n * 6), st.take(d_out, (size_t)n * 6);
+          if (host) st.take(e, n), st.take(d_st, n);
+          if (host && aos) st.take(tmp, (size_t)n * 6);
+        }))
       return s;
-    Staging st{static_cast<char *>(ctx->scratch)};
-    float *r = st.take<float>((size_t)n * 6);
-    d_out = st.take<float>((size_t)n * 6);
-    if (host) {
-      uint32_t *e = st.take<uint32_t>(n);
-      d_st = st.take<uint32_t>(n);
-      if (expected) BZR_HIP(hipMemcpyAsync(e, expected, ib, hipMemcpyHostToDevice, ctx->stream));
-      d_exp = expected ? e : nullptr;
+    if (host && expected) {
+      BZR_HIP(hipMemcpyAsync(e, expected, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+      d_exp = e;
     }
-    if (host && aos) tmp = st.take<float>((size_t)n * 6);
     if (bzr_status s = rays_in(ctx, rays, r, n, host, aos, tmp)) return s;
     d_rays = r;
   }
@@ -3681,47 +3719,37 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
   const bool host = !(flags & BZR_DEVICE_PTRS), aos = (flags & BZR_RAYS_AOS) != 0;
   if (kSpectral)
     if (bzr_status s = upload_ri_table(ctx, ri, nlens, nchan)) return s;
-  float *tmp = nullptr;  // host + AoS: the records on the device, in and out
-  // kModeTir: the staged chain's pending row (one word per ray) and a host caller's bounce row, behind the rest
   const bool staged = !use_scan(flags) && use_staged(flags, n, max_patches(set));
-  const size_t tir_rows = kTir ? (staged ? 1 : 0) + (host && out_bounces ? 1 : 0) : 0;
-  if (host || aos || tir_rows) {
-    size_t rb = (size_t)n * 24, ib = (size_t)n * 4;
-    if (bzr_status s = ensure_buffer(ctx->scratch, ctx->scratch_bytes,
-                                     (host || aos ? 2 * round256(rb) : 0) + (host ? (kPower ? 3 : 2) * round256(ib) : 0) +
-                                         (host && aos ? round256(rb) : 0) + (host && channel ? round256(n) : 0) +
-                                         tir_rows * round256(ib)))
-      return s;
-    Staging st{static_cast<char *>(ctx->scratch)};
-    if (host || aos) {
-      float *r = st.take<float>((size_t)n * 6);
-      d_out = st.take<float>((size_t)n * 6);
-      if (host) {
-        d_st = st.take<uint32_t>(n);
-        d_seg = st.take<uint32_t>(n);
-        if (kPower) {
-          d_w = st.take<float>(n);
-          if (weight_in) BZR_HIP(hipMemcpyAsync(d_w, weight_in, ib, hipMemcpyHostToDevice, ctx->stream));
-          d_win = weight_in ? d_w : nullptr;
-        }
-        if (kSpectral && channel) {
-          uint8_t *c = st.take<uint8_t>(n);
-          BZR_HIP(hipMemcpyAsync(c, channel, n, hipMemcpyHostToDevice, ctx->stream));
-          d_ch = c;
-        }
-      }
-      if (host && aos) tmp = st.take<float>((size_t)n * 6);
-      if (bzr_status s = rays_in(ctx, rays, r, n, host, aos, tmp)) return s;
-      d_rays = r;
-    }
-    if (kTir && staged) d_pend = st.take<uint32_t>(n);
-    if (kTir && host && out_bounces) d_bnc = st.take<uint32_t>(n);
+  float *r = nullptr, *tmp = nullptr;  // tmp, host + AoS: the records on the device, in and out
+  uint8_t *c = nullptr;
+  // kModeTir: the staged chain's pending row (one word per ray) and a host caller's bounce row, behind the rest
+  if (bzr_status s = carve_buffer(ctx->scratch, ctx->scratch_bytes, [&](Staging &st) {
+        if (host || aos) st.take(r, (size_t)n * 6), st.take(d_out, (size_t)n * 6);
+        if (host) st.take(d_st, n), st.take(d_seg, n);
+        if (host && kPower) st.take(d_w, n);
+        if (host && kSpectral && channel) st.take(c, n);
+        if (host && aos) st.take(tmp, (size_t)n * 6);
+        if (kTir && staged) st.take(d_pend, n);
+        if (kTir && host && out_bounces) st.take(d_bnc, n);
+      }))
+    return s;
+  if (host && kPower && weight_in) {
+    BZR_HIP(hipMemcpyAsync(d_w, weight_in, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    d_win = d_w;
+  }
+  if (c) {
+    BZR_HIP(hipMemcpyAsync(c, channel, n, hipMemcpyHostToDevice, ctx->stream));
+    d_ch = c;
+  }
+  if (host || aos) {
+    if (bzr_status s = rays_in(ctx, rays, r, n, host, aos, tmp)) return s;
+    d_rays = r;
   }
   if (use_scan(flags)) {
     launch(ctx, BZR_KERNEL_CHAIN_SCAN, k_chain_scan<kTir ? 3 : (kSpectral ? 2 : (kPower ? 1 : 0))>, dim3(grid_for(n)), set,
            d_rays, n, d_out, d_st, d_seg, d_win, d_w, d_ch, (const float *)ctx->ri_table, nchan, d_bnc, max_bounces);
     BZR_HIP(hipGetLastError());
-  } else if (!staged) {
+  } else {
     TraceJob job{};
     job.rays = d_rays;
     job.out_rays = d_out;
@@ -3735,46 +3763,11 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     job.nchan = nchan;
     job.bounces = d_bnc;
     job.max_bounces = max_bounces;
-    if (bzr_status s = run_fused<kMode>(ctx, set, job, flags)) return s;
-  } else {
-    // stage by stage: out_rays holds the rays in flight, out_status != NONE marks them alive
-    uint32_t nb = 0;
-    for (uint32_t l = 0; l < nlens; ++l) nb = std::max(nb, set.lens[l].n);
     Work w;
-    const uint32_t ch = chunk_for(ctx, n);
-    if (bzr_status s = ensure_work(ctx, ch, nb, w)) return s;
-    // the first stage reads the caller's rays and writes every ray's ray / status / segments (no
-    // copy or fill launches); later stages update the rays in flight in place, alive = status != NONE
-    for (uint32_t off = 0; off < n; off += ch) {
-      const uint32_t m = std::min(ch, n - off);
-      for (uint32_t l = 0; l < nlens; ++l) {
-        // kModeTir: per lens the INSIDE stage, then 1 + max_bounces OUTSIDE stages -- the first over the rays whose
-        // status is not NONE, each later one over the rays the stage before it reflected (the pending row); the last
-        // may not reflect.  The stages are queued whether or not a ray is pending (no read-back decides it).
-        for (uint32_t j = 0; j < (kTir ? 2 + max_bounces : 2); ++j) {
-          Out o{};
-          o.rays = d_out;
-          o.expected_all = j == 0 ? uint32_t(BZR_RR_INSIDE) : uint32_t(BZR_RR_OUTSIDE);
-          o.pend = d_pend;
-          o.bounces = d_bnc;
-          o.bounce_stage = (kTir && j >= 2) ? 1u : 0u;
-          o.may_reflect = (kTir && j >= 1 && j <= max_bounces) ? 1u : 0u;
-          o.status = d_st;
-          o.segments = d_seg;
-          o.ri = set.lens[l].ri;
-          o.first = (l == 0 && j == 0) ? 1u : 0u;
-          o.weight = d_w;
-          o.weight_in = d_win;
-          o.channel = d_ch;
-          o.ri_row = kSpectral ? ctx->ri_table + (size_t)l * nchan : nullptr;
-          o.nchan = nchan;
-          if (bzr_status s = run_segment<kMode>(use_fast(flags), ctx, set.lens[l], o.first ? d_rays : d_out, n, off,
-                                                     m, o.first ? nullptr : (o.bounce_stage ? d_pend : d_st), o, w))
-            return s;
-        }
-      }
-    }
-    BZR_HIP(hipGetLastError());
+    const uint32_t ch = staged ? chunk_for(ctx, n) : 0u;
+    if (staged)
+      if (bzr_status s = ensure_work(ctx, ch, max_patches(set), w)) return s;
+    if (bzr_status s = run_chain<kMode>(ctx, set, job, flags, staged, d_pend, ch, w)) return s;
   }
   if (bzr_status s = rays_out(ctx, d_out, out_rays, n, host, aos, tmp)) return s;
   if (host) {
@@ -4000,11 +3993,13 @@ extern "C" bzr_status bzr_mesh_interpolate(bzr_ctx *ctx, const bzr_mesh *mesh, i
   if (bzr_internal_unit_subtriangles(divisor, bary.data()) != K)
     return set_error(BZR_ERR_INVALID_ARGUMENT, "sub-triangle count mismatch");
   const bool host = !(flags & BZR_DEVICE_PTRS);
-  const size_t bb = round256(bary.size() * 4), ob = (size_t)total * 9 * 4;
-  if (bzr_status s = ensure_buffer(ctx->scratch, ctx->scratch_bytes, bb + (host ? round256(ob) : 0))) return s;
-  Staging st{static_cast<char *>(ctx->scratch)};
-  float *d_bary = st.take<float>(bary.size());
-  float *d_out = host ? st.take<float>((size_t)total * 9) : out_xyz;
+  const size_t ob = (size_t)total * 9 * 4;
+  float *d_bary = nullptr, *d_out = out_xyz;
+  if (bzr_status s = carve_buffer(ctx->scratch, ctx->scratch_bytes, [&](Staging &st) {
+        st.take(d_bary, bary.size());
+        if (host) st.take(d_out, (size_t)total * 9);
+      }))
+    return s;
   BZR_HIP(hipMemcpyAsync(d_bary, bary.data(), bary.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(k_tessellate, dim3(static_cast<uint32_t>((total + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                      ctx->stream, mesh->full, mesh->n, d_bary, total, d_out);
@@ -4201,19 +4196,23 @@ bzr_status check_emitter(const bzr_emitter *em) {
   return BZR_OK;
 }
 
-// The belt tables in device memory (carved from `st`), as the kernels' BeltTable.
-bzr_status upload_belts(bzr_ctx *ctx, const bzr_emitter *em, Staging &st, BeltTable &bt, std::vector<float> &cos_lo,
-                        std::vector<uint32_t> &count, std::vector<uint32_t> &first) {
-  if (bzr_status s = belt_tables(em->belts, cos_lo, count, first)) return s;
-  float *c = st.take<float>(em->belts);
-  uint32_t *k = st.take<uint32_t>(em->belts), *f = st.take<uint32_t>(em->belts);
-  BZR_HIP(hipMemcpyAsync(c, cos_lo.data(), em->belts * 4, hipMemcpyHostToDevice, ctx->stream));
-  BZR_HIP(hipMemcpyAsync(k, count.data(), em->belts * 4, hipMemcpyHostToDevice, ctx->stream));
-  BZR_HIP(hipMemcpyAsync(f, first.data(), em->belts * 4, hipMemcpyHostToDevice, ctx->stream));
-  bt = BeltTable{c, k, f, em->belts};
+// The kernels' BeltTable in device memory: its three rows carved from `st`, then filled (the host tables must
+// outlive the copies: the callers synchronise before they return).
+void belt_layout(Staging &st, uint32_t belts, BeltTable &bt) {
+  bt.belts = belts;
+  st.take(bt.cos_lo, belts), st.take(bt.count, belts), st.take(bt.first, belts);
+}
+struct BeltHost {
+  std::vector<float> cos_lo;
+  std::vector<uint32_t> count, first;
+};
+bzr_status upload_belts(bzr_ctx *ctx, const BeltTable &bt, BeltHost &h) {
+  if (bzr_status s = belt_tables(bt.belts, h.cos_lo, h.count, h.first)) return s;
+  BZR_HIP(hipMemcpyAsync(const_cast<float *>(bt.cos_lo), h.cos_lo.data(), bt.belts * 4, hipMemcpyHostToDevice, ctx->stream));
+  BZR_HIP(hipMemcpyAsync(const_cast<uint32_t *>(bt.count), h.count.data(), bt.belts * 4, hipMemcpyHostToDevice, ctx->stream));
+  BZR_HIP(hipMemcpyAsync(const_cast<uint32_t *>(bt.first), h.first.data(), bt.belts * 4, hipMemcpyHostToDevice, ctx->stream));
   return BZR_OK;
 }
-size_t belt_bytes(uint32_t belts) { return 3 * round256((size_t)belts * 4); }
 }  // namespace
 
 extern "C" bzr_status bzr_mesh_bounding_sphere(const bzr_mesh *mesh, float out[4]) {
@@ -4231,16 +4230,17 @@ extern "C" bzr_status bzr_emit(bzr_ctx *ctx, const bzr_emitter *em, uint64_t fir
   DeviceGuard g(ctx->device);
   const bool host = !(flags & BZR_DEVICE_PTRS);
   const size_t rb = (size_t)n * 24, pb = (size_t)n * 4;
-  if (bzr_status s = ensure_buffer(ctx->scratch, ctx->scratch_bytes,
-                                   belt_bytes(em->belts) + (host ? round256(rb) + round256(pb) : 0)))
-    return s;
-  Staging st{static_cast<char *>(ctx->scratch)};
   BeltTable bt;
-  std::vector<float> cos_lo;
-  std::vector<uint32_t> count, firsts;
-  if (bzr_status s = upload_belts(ctx, em, st, bt, cos_lo, count, firsts)) return s;
-  float *d_rays = host ? st.take<float>((size_t)n * 6) : rays_soa;
-  uint32_t *d_patch = host ? (patch_index ? st.take<uint32_t>(n) : nullptr) : patch_index;
+  BeltHost belts;
+  float *d_rays = rays_soa;
+  uint32_t *d_patch = patch_index;
+  if (bzr_status s = carve_buffer(ctx->scratch, ctx->scratch_bytes, [&](Staging &st) {
+        belt_layout(st, em->belts, bt);
+        if (host) st.take(d_rays, (size_t)n * 6);
+        if (host && patch_index) st.take(d_patch, n);
+      }))
+    return s;
+  if (bzr_status s = upload_belts(ctx, bt, belts)) return s;
   hipLaunchKernelGGL(k_emit<0>, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, *em, bt, first, n, n, d_rays, d_patch,
                      (uint32_t *)nullptr, (uint32_t *)nullptr, make_float4(0.0f, 0.0f, 0.0f, 0.0f), (const float4 *)nullptr,
                      0u, (unsigned long long *)nullptr, (float *)nullptr, 0u, (unsigned long long *)nullptr,
@@ -4281,12 +4281,11 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   if (bzr_status s = check_flags(flags)) return s;
   LensSet set{};
   set.count = nlens;
-  uint32_t nb = 0;
   for (uint32_t l = 0; l < nlens; ++l) {
     if (bzr_status s = check_ctx_mesh(ctx, lenses[l])) return s;
     set.lens[l] = view_of(lenses[l], spectral ? 1.0f : ri[l]);
-    nb = std::max(nb, set.lens[l].n);
   }
+  const uint32_t nb = max_patches(set);
   DeviceGuard g(ctx->device);
   if (spectral)
     if (bzr_status s = upload_ri_table(ctx, ri, nlens, nchan)) return s;
@@ -4308,108 +4307,63 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   const size_t maps = cells * NC;  // cells of all the channels' maps
   const bool host = !(flags & BZR_DEVICE_PTRS);
   const uint32_t B = chunk_for(ctx, total_rays);
-  if (bzr_status s = ensure_buffer(ctx->scratch, ctx->scratch_bytes,
-                                   belt_bytes(em->belts) + round256((size_t)B * 24) + 2 * round256((size_t)B * 4) +
-                                       round256(32 * NC) + (host && hist ? round256(maps * 4) : 0) +
-                                       (with_power ? round256((size_t)B * 4) + round256(32 * NC) + (host ? round256(maps * 8) : 0)
-                                                   : 0) +
-                                       (spectral ? round256(B) : 0)))
-    return s;
-  Staging st{static_cast<char *>(ctx->scratch)};
   BeltTable bt;
-  std::vector<float> cos_lo;
-  std::vector<uint32_t> count, firsts;
-  if (bzr_status s = upload_belts(ctx, em, st, bt, cos_lo, count, firsts)) return s;
-  float *d_rays = st.take<float>((size_t)B * 6);
-  uint32_t *d_st = st.take<uint32_t>(B), *d_seg = st.take<uint32_t>(B);
-  unsigned long long *d_stats = st.take<unsigned long long>(4 * NC);
-  uint32_t *d_hist = host && hist ? st.take<uint32_t>(maps) : hist;
+  BeltHost belts;
+  float *d_rays = nullptr, *d_w = nullptr;  // the batch's rays and, with_power, their power
+  uint32_t *d_st = nullptr, *d_seg = nullptr, *d_hist = hist;
+  unsigned long long *d_stats = nullptr, *d_power = nullptr;  // the four counts and, with_power, the four power sums
+  unsigned long long *d_flux = reinterpret_cast<unsigned long long *>(flux);
+  uint8_t *d_ch = nullptr;  // spectral: the batch's channel row
+  if (bzr_status s = carve_buffer(ctx->scratch, ctx->scratch_bytes, [&](Staging &st) {
+        belt_layout(st, em->belts, bt);
+        st.take(d_rays, (size_t)B * 6), st.take(d_st, B), st.take(d_seg, B), st.take(d_stats, 4 * NC);
+        if (host && hist) st.take(d_hist, maps);
+        if (with_power) st.take(d_w, B), st.take(d_power, 4 * NC);
+        if (with_power && host) st.take(d_flux, maps);
+        if (spectral) st.take(d_ch, B);
+      }))
+    return s;
+  if (bzr_status s = upload_belts(ctx, bt, belts)) return s;
   BZR_HIP(hipMemsetAsync(d_stats, 0, 32 * NC, ctx->stream));
   if (host && hist) BZR_HIP(hipMemsetAsync(d_hist, 0, maps * 4, ctx->stream));
-  float *d_w = nullptr;  // the batch's ray power, its four sums and the flux cells
-  unsigned long long *d_power = nullptr, *d_flux = reinterpret_cast<unsigned long long *>(flux);
   if (with_power) {
-    d_w = st.take<float>(B);
-    d_power = st.take<unsigned long long>(4 * NC);
     BZR_HIP(hipMemsetAsync(d_power, 0, 32 * NC, ctx->stream));
-    if (host) {
-      d_flux = st.take<unsigned long long>(maps);
-      BZR_HIP(hipMemsetAsync(d_flux, 0, maps * 8, ctx->stream));
-    }
+    if (host) BZR_HIP(hipMemsetAsync(d_flux, 0, maps * 8, ctx->stream));
   }
-  uint8_t *d_ch = spectral ? st.take<uint8_t>(B) : nullptr;  // the batch's channel row
   Work w;
   const bool staged = use_staged(flags, B, nb);
   if (staged)
     if (bzr_status s = ensure_work(ctx, B, nb, w)) return s;
   const float4 sphere = make_float4(lenses[0]->sphere[0], lenses[0]->sphere[1], lenses[0]->sphere[2],
                                     lenses[0]->sphere[3]);
+  const uint32_t lambert = with_power && rad->emission == BZR_EMISSION_LAMBERT ? 1u : 0u;
+  // the mode, chosen once: the chain's (a lossless surface leaves the weights as emitted: the plain chain; the
+  // spectral chain refracts per channel with a lossless surface too: its run-time flag) and the two kernels'
+  auto *const chain = spectral  ? &run_chain<kModeSpectral>
+                      : fresnel ? &run_chain<kModePower>
+                                : &run_chain<kModeStage>;
+  auto *const emit = spectral ? &k_emit<2> : with_power ? &k_emit<1> : &k_emit<0>;
+  auto *const land = spectral ? &k_land<2> : with_power ? &k_land<1> : &k_land<0>;
   for (uint64_t first = 0; first < total_rays; first += B) {
     const uint32_t m = (uint32_t)std::min<uint64_t>(B, total_rays - first);
-    if (spectral)
-      hipLaunchKernelGGL(k_emit<2>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays,
-                         (uint32_t *)nullptr, d_st, d_seg, sphere, set.lens[0].always, set.lens[0].n_always, d_stats, d_w,
-                         rad->emission == BZR_EMISSION_LAMBERT ? 1u : 0u, d_power, d_ch, nchan);
-    else if (with_power)
-      hipLaunchKernelGGL(k_emit<1>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays,
-                         (uint32_t *)nullptr, d_st, d_seg, sphere, set.lens[0].always, set.lens[0].n_always, d_stats, d_w,
-                         rad->emission == BZR_EMISSION_LAMBERT ? 1u : 0u, d_power, (uint8_t *)nullptr, 0u);
-    else
-      hipLaunchKernelGGL(k_emit<0>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays,
-                         (uint32_t *)nullptr, d_st, d_seg, sphere, set.lens[0].always, set.lens[0].n_always, d_stats,
-                         (float *)nullptr, 0u, (unsigned long long *)nullptr, (uint8_t *)nullptr, 0u);
-    if (!staged) {  // the chain in place over the batch; culled rays (status NONE) are skipped
-      TraceJob job{};
-      job.rays = d_rays;
-      job.out_rays = d_rays;
-      job.status = d_st;
-      job.segments = d_seg;
-      job.alive_in = d_st;
-      job.n = m;
-      job.ld = B;
-      job.weight = d_w;  // (a lossless surface leaves the weights as emitted: the plain chain)
-      job.weight_in = d_w;
-      job.channel = d_ch;  // (the spectral chain refracts per channel with a lossless surface too: its run-time flag)
-      job.ri_table = ctx->ri_table;
-      job.nchan = nchan;
-      job.lossless = fresnel ? 0u : 1u;
-      if (bzr_status s = spectral  ? run_fused<kModeSpectral>(ctx, set, job, flags)
-                         : fresnel ? run_fused<kModePower>(ctx, set, job, flags)
-                                   : run_fused<kModeStage>(ctx, set, job, flags))
-        return s;
-    } else {
-      for (uint32_t l = 0; l < nlens; ++l)
-        for (uint32_t j = 0; j < 2; ++j) {
-          Out o{};
-          o.rays = d_rays;
-          o.expected_all = j == 0 ? uint32_t(BZR_RR_INSIDE) : uint32_t(BZR_RR_OUTSIDE);
-          o.status = d_st;
-          o.segments = d_seg;
-          o.ri = set.lens[l].ri;
-          o.weight = d_w;
-          o.channel = d_ch;
-          o.ri_row = spectral ? ctx->ri_table + (size_t)l * nchan : nullptr;
-          o.nchan = nchan;
-          o.lossless = fresnel ? 0u : 1u;
-          if (bzr_status s = spectral  ? run_segment<kModeSpectral>(use_fast(flags), ctx, set.lens[l], d_rays, B, 0, m, d_st, o, w)
-                             : fresnel ? run_segment<kModePower>(use_fast(flags), ctx, set.lens[l], d_rays, B, 0, m, d_st, o, w)
-                                       : run_segment<kModeStage>(use_fast(flags), ctx, set.lens[l], d_rays, B, 0, m, d_st, o, w))
-            return s;
-        }
-    }
-    if (spectral)
-      hipLaunchKernelGGL(k_land<2>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg,
-                         make_float4(pn.x, pn.y, pn.z, pc), cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats, d_w, d_flux,
-                         d_power, (const uint8_t *)d_ch, (uint32_t)cells);
-    else if (with_power)
-      hipLaunchKernelGGL(k_land<1>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg,
-                         make_float4(pn.x, pn.y, pn.z, pc), cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats, d_w, d_flux,
-                         d_power, (const uint8_t *)nullptr, 0u);
-    else
-      hipLaunchKernelGGL(k_land<0>, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg,
-                         make_float4(pn.x, pn.y, pn.z, pc), cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats,
-                         (const float *)nullptr, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                         (const uint8_t *)nullptr, 0u);
+    hipLaunchKernelGGL(emit, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays,
+                       (uint32_t *)nullptr, d_st, d_seg, sphere, set.lens[0].always, set.lens[0].n_always, d_stats, d_w,
+                       lambert, d_power, d_ch, nchan);
+    TraceJob job{};  // the chain in place over the batch; culled rays (status NONE) are skipped
+    job.rays = job.out_rays = d_rays;
+    job.alive_in = job.status = d_st;
+    job.segments = d_seg;
+    job.n = m;
+    job.ld = B;
+    job.weight_in = job.weight = d_w;
+    job.channel = d_ch;
+    job.ri_table = ctx->ri_table;
+    job.nchan = nchan;
+    job.lossless = fresnel ? 0u : 1u;
+    if (bzr_status s = chain(ctx, set, job, flags, staged, nullptr, B, w)) return s;
+    hipLaunchKernelGGL(land, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg, make_float4(pn.x, pn.y, pn.z, pc),
+                       cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats, d_w, d_flux, d_power, (const uint8_t *)d_ch,
+                       spectral ? (uint32_t)cells : 0u);
     BZR_HIP(hipGetLastError());
   }
   unsigned long long hs[4 * kMaxChannels];
