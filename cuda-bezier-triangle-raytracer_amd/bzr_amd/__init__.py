@@ -96,6 +96,8 @@ _SIGS = {
     "bzr_illuminate": [_P, _P, _P, _U32, _P, ctypes.c_uint64, _P, _P, _P, _U32],
     "bzr_illuminate_power": [_P, _P, _P, _U32, _P, ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _U32],
     "bzr_illuminate_spectral": [_P, _P, _P, _U32, _U32, _P, ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _U32],
+    "bzr_illuminate_tir": [_P, _P, _P, _U32, _U32, _P, ctypes.c_uint64, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P,
+                           _U32],
     "bzr_mesh_bounding_sphere": [_P, _P],
     "bzr_trimesh_create": [ctypes.POINTER(_P)],
     "bzr_trimesh_destroy": [_P],
@@ -129,7 +131,7 @@ _SIGS = {
 }
 # entry points added without an ABI bump: an explicitly chosen earlier build (BZR_LIBRARY) may lack them
 _ADDED = ("bzr_trace_chain_power", "bzr_illuminate_power", "bzr_trace_chain_spectral", "bzr_illuminate_spectral",
-          "bzr_dispersion_index", "bzr_trace_chain_tir")
+          "bzr_dispersion_index", "bzr_trace_chain_tir", "bzr_illuminate_tir")
 _RET = {"bzr_last_error": ctypes.c_char_p, "bzr_abi_version": _I32}
 
 _lib = None
@@ -800,6 +802,58 @@ def illuminate_spectral(ctx: Context, lenses, ri_table, em: Emitter, total_rays:
                                              f.ptr, h.ptr, stats, power, res | mode))
     return (flux, hist, [dict(zip(ILLUM_STATS, [int(x) for x in stats[4 * c:4 * c + 4]])) for c in range(nchan)],
             [dict(zip(ILLUM_STATS, [int(x) for x in power[4 * c:4 * c + 4]])) for c in range(nchan)])
+
+
+LEDGER_LOST, LEDGER_EXITED, LEDGER_LANDED, LEDGER_FIELDS = 0, 1, 2, 3  # BZR_LEDGER_*
+LEDGER_ROWS = MAX_BOUNCES + 1  # BZR_LEDGER_ROWS: row min(bounces, MAX_BOUNCES)
+
+
+def illuminate_tir(ctx: Context, lenses, ri_table, em: Emitter, total_rays: int, target: Target, max_bounces=4,
+                   emission=EMISSION_LAMBERT, surface=SURFACE_FRESNEL, flux=None, hist=None, reflected_flux=None,
+                   reflected_hist=None, mode=MODE_PARITY):
+    """illuminate_spectral with total internal reflection: every traced ray goes through trace_chain_tir's chain with up
+    to max_bounces (<= MAX_BOUNCES) reflections per lens.  Returns (flux, hist, reflected_flux, reflected_hist, stats,
+    power, ledger): the first two and stats / power as illuminate_spectral returns them, now including the rays that
+    reflected; reflected_flux / reflected_hist [nchan, bins_v, bins_u] hold the landed rays with at least one reflection
+    (the stray-light map), accumulated into the arrays given; ledger = {"count", "power"}: uint64
+    [nchan, LEDGER_ROWS, LEDGER_FIELDS], every traced ray of channel c in row min(bounces, MAX_BOUNCES) under
+    LEDGER_LOST (ended NONE) or LEDGER_EXITED (left the last lens), and under LEDGER_LANDED too if it met the target;
+    "power" sums the rays' final weights in the maps' 32.32 fixed point (bzr.h bzr_illuminate_tir)."""
+    nl = len(lenses)
+    handles = (_P * nl)(*[m.handle for m in lenses])
+    table, nchan = _ri_table(ri_table, nl)
+    shape = (nchan, target.bins_v, target.bins_u)
+    if flux is None:
+        flux = np.zeros(shape, np.uint64)
+
+    def like_flux(a, np_dtype, torch_dtype):
+        if a is not None:
+            return a
+        if _is_tensor(flux):
+            import torch
+
+            return torch.zeros(shape, dtype=getattr(torch, torch_dtype), device=flux.device)
+        return np.zeros(shape, np_dtype)
+
+    hist = like_flux(hist, np.uint32, "int32")
+    reflected_flux = like_flux(reflected_flux, np.uint64, "int64")
+    reflected_hist = like_flux(reflected_hist, np.uint32, "int32")
+    f, h = _Buf(flux, np.uint64, True), _Buf(hist, np.uint32, True)
+    rf, rh = _Buf(reflected_flux, np.uint64, True), _Buf(reflected_hist, np.uint32, True)
+    rad = Radiometry(int(emission), int(surface))
+    rows = max(nchan, 1)
+    stats, power = (ctypes.c_uint64 * (4 * rows))(), (ctypes.c_uint64 * (4 * rows))()
+    ledger = {k: np.zeros((rows, LEDGER_ROWS, LEDGER_FIELDS), np.uint64) for k in ("count", "power")}
+    res = _residency(f, h, rf, rh)
+    with _stream_for(ctx, res):
+        _check(lib().bzr_illuminate_tir(ctx.handle, handles, table.ctypes.data if table.size else None, nl, nchan,
+                                        ctypes.byref(em), int(total_rays), ctypes.byref(target), ctypes.byref(rad),
+                                        int(max_bounces), f.ptr, h.ptr, rf.ptr, rh.ptr, stats, power,
+                                        ledger["count"].ctypes.data, ledger["power"].ctypes.data, res | mode))
+    return (flux, hist, reflected_flux, reflected_hist,
+            [dict(zip(ILLUM_STATS, [int(x) for x in stats[4 * c:4 * c + 4]])) for c in range(nchan)],
+            [dict(zip(ILLUM_STATS, [int(x) for x in power[4 * c:4 * c + 4]])) for c in range(nchan)],
+            {k: v[:nchan] for k, v in ledger.items()})
 
 
 def flux_to_float(flux) -> np.ndarray:

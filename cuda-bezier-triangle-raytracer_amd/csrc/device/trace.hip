@@ -4023,11 +4023,38 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
   return v;
 }
 
-// Per-channel form of the two kernels' wave reductions.  The lanes of a wave hold mixed channels, so the wave loops
-// over the channels present among its `valid` lanes (the lowest such lane names the next one); per channel, the
-// lanes of that channel reduce two counts (`a`, `b`: ballots) and the two sums of q over them, and lane 0 adds the
-// four to the channel's row: ctr[4 c], ctr[4 c + 1], sum[4 c], sum[4 c + 1].  One atomic per wave, channel and
-// counter; the loop's trip count is wave-uniform.
+// Keyed form of the illumination kernels' wave reductions.  The lanes of a wave hold mixed keys, so the wave loops
+// over the distinct keys among its `valid` lanes (the lowest such lane names the next one); per key, the lanes of
+// that key reduce kN counts (`in[k]`: ballots) and the kN sums of q over them, and lane 0 adds them to the key's
+// row: ctr[kStride key + k], sum[kStride key + k].  At most one atomic per wave, key and counter; the loop's trip
+// count is wave-uniform.
+template <int kN, uint32_t kStride>
+__device__ __forceinline__ void keyed_rows(bool valid, uint32_t key, const bool (&in)[kN], unsigned long long q,
+                                           unsigned long long *__restrict__ ctr, unsigned long long *__restrict__ sum) {
+  unsigned long long todo = __ballot(valid);
+  while (todo) {
+    const uint32_t c = __shfl(key, (int)__ffsll((long long)todo) - 1, 64);
+    const bool mine = valid && key == c;
+    unsigned long long cnt[kN], tot[kN];
+#pragma unroll
+    for (int k = 0; k < kN; ++k) cnt[k] = __ballot(mine && in[k]);
+#pragma unroll
+    for (int k = 0; k < kN; ++k)  // (a counter no lane of the key feeds has nothing to sum: the ballot is uniform)
+      tot[k] = cnt[k] ? wave_sum_u64(mine && in[k] ? q : 0ull) : 0ull;
+    if ((threadIdx.x & 63u) == 0u) {
+#pragma unroll
+      for (int k = 0; k < kN; ++k)
+        if (cnt[k]) atomicAdd(&ctr[kStride * c + (uint32_t)k], (unsigned long long)__popcll(cnt[k]));
+#pragma unroll
+      for (int k = 0; k < kN; ++k)
+        if (tot[k]) atomicAdd(&sum[kStride * c + (uint32_t)k], tot[k]);
+    }
+    todo &= ~__ballot(mine);
+  }
+}
+// The per-channel form, keyed_rows<2, 4> by hand: the key is the lane's channel, the two counts (`a`, `b`: ballots)
+// and the two sums of q go to the channel's row of four: ctr[4 c], ctr[4 c + 1], sum[4 c], sum[4 c + 1].  (Kept as
+// its own text: expressed through keyed_rows, k_emit<2> and k_land<2> came out with other registers.)
 __device__ __forceinline__ void channel_rows(bool valid, uint32_t ch, bool a, bool b, unsigned long long q,
                                              unsigned long long *__restrict__ ctr, unsigned long long *__restrict__ sum) {
   unsigned long long todo = __ballot(valid);
@@ -4168,6 +4195,61 @@ __global__ __launch_bounds__(kBlock) void k_land(bzr_target tg, float4 plane, fl
   }
 }
 
+// bzr_illuminate_tir's landing kernel: k_land<2> over a chain that reflects, plus the stray-light maps and the bounce
+// ledger.  A ray is traced when its segment count is not 0 (k_emit wrote 0, the chain counts every segment of a ray
+// it traces); only a traced ray's status, bounce word and weight are read as data.  A landed ray that reflected at
+// least once is binned into rflux / rhist (each may be null) as well.  Every traced ray of channel c is added to
+// ledger row c * BZR_LEDGER_ROWS + min(bounces, BZR_MAX_BOUNCES): its count and q(w) under LOST (it ended NONE) or
+// EXITED (OUTSIDE), and under LANDED too if it met the target -- reduced over the wave per (channel, row), like the
+// stats and power rows per channel (keyed_rows).
+struct LandTir {
+  const uint32_t *segments, *bounces;  // [n] of the batch
+  uint32_t *rhist;                     // [nchan][cells] or null
+  unsigned long long *rflux;           // [nchan][cells] or null
+  unsigned long long *count, *power;   // the ledger [nchan][BZR_LEDGER_ROWS][BZR_LEDGER_FIELDS]
+};
+__global__ __launch_bounds__(kBlock) void k_land_tir(bzr_target tg, float4 plane, float cell_u, float cell_v,
+                                                     const float *__restrict__ rays, uint32_t ld, uint32_t n,
+                                                     const uint32_t *__restrict__ status, uint32_t *__restrict__ hist,
+                                                     unsigned long long *__restrict__ stats,
+                                                     const float *__restrict__ weight,
+                                                     unsigned long long *__restrict__ flux,
+                                                     unsigned long long *__restrict__ power,
+                                                     const uint8_t *__restrict__ channel, uint32_t cells, LandTir t) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  bool traced = false, lost = false, exited = false, landed = false;
+  unsigned long long q = 0ull;
+  uint32_t ch = 0u, row = 0u;
+  if (i < n && t.segments[i] != 0u) {
+    traced = true;
+    const uint32_t st = status[i], bounces = t.bounces[i];
+    lost = st == BZR_RR_NONE;
+    exited = st == BZR_RR_OUTSIDE;
+    q = power_q32(weight[i]);
+    ch = channel[i];
+    row = bounces < BZR_MAX_BOUNCES ? bounces : uint32_t(BZR_MAX_BOUNCES);
+    if (exited) {
+      f3 s, d;
+      load_ray(rays, ld, i, s, d);
+      const int32_t cell = target_cell(tg, mk(plane.x, plane.y, plane.z), plane.w, cell_u, cell_v, s, d);
+      if (cell >= 0) {
+        landed = true;
+        const size_t at = (size_t)ch * cells + (uint32_t)cell;
+        atomicAdd(&flux[at], q);
+        if (hist) atomicAdd(&hist[at], 1u);
+        if (bounces != 0u) {
+          if (t.rflux) atomicAdd(&t.rflux[at], q);
+          if (t.rhist) atomicAdd(&t.rhist[at], 1u);
+        }
+      }
+    }
+  }
+  channel_rows(exited, ch, exited, landed, q, stats + BZR_ILLUM_EXITED, power + BZR_ILLUM_EXITED);
+  const bool in[BZR_LEDGER_FIELDS] = {lost, exited, landed};
+  static_assert(BZR_LEDGER_LOST == 0 && BZR_LEDGER_EXITED == 1 && BZR_LEDGER_LANDED == 2, "the ledger's field order");
+  keyed_rows<BZR_LEDGER_FIELDS, BZR_LEDGER_FIELDS>(traced, ch * BZR_LEDGER_ROWS + row, in, q, t.count, t.power);
+}
+
 // UniformHemisphere(belts)'s patch table (reference/hostUtil.cpp:3-14, same float expressions) and the
 // belt boundaries cos(i * width) the device compares cos(incidence) against.
 bzr_status belt_tables(uint32_t belts, std::vector<float> &cos_lo, std::vector<uint32_t> &count,
@@ -4257,13 +4339,21 @@ extern "C" bzr_status bzr_emit(bzr_ctx *ctx, const bzr_emitter *em, uint64_t fir
 // bzr_illuminate (rad and flux null: counts only) and bzr_illuminate_power (rad and flux given, hist optional).
 // bzr_illuminate_spectral: nchan > 0, `ri` is the index table [nlens][nchan], and flux, hist, stats and power hold
 // nchan maps / rows of four, one per channel (NC below is 1 otherwise).
+// bzr_illuminate_tir: spectral with `tir`, the chain that reflects (kModeTir) and what only that call returns.
+struct IllumTir {
+  uint32_t max_bounces;
+  uint64_t *rflux;          // the stray-light maps [nchan][cells], host or device memory like flux; each may be null
+  uint32_t *rhist;
+  uint64_t *count, *power;  // the ledger [nchan][BZR_LEDGER_ROWS][BZR_LEDGER_FIELDS], host memory; each may be null
+};
 static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
                              const bzr_emitter *em, uint64_t total_rays, const bzr_target *tg, const bzr_radiometry *rad,
                              uint64_t *flux, uint32_t *hist, uint64_t *stats, uint64_t *power, uint32_t flags,
-                             bool spectral = false, uint32_t nchan = 0) {
+                             bool spectral = false, uint32_t nchan = 0, const IllumTir *tir = nullptr) {
   const bool with_power = rad != nullptr;
   if (!ctx) return set_error(BZR_ERR_INVALID_ARGUMENT, "null context");
   if (nlens == 0 || nlens > kMaxLenses) return set_error(BZR_ERR_INVALID_ARGUMENT, "nlens must be 1..8");
+  if (tir && tir->max_bounces > BZR_MAX_BOUNCES) return set_error(BZR_ERR_INVALID_ARGUMENT, "max_bounces must be 0..8");
   if (spectral)
     if (bzr_status s = check_channels(ri, nchan)) return s;
   const uint32_t NC = spectral ? nchan : 1u;
@@ -4314,6 +4404,13 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   unsigned long long *d_stats = nullptr, *d_power = nullptr;  // the four counts and, with_power, the four power sums
   unsigned long long *d_flux = reinterpret_cast<unsigned long long *>(flux);
   uint8_t *d_ch = nullptr;  // spectral: the batch's channel row
+  // tir: the batch's bounce row and, staged, the chain's pending row directly behind it (one memset clears both);
+  // the ledger; the stray-light maps of a host caller
+  const size_t ledger = (size_t)BZR_LEDGER_ROWS * BZR_LEDGER_FIELDS * NC;
+  const bool staged = use_staged(flags, B, nb);
+  uint32_t *d_bnc = nullptr, *d_pend = nullptr, *d_rhist = tir ? tir->rhist : nullptr;
+  unsigned long long *d_rflux = tir ? reinterpret_cast<unsigned long long *>(tir->rflux) : nullptr;
+  unsigned long long *d_lcount = nullptr, *d_lpower = nullptr;
   if (bzr_status s = carve_buffer(ctx->scratch, ctx->scratch_bytes, [&](Staging &st) {
         belt_layout(st, em->belts, bt);
         st.take(d_rays, (size_t)B * 6), st.take(d_st, B), st.take(d_seg, B), st.take(d_stats, 4 * NC);
@@ -4321,6 +4418,11 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
         if (with_power) st.take(d_w, B), st.take(d_power, 4 * NC);
         if (with_power && host) st.take(d_flux, maps);
         if (spectral) st.take(d_ch, B);
+        if (tir) st.take(d_bnc, B);
+        if (tir && staged) st.take(d_pend, B);
+        if (tir) st.take(d_lcount, ledger), st.take(d_lpower, ledger);
+        if (tir && host && tir->rflux) st.take(d_rflux, maps);
+        if (tir && host && tir->rhist) st.take(d_rhist, maps);
       }))
     return s;
   if (bzr_status s = upload_belts(ctx, bt, belts)) return s;
@@ -4330,8 +4432,19 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
     BZR_HIP(hipMemsetAsync(d_power, 0, 32 * NC, ctx->stream));
     if (host) BZR_HIP(hipMemsetAsync(d_flux, 0, maps * 8, ctx->stream));
   }
+  if (tir) {
+    BZR_HIP(hipMemsetAsync(d_lcount, 0, ledger * 8, ctx->stream));
+    BZR_HIP(hipMemsetAsync(d_lpower, 0, ledger * 8, ctx->stream));
+    if (host && tir->rflux) BZR_HIP(hipMemsetAsync(d_rflux, 0, maps * 8, ctx->stream));
+    if (host && tir->rhist) BZR_HIP(hipMemsetAsync(d_rhist, 0, maps * 4, ctx->stream));
+  }
+  // The in-place job has alive_in set, so the chain has no first stage: nothing in it writes a culled ray's bounce
+  // word (either pipeline) or pending word (staged), and a staged bounce stage traces every ray whose pending word is
+  // set.  Both rows are therefore cleared before every batch's chain, by one memset on the context's stream (chosen
+  // over a store in k_emit, whose instantiations for the other entry points stay as they are).
+  const size_t tir_rows = !tir ? 0 : staged ? (size_t)(reinterpret_cast<char *>(d_pend + B) - reinterpret_cast<char *>(d_bnc))
+                                            : (size_t)B * 4;
   Work w;
-  const bool staged = use_staged(flags, B, nb);
   if (staged)
     if (bzr_status s = ensure_work(ctx, B, nb, w)) return s;
   const float4 sphere = make_float4(lenses[0]->sphere[0], lenses[0]->sphere[1], lenses[0]->sphere[2],
@@ -4339,9 +4452,10 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   const uint32_t lambert = with_power && rad->emission == BZR_EMISSION_LAMBERT ? 1u : 0u;
   // the mode, chosen once: the chain's (a lossless surface leaves the weights as emitted: the plain chain; the
   // spectral chain refracts per channel with a lossless surface too: its run-time flag) and the two kernels'
-  auto *const chain = spectral  ? &run_chain<kModeSpectral>
-                      : fresnel ? &run_chain<kModePower>
-                                : &run_chain<kModeStage>;
+  auto *const chain = tir        ? &run_chain<kModeTir>
+                      : spectral ? &run_chain<kModeSpectral>
+                      : fresnel  ? &run_chain<kModePower>
+                                 : &run_chain<kModeStage>;
   auto *const emit = spectral ? &k_emit<2> : with_power ? &k_emit<1> : &k_emit<0>;
   auto *const land = spectral ? &k_land<2> : with_power ? &k_land<1> : &k_land<0>;
   for (uint64_t first = 0; first < total_rays; first += B) {
@@ -4349,6 +4463,7 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
     hipLaunchKernelGGL(emit, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *em, bt, first, m, B, d_rays,
                        (uint32_t *)nullptr, d_st, d_seg, sphere, set.lens[0].always, set.lens[0].n_always, d_stats, d_w,
                        lambert, d_power, d_ch, nchan);
+    if (tir) BZR_HIP(hipMemsetAsync(d_bnc, 0, tir_rows, ctx->stream));
     TraceJob job{};  // the chain in place over the batch; culled rays (status NONE) are skipped
     job.rays = job.out_rays = d_rays;
     job.alive_in = job.status = d_st;
@@ -4360,10 +4475,18 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
     job.ri_table = ctx->ri_table;
     job.nchan = nchan;
     job.lossless = fresnel ? 0u : 1u;
-    if (bzr_status s = chain(ctx, set, job, flags, staged, nullptr, B, w)) return s;
-    hipLaunchKernelGGL(land, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg, make_float4(pn.x, pn.y, pn.z, pc),
-                       cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats, d_w, d_flux, d_power, (const uint8_t *)d_ch,
-                       spectral ? (uint32_t)cells : 0u);
+    job.bounces = d_bnc;
+    job.max_bounces = tir ? tir->max_bounces : 0u;
+    if (bzr_status s = chain(ctx, set, job, flags, staged, d_pend, B, w)) return s;
+    if (tir)
+      hipLaunchKernelGGL(k_land_tir, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg,
+                         make_float4(pn.x, pn.y, pn.z, pc), cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats, d_w, d_flux,
+                         d_power, (const uint8_t *)d_ch, (uint32_t)cells,
+                         LandTir{d_seg, d_bnc, d_rhist, d_rflux, d_lcount, d_lpower});
+    else
+      hipLaunchKernelGGL(land, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg, make_float4(pn.x, pn.y, pn.z, pc),
+                         cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats, d_w, d_flux, d_power, (const uint8_t *)d_ch,
+                         spectral ? (uint32_t)cells : 0u);
     BZR_HIP(hipGetLastError());
   }
   unsigned long long hs[4 * kMaxChannels];
@@ -4376,7 +4499,21 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
     BZR_HIP(hipMemcpyAsync(hp, d_power, 32 * NC, hipMemcpyDeviceToHost, ctx->stream));
     if (host) BZR_HIP(hipMemcpyAsync(hf.data(), d_flux, maps * 8, hipMemcpyDeviceToHost, ctx->stream));
   }
+  std::vector<unsigned long long> hrf(tir && host && tir->rflux ? maps : 0), hl(tir ? 2 * ledger : 0);
+  std::vector<uint32_t> hrh(tir && host && tir->rhist ? maps : 0);
+  if (tir) {
+    BZR_HIP(hipMemcpyAsync(hl.data(), d_lcount, ledger * 8, hipMemcpyDeviceToHost, ctx->stream));
+    BZR_HIP(hipMemcpyAsync(hl.data() + ledger, d_lpower, ledger * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (!hrf.empty()) BZR_HIP(hipMemcpyAsync(hrf.data(), d_rflux, maps * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (!hrh.empty()) BZR_HIP(hipMemcpyAsync(hrh.data(), d_rhist, maps * 4, hipMemcpyDeviceToHost, ctx->stream));
+  }
   BZR_HIP(hipStreamSynchronize(ctx->stream));
+  for (size_t k = 0; k < hrf.size(); ++k) tir->rflux[k] += hrf[k];
+  for (size_t k = 0; k < hrh.size(); ++k) tir->rhist[k] += hrh[k];
+  if (tir && tir->count)
+    for (size_t k = 0; k < ledger; ++k) tir->count[k] = hl[k];
+  if (tir && tir->power)
+    for (size_t k = 0; k < ledger; ++k) tir->power[k] = hl[ledger + k];
   if (host && hist)
     for (size_t k = 0; k < maps; ++k) hist[k] += hh[k];
   if (host && with_power)
@@ -4409,4 +4546,16 @@ extern "C" bzr_status bzr_illuminate_spectral(bzr_ctx *ctx, const bzr_mesh *cons
   if (!rad) return set_error(BZR_ERR_INVALID_ARGUMENT, "null radiometry");
   return illuminate(ctx, lenses, ri_table, nlens, em, total_rays, tg, rad, flux_q32, hist, stats, power_q32, flags, true,
                     nchan);
+}
+
+extern "C" bzr_status bzr_illuminate_tir(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table, uint32_t nlens,
+                                         uint32_t nchan, const bzr_emitter *em, uint64_t total_rays, const bzr_target *tg,
+                                         const bzr_radiometry *rad, uint32_t max_bounces, uint64_t *flux_q32, uint32_t *hist,
+                                         uint64_t *reflected_flux_q32, uint32_t *reflected_hist, uint64_t *stats,
+                                         uint64_t *power_q32, uint64_t *ledger_count, uint64_t *ledger_power_q32,
+                                         uint32_t flags) {
+  if (!rad) return set_error(BZR_ERR_INVALID_ARGUMENT, "null radiometry");
+  const IllumTir tir{max_bounces, reflected_flux_q32, reflected_hist, ledger_count, ledger_power_q32};
+  return illuminate(ctx, lenses, ri_table, nlens, em, total_rays, tg, rad, flux_q32, hist, stats, power_q32, flags, true,
+                    nchan, &tir);
 }

@@ -288,8 +288,9 @@ bzr_status bzr_trace_chain_spectral(bzr_ctx *ctx, const bzr_mesh *const *lenses,
  * out_bounces is all zero.  max_bounces above BZR_MAX_BOUNCES returns BZR_ERR_INVALID_ARGUMENT before any output is
  * touched; everything else -- the table and nlens rules, weight_in NULL or aliasing out_weight, out_weight required,
  * a channel at or above nchan and a non-finite ray (NONE after one segment, unchanged), flags, BZR_RAYS_AOS, host and
- * device pointers, the pipeline choice and chunking -- is bzr_trace_chain_spectral's.  The illumination entry
- * points, the multi-GPU plan and bzr_refract do not reflect. */
+ * device pointers, the pipeline choice and chunking -- is bzr_trace_chain_spectral's.  bzr_illuminate_tir (below)
+ * is the illumination entry point that reflects; bzr_illuminate, bzr_illuminate_power and bzr_illuminate_spectral,
+ * the multi-GPU plan and bzr_refract do not reflect. */
 #define BZR_MAX_BOUNCES 8
 bzr_status bzr_trace_chain_tir(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table, uint32_t nlens,
                                uint32_t nchan, const float *rays_soa, const uint8_t *channel, const float *weight_in,
@@ -450,6 +451,40 @@ bzr_status bzr_illuminate_spectral(bzr_ctx *ctx, const bzr_mesh *const *lenses, 
                                    uint32_t nchan, const bzr_emitter *em, uint64_t total_rays, const bzr_target *target,
                                    const bzr_radiometry *rad, uint64_t *flux_q32, uint32_t *hist, uint64_t *stats,
                                    uint64_t *power_q32, uint32_t flags);
+/* bzr_illuminate_spectral with the chain of bzr_trace_chain_tir: the same emitter stream (global ray i in channel
+ * i mod nchan), sphere cull, batching rule, 32.32 fixed point, accumulation into the maps and flags; every traced ray
+ * goes through the refraction chain with up to max_bounces reflections per lens, exactly as bzr_trace_chain_tir
+ * traces it (a reflection leaves the weight untouched; rad->surface == BZR_SURFACE_LOSSLESS keeps the weights as
+ * emitted).  flux_q32, hist, stats [nchan][4] and power_q32 [nchan][4] are bzr_illuminate_spectral's, now including
+ * the rays that reflected.
+ *   reflected_flux_q32, reflected_hist  [nchan][bins_v][bins_u], each may be NULL, host or device memory per `flags`
+ *     like flux_q32, accumulating: the part of flux_q32 / hist that comes from landed rays with at least one
+ *     reflection -- the stray-light map.
+ *   ledger_count, ledger_power_q32  [nchan][BZR_LEDGER_ROWS][BZR_LEDGER_FIELDS], host memory always, each may be
+ *     NULL, overwritten like stats: where the power went.  Every traced ray (not culled: at least one segment) of
+ *     channel c is counted once in row min(bounces, BZR_MAX_BOUNCES), bounces being bzr_trace_chain_tir's out_bounces
+ *     (summed over the lenses): under LOST if it ended NONE, under EXITED if it ended OUTSIDE, and under LANDED as
+ *     well if it meets the target.  The power entries add q(w) of the weight the ray ended with.  Culled rays are in
+ *     no row.
+ * By construction, per channel c (sums over the rows r):
+ *   sum_r EXITED = stats[c][EXITED]     sum_r LANDED = stats[c][LANDED]     (and the power sums against power_q32[c])
+ *   sum_r (LOST + EXITED) = stats[c][EMITTED] - stats[c][CULLED]: every traced ray is in exactly one of the two.
+ *     The ledger's power is what the rays ended with, power_q32[c][EMITTED] what they started with, so the power form
+ *     of this line holds where no surface takes power (BZR_SURFACE_LOSSLESS); with Fresnel surfaces the difference
+ *     is what the refractions reflected away.
+ *   sum_{r >= 1} LANDED power = the sum over the cells of what this call added to reflected_flux_q32[c]
+ * With max_bounces = 0, flux_q32, hist, stats and power_q32 are bzr_illuminate_spectral's bit for bit, the reflected
+ * maps get nothing added and only ledger row 0 is non-zero.  max_bounces above BZR_MAX_BOUNCES, and every argument
+ * bzr_illuminate_spectral rejects, return BZR_ERR_INVALID_ARGUMENT before any output is touched. */
+enum { BZR_LEDGER_LOST = 0, BZR_LEDGER_EXITED = 1, BZR_LEDGER_LANDED = 2, BZR_LEDGER_FIELDS = 3 };
+#define BZR_LEDGER_ROWS (BZR_MAX_BOUNCES + 1)
+bzr_status bzr_illuminate_tir(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table, uint32_t nlens,
+                              uint32_t nchan, const bzr_emitter *em, uint64_t total_rays, const bzr_target *target,
+                              const bzr_radiometry *rad, uint32_t max_bounces,
+                              uint64_t *flux_q32, uint32_t *hist,
+                              uint64_t *reflected_flux_q32, uint32_t *reflected_hist,
+                              uint64_t *stats, uint64_t *power_q32,
+                              uint64_t *ledger_count, uint64_t *ledger_power_q32, uint32_t flags);
 /* The bounding sphere bzr_illuminate culls with: center xyz, radius. */
 bzr_status bzr_mesh_bounding_sphere(const bzr_mesh *mesh, float out[4]);
 

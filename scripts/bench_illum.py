@@ -3,12 +3,16 @@
 on the cfg2 lens, emitter just behind it (inside the lens's bounding sphere, so nothing is culled and
 every ray is traced).  Prints one JSON line: emitted rays / s and the landed fraction.
 
-usage: bench_illum.py [total_rays] [--power]
+usage: bench_illum.py [total_rays] [--power] [--tir [max_bounces]]
 --power times bzr_illuminate_power (Lambert emitter, Fresnel surfaces: k_emit<true> -> chain with weights ->
 k_land<true>, 64-bit flux cells) beside bzr_illuminate on the same rays, alternating, and prints one more JSON line
 with both; the chain kernels' share comes from the context's event timing in a separate pass, the rest of a call is
 its emit and landing kernels and the host's part.  Per-kernel durations of k_land<false> / k_land<true>: run this
-under a kernel-trace profiler."""
+under a kernel-trace profiler.
+--tir [max_bounces] (default 4) prints one more JSON line: on a wide emitter 1 unit in front of the lens (inside its
+sphere: nothing is culled) with the indices 1.3 / 1.5 / 1.8 / 2.4, bzr_illuminate_spectral, bzr_illuminate_tir at budget
+0 and bzr_illuminate_tir at max_bounces on the same rays, alternating; the ratios are the cost of the reflecting chain's
+plumbing (the per-batch row clear, k_land_tir's ledger) and of the bounce segments."""
 import json
 import statistics
 import sys
@@ -26,6 +30,11 @@ from bzr_amd.configs import CONFIGS, build_lens  # noqa: E402
 def main():
     args = [a for a in sys.argv[1:] if a != "--power"]
     power = "--power" in sys.argv[1:]
+    tir = None
+    if "--tir" in args:
+        k = args.index("--tir")
+        tir = int(args[k + 1]) if k + 1 < len(args) and args[k + 1].isdigit() else 4
+        del args[k:k + (2 if k + 1 < len(args) and args[k + 1].isdigit() else 1)]
     total = int(args[0]) if args else 1 << 24
     ctx = bzr_amd.Context(0)
     dm = bzr_amd.DeviceMesh(ctx, build_lens(bzr_amd.TriMesh, CONFIGS["cfg2"].lenses[0]).bezier_patches())
@@ -40,6 +49,8 @@ def main():
     print(json.dumps({"workload": "illuminate cfg2 lens, emitter at x=0 (no cull), 512^2 target",
                       "rays": total, "seconds": round(dt, 4), "mrays_per_s": round(total / dt / 1e6, 1),
                       "stats": stats, "landed_fraction": round(stats["landed"] / total, 5)}))
+    if tir is not None:
+        bench_tir(ctx, dm, tg, total, tir)
     if not power:
         return
 
@@ -73,6 +84,51 @@ def main():
                       "emit_land_host_seconds": {k: round(med[k] - chain[k], 4) for k in med},
                       "power_over_counts": round(med["illuminate_power"] / med["illuminate"], 4),
                       "stats": pstats, "landed_power_fraction": round(ppower["landed"] / max(ppower["emitted"], 1), 5)}))
+
+
+def bench_tir(ctx, dm, tg, total, max_bounces):
+    row1 = [1.3, 1.5, 1.8, 2.4]
+    em = bzr_amd.Emitter(origin=(8.0, -3.0, -1.5), edge_u=(0.0, 6.0, 0.0), edge_v=(0.0, 0.0, 3.0), parts_u=4, parts_v=4,
+                         points_per_part=1024, rays_per_point=1024, belts=16, seed=1)
+    calls = {"illuminate_spectral": lambda n: bzr_amd.illuminate_spectral(ctx, [dm], [row1], em, n, tg)[2:],
+             "illuminate_tir_0": lambda n: bzr_amd.illuminate_tir(ctx, [dm], [row1], em, n, tg, max_bounces=0)[4:],
+             f"illuminate_tir_{max_bounces}":
+                 lambda n: bzr_amd.illuminate_tir(ctx, [dm], [row1], em, n, tg, max_bounces=max_bounces)[4:]}
+    wall, out = {k: [] for k in calls}, {}
+    for call in calls.values():
+        call(1 << 20)  # warm-up
+    names = list(calls)
+    for r in range(6):  # alternating, so drift hits all three alike; rotated, so each call follows each other one
+        for name in names[r % 3:] + names[:r % 3]:
+            t0 = time.perf_counter()
+            out[name] = calls[name](total)
+            wall[name].append(time.perf_counter() - t0)
+    chain = {}
+    for name in names:  # the chain kernels' share, from the context's events (a pass of its own: it perturbs the wall time)
+        ctx.timing(True)
+        ctx.timing_report()
+        calls[name](total)
+        chain[name] = sum(v[0] for v in ctx.timing_report().values()) / 1e3
+        ctx.timing(False)
+    med = {k: statistics.median(v) for k, v in wall.items()}
+    top = f"illuminate_tir_{max_bounces}"
+    stats, _, ledger = out[top]
+    count = ledger["count"].sum(axis=0)
+    print(json.dumps({"workload": "illuminate_tir beside illuminate_spectral, cfg2 lens, emitter at x=8 (no cull), "
+                                  "indices 1.3/1.5/1.8/2.4, 512^2 target",
+                      "rays": total, "max_bounces": max_bounces,
+                      "seconds": {k: round(v, 4) for k, v in med.items()},
+                      "seconds_min_max": {k: [round(min(v), 4), round(max(v), 4)] for k, v in wall.items()},
+                      "mrays_per_s": {k: round(total / v / 1e6, 1) for k, v in med.items()},
+                      "chain_kernels_seconds": {k: round(v, 4) for k, v in chain.items()},
+                      "emit_land_host_seconds": {k: round(med[k] - chain[k], 4) for k in med},
+                      "tir_0_over_spectral": round(med["illuminate_tir_0"] / med["illuminate_spectral"], 4),
+                      "tir_n_over_tir_0": round(med[top] / med["illuminate_tir_0"], 4),
+                      "reflecting_fraction": round(int(count[1:, :2].sum()) / total, 5),
+                      "landed": {"spectral": sum(s["landed"] for s in out["illuminate_spectral"][0]),
+                                 "tir_0": sum(s["landed"] for s in out["illuminate_tir_0"][0]),
+                                 top: sum(s["landed"] for s in stats), "reflected": int(count[1:, 2].sum())},
+                      "ledger_rows_lost_exited_landed": count.tolist()}))
 
 
 if __name__ == "__main__":
