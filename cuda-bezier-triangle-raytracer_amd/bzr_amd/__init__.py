@@ -79,6 +79,7 @@ _SIGS = {
     "bzr_trace_chain_power": [_P, _P, _P, _U32, _P, _P, _U32, _P, _P, _P, _P, _U32],
     "bzr_trace_chain_spectral": [_P, _P, _P, _U32, _U32, _P, _P, _P, _U32, _P, _P, _P, _P, _U32],
     "bzr_trace_chain_tir": [_P, _P, _P, _U32, _U32, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _U32],
+    "bzr_trace_chain_opl": [_P, _P, _P, _U32, _U32, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _U32],
     "bzr_dispersion_index": [_I32, _P, _U32, _P, _U32, _P],
     "bzr_trace_tiled": [_P, _U32, _P, _P, _U32, _P, _U32, _U32, _P, _P, _P, _U32],
     "bzr_tiled_create": [_P, _U32, _U32, _U32, _U32, _I32, ctypes.POINTER(_P)],
@@ -131,7 +132,7 @@ _SIGS = {
 }
 # entry points added without an ABI bump: an explicitly chosen earlier build (BZR_LIBRARY) may lack them
 _ADDED = ("bzr_trace_chain_power", "bzr_illuminate_power", "bzr_trace_chain_spectral", "bzr_illuminate_spectral",
-          "bzr_dispersion_index", "bzr_trace_chain_tir", "bzr_illuminate_tir")
+          "bzr_dispersion_index", "bzr_trace_chain_tir", "bzr_illuminate_tir", "bzr_trace_chain_opl")
 _RET = {"bzr_last_error": ctypes.c_char_p, "bzr_abi_version": _I32}
 
 _lib = None
@@ -516,6 +517,41 @@ def trace_chain_tir(ctx: Context, lenses, ri_table, rays, channel=None, weight=N
                                          nl, nchan, r.ptr, c.ptr, wi.ptr, n, int(max_bounces), o.ptr, w.ptr, s.ptr, g.ptr,
                                          b.ptr, res | mode))
     return out_rays, out_weight, out_status, out_segments, out_bounces
+
+
+def trace_chain_opl(ctx: Context, lenses, ri_table, rays, channel=None, weight=None, opl=None, max_bounces=4,
+                    out_rays=None, out_weight=None, out_status=None, out_segments=None, out_bounces=None, out_opl=None,
+                    out_glass=None, mode=MODE_PARITY):
+    """trace_chain_tir with the rays' optical path -> (rays, weight [n], status [n], segments [n], bounces [n], opl [n],
+    glass [n]).  opl [n] float32 is the path the rays arrive with (None: 0 each; out_opl may be `opl` itself).  Every
+    segment that ends in a refraction or a reflection adds its leg, the distance from the segment's origin to the hit
+    point: to opl as it is in air, times the lens's index for the ray's channel in glass, where glass takes the bare
+    length.  The first five outputs are trace_chain_tir's bit for bit.  out_glass=False: no glass row is computed and
+    the last element is None (bzr.h bzr_trace_chain_opl)."""
+    n = _n_of(rays, mode)
+    nl = len(lenses)
+    handles = (_P * nl)(*[m.handle for m in lenses])
+    table, nchan = _ri_table(ri_table, nl)
+    out_rays = _empty_like(rays, 6, np.float32, mode) if out_rays is None else out_rays
+    out_weight = _empty_like(rays, 0, np.float32, mode) if out_weight is None else out_weight
+    out_status = _empty_like(rays, 0, np.uint32, mode) if out_status is None else out_status
+    out_segments = _empty_like(rays, 0, np.uint32, mode) if out_segments is None else out_segments
+    out_bounces = _empty_like(rays, 0, np.uint32, mode) if out_bounces is None else out_bounces
+    out_opl = _empty_like(rays, 0, np.float32, mode) if out_opl is None else out_opl
+    if out_glass is False:
+        out_glass = None
+    elif out_glass is None:
+        out_glass = _empty_like(rays, 0, np.float32, mode)
+    r, c, wi, pi = _Buf(rays, np.float32), _Buf(channel, np.uint8), _Buf(weight, np.float32), _Buf(opl, np.float32)
+    o, w = _Buf(out_rays, np.float32, True), _Buf(out_weight, np.float32, True)
+    s, g, b = _Buf(out_status, np.uint32, True), _Buf(out_segments, np.uint32, True), _Buf(out_bounces, np.uint32, True)
+    p, q = _Buf(out_opl, np.float32, True), _Buf(out_glass, np.float32, True)
+    res = _residency(r, c, o, w, s, g, b, wi, pi, p, q)
+    with _stream_for(ctx, res):
+        _check(lib().bzr_trace_chain_opl(ctx.handle, ctypes.cast(handles, _P), table.ctypes.data if table.size else None,
+                                         nl, nchan, r.ptr, c.ptr, wi.ptr, pi.ptr, n, int(max_bounces), o.ptr, w.ptr,
+                                         s.ptr, g.ptr, b.ptr, p.ptr, q.ptr, res | mode))
+    return out_rays, out_weight, out_status, out_segments, out_bounces, out_opl, out_glass
 
 
 def dispersion_index(model: int, coeff, wavelength_um) -> np.ndarray:

@@ -337,6 +337,23 @@ __device__ __forceinline__ uint32_t tir_hit_t(const Hit &h, float ri, f3 s, f3 d
   return refract_hit_t<kGain>(h, ri, s, d, expected, o_s, o_d, gain);
 }
 
+// The optical path's per-leg step (kModeOpl), for a segment from origin s that ended in a refraction or a reflection
+// at the winning hit's point p: len = |p - s|, the polyline through the points the chain continues from (not the
+// hit's t, BezierIntersection's value from before the last Newton step).  A leg in air (the segment expected INSIDE)
+// adds len to opl; a leg in glass (expected OUTSIDE, bounce segments included) adds len to glass and ri len to opl.
+// Exact binary32 in both modes, like the Fresnel term: it belongs to the chain step.
+__device__ __forceinline__ void opl_leg(f3 s, f3 p, float ri, bool in_glass, float &opl, float &glass) {
+  const f3 e = sub(p, s);
+  const float len = sqrt_rn(dot(e, e));
+  if (in_glass) {
+    glass = glass + len;
+    const float m = ri * len;
+    opl = opl + m;
+  } else {
+    opl = opl + len;
+  }
+}
+
 __device__ __forceinline__ void load_ray(const float *__restrict__ r, uint32_t n, uint32_t i, f3 &s, f3 &d) {
   s = mk(r[i], r[(size_t)n + i], r[(size_t)2 * n + i]);
   d = mk(r[(size_t)3 * n + i], r[(size_t)4 * n + i], r[(size_t)5 * n + i]);
@@ -466,12 +483,19 @@ constexpr uint32_t kSlotWords = 12;  // t, point, cos, bary, normal, source patc
 // one segment, ray and weight as they came).  Again a mode of its own: the other four compile to the code they had.
 // kModeTir: kModeSpectral with total internal reflection (tir_hit_t) -- a ray that cannot leave a lens is mirrored
 // and traced against the same lens again, up to max_bounces times per lens.  A mode of its own once more.
-enum OutMode { kModeHits = 0, kModeRefract = 1, kModeStage = 2, kModePower = 3, kModeSpectral = 4, kModeTir = 5 };
+// kModeOpl: kModeTir with the ray's optical path length and its length inside glass (opl_leg), two more words per ray.
+// A mode of its own again: the other six compile to the code they had.
+enum OutMode {
+  kModeHits = 0, kModeRefract = 1, kModeStage = 2, kModePower = 3, kModeSpectral = 4, kModeTir = 5, kModeOpl = 6
+};
 constexpr bool is_stage(int mode) {
-  return mode == kModeStage || mode == kModePower || mode == kModeSpectral || mode == kModeTir;
+  return mode == kModeStage || mode == kModePower || mode == kModeSpectral || mode == kModeTir || mode == kModeOpl;
 }
-constexpr bool has_power(int mode) { return mode == kModePower || mode == kModeSpectral || mode == kModeTir; }
-constexpr bool has_channels(int mode) { return mode == kModeSpectral || mode == kModeTir; }
+constexpr bool has_power(int mode) {
+  return mode == kModePower || mode == kModeSpectral || mode == kModeTir || mode == kModeOpl;
+}
+constexpr bool has_channels(int mode) { return mode == kModeSpectral || mode == kModeTir || mode == kModeOpl; }
+constexpr bool has_tir(int mode) { return mode == kModeTir || mode == kModeOpl; }
 struct Out {
   float *hits;               // kModeHits: SoA [13][ld]
   float *rays;               // kModeRefract: output rays; kModeStage: rays in flight (in place)
@@ -495,6 +519,11 @@ struct Out {
   uint32_t *bounces;         // [ld] optional: the ray's reflections so far
   uint32_t bounce_stage;     // this stage traces the pending rays only
   uint32_t may_reflect;      // the rays this stage traces have bounce budget left in this lens
+  // kModeOpl: the optical path and the glass path in flight [ld], in place like weight.  The chain's first stage
+  // writes every ray's two words (opl_in or 0; 0), later stages add the leg of the rays they refracted or reflected.
+  float *opl;
+  const float *opl_in;       // first stage: the caller's path so far, or null -> 0
+  float *glass;              // optional
 };
 
 template <int kMode>
@@ -507,12 +536,12 @@ __device__ __forceinline__ void emit(const Out &o, uint32_t ld, uint32_t gi, f3 
     float ri = o.ri;
     bool in_table = true;
     if constexpr (has_channels(kMode)) {
-      const uint32_t ch = (kMode == kModeTir && !o.channel) ? 0u : o.channel[gi];
+      const uint32_t ch = (has_tir(kMode) && !o.channel) ? 0u : o.channel[gi];
       in_table = ch < o.nchan;
       ri = o.ri_row[in_table ? ch : 0u];
     }
     uint32_t st;
-    if constexpr (kMode == kModeTir)
+    if constexpr (has_tir(kMode))
       st = tir_hit_t<true>(h, ri, s, d, o.expected_all, in_table && o.may_reflect, os, od, gain);
     else
       st = refract_hit_t<has_power(kMode)>(h, ri, s, d, o.expected ? o.expected[gi] : o.expected_all, os, od, gain);
@@ -520,8 +549,17 @@ __device__ __forceinline__ void emit(const Out &o, uint32_t ld, uint32_t gi, f3 
       if (!in_table) st = BZR_RR_NONE;
       if (o.lossless) gain = 1.0f;
     }
+    if constexpr (kMode == kModeOpl) {  // (st: the expected status, kReflected or NONE; os: the hit's point)
+      if (o.first || st != BZR_RR_NONE) {
+        float opl = o.first ? (o.opl_in ? o.opl_in[gi] : 0.0f) : o.opl[gi];
+        float glass = (o.first || !o.glass) ? 0.0f : o.glass[gi];
+        if (st != BZR_RR_NONE) opl_leg(s, os, ri, o.expected_all == BZR_RR_OUTSIDE, opl, glass);
+        o.opl[gi] = opl;
+        if (o.glass) o.glass[gi] = glass;
+      }
+    }
     bool reflected = false;
-    if constexpr (kMode == kModeTir) {  // in memory a reflected ray is inside and pending; its weight is not touched
+    if constexpr (has_tir(kMode)) {  // in memory a reflected ray is inside and pending; its weight is not touched
       reflected = st == kReflected;
       if (o.first || o.expected_all == BZR_RR_OUTSIDE) o.pend[gi] = reflected ? 1u : 0u;
       if (o.bounces && (o.first || reflected)) o.bounces[gi] = o.first ? 0u : o.bounces[gi] + 1u;
@@ -1562,7 +1600,7 @@ __global__ __launch_bounds__(kBlock) void k_finish(MeshView m, const float *rays
     return;
   }
   if (is_stage(kMode) && !o.first && o.status[gi] == BZR_RR_NONE) return;
-  if constexpr (kMode == kModeTir)  // a bounce stage: the rays that left this lens keep every word
+  if constexpr (has_tir(kMode))  // a bounce stage: the rays that left this lens keep every word
     if (o.bounce_stage && o.pend[gi] == 0u) return;
   // the ray is loaded unconditionally: making the load depend on w.count (an intersect chunk's hits need it
   // only for an overflow ray) serialises the two reads and measured slower (cfg3 k_finish 0.059 -> 0.069 ms,
@@ -1800,6 +1838,14 @@ template <>
 struct TraceKeep<kModeTir> {
   uint32_t count[64];
   float weight[64];
+};
+// kModeOpl: and the lane's optical path and glass path (512 B more per wave: 5 976 B, 24 waves per CU still fit).
+template <>
+struct TraceKeep<kModeOpl> {
+  uint32_t count[64];
+  float weight[64];
+  float opl[64];
+  float glass[64];
 };
 // The bundle walk's set of leaf slots already queued in this wave-segment (bundle_batch `seen`), one bit per
 // slot: the refract and chain kernels walk the trees with split leaf boxes (MeshView swide).  The intersect
@@ -2314,6 +2360,9 @@ struct TraceJob {
   uint32_t lossless;               // kModeSpectral: the weights stay as they are (the gain counts as 1)
   uint32_t *bounces;               // kModeTir, optional [n]: the rays' reflections (channel may be null: channel 0)
   uint32_t max_bounces;            // kModeTir: reflections allowed per ray and lens (<= BZR_MAX_BOUNCES)
+  float *opl;                      // kModeOpl [n]: the traced rays' optical path length (may alias opl_in)
+  const float *opl_in;             // kModeOpl [n]: the path the rays start with, or null -> 0
+  float *glass;                    // kModeOpl, optional [n]: the rays' geometric length inside glass
 };
 
 // kTraceWpe: amdgpu_waves_per_eu lower bound for k_trace.  The chain kernel needs 72 VGPRs
@@ -2421,13 +2470,17 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
   float wgt = 1.0f;  // kModePower: the lane's power (loaded behind the first segment's walk, below)
   const uint32_t nseg = is_stage(kMode) ? 2u * lenses.count : 1u;
   uint32_t st = BZR_RR_NONE, seg = 0;
-  if constexpr (kMode == kModeTir) {
+  if constexpr (has_tir(kMode)) {
     // The lens stays wave-uniform: per lens one INSIDE segment (b == 0), then up to 1 + max_bounces OUTSIDE segments
     // over the lanes still inside it (`pend`); lanes that left the lens wait, and a wave vote ends the lens's
     // segments when none is pending.  The last OUTSIDE segment may not reflect, so no lane leaves the loop pending.
     // The lane's counters (segments in the low half, reflections in the high half) and its weight wait in LDS.
     L.count[lane] = 0u;
     L.weight[lane] = 1.0f;
+    if constexpr (kMode == kModeOpl) {  // the lane's optical path and glass path wait there too
+      L.opl[lane] = 0.0f;
+      L.glass[lane] = 0.0f;
+    }
     for (uint32_t l = 0; l < lenses.count; ++l) {
       if (!__any(alive)) break;
       const MeshView &m = lenses.lens[l];
@@ -2448,6 +2501,8 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
         // (the caller's weight behind the first walk, as below: fetched ahead of the loop, all four kernels came out
         // with 36 B of scratch reserved)
         if (l == 0u && b == 0u && i < n && job.weight_in) L.weight[lane] = job.weight_in[i];
+        if constexpr (kMode == kModeOpl)
+          if (l == 0u && b == 0u && i < n && job.opl_in) L.opl[lane] = job.opl_in[i];
         Hit h = no_hit();
         uint32_t patch = 0xFFFFFFFFu;
         if (best != ~0ull) h = winner(L, lane, patch);
@@ -2461,6 +2516,8 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
         if (!in_table) r = BZR_RR_NONE;
         if (job.lossless) gain = 1.0f;
         if (act) {
+          if constexpr (kMode == kModeOpl)  // the leg from s to the hit (os), before s moves there
+            if (r != BZR_RR_NONE) opl_leg(s, os, ri, b != 0u, L.opl[lane], L.glass[lane]);
           L.count[lane] += r == kReflected ? 0x10001u : 1u;
           if (r == kReflected) {  // stays pending; the weight is not touched
             s = os;
@@ -2483,6 +2540,12 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
     wgt = L.weight[lane];
     if (traced && job.bounces) job.bounces[i] = seg >> 16;
     seg &= 0xFFFFu;
+    if constexpr (kMode == kModeOpl) {
+      if (traced) {
+        job.opl[i] = L.opl[lane];
+        if (job.glass) job.glass[i] = L.glass[lane];
+      }
+    }
   } else
   for (uint32_t k = 0; k < nseg; ++k) {
     if (!__any(alive)) break;
@@ -2612,15 +2675,18 @@ __global__ __launch_bounds__(kBlock) void k_refract_scan(MeshView m, const float
 // A/B reference of the two culled paths); weight_in may be null (1) and may alias out_weight.  kScan 2: kModeSpectral's
 // form, the index from ri_table[l][channel[i]].  kScan 3: kModeTir's form -- per lane, a lens's OUTSIDE segment is
 // repeated while the ray reflects, up to max_bounces times per lens; channel may be null (channel 0), out_bounces
-// is optional.  (An int, not an enum: instantiations 0 to 2 keep their names.)
+// is optional.  kScan 4: kModeOpl's form -- kScan 3 with the optical path and the glass path (opl_leg); opl_in may be
+// null (0) and may alias out_opl, out_glass is optional.  (An int, not an enum: instantiations 0 to 3 keep their
+// names.)
 template <int kScan>
 __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const float *__restrict__ rays, uint32_t n,
                                                        float *__restrict__ out_rays, uint32_t *__restrict__ out_status,
                                                        uint32_t *__restrict__ out_segments, const float *weight_in,
                                                        float *out_weight, const uint8_t *__restrict__ channel,
                                                        const float *__restrict__ ri_table, uint32_t nchan,
-                                                       uint32_t *__restrict__ out_bounces, uint32_t max_bounces) {
-  constexpr bool kPower = kScan != 0, kSpectral = kScan >= 2, kTir = kScan == 3;
+                                                       uint32_t *__restrict__ out_bounces, uint32_t max_bounces,
+                                                       const float *opl_in, float *out_opl, float *out_glass) {
+  constexpr bool kPower = kScan != 0, kSpectral = kScan >= 2, kTir = kScan >= 3, kOpl = kScan == 4;
   uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   f3 s, d;
@@ -2635,6 +2701,8 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
     if (!in_table) ch = 0u;
   }
   uint32_t st = BZR_RR_NONE, seg = 0, bounces = 0;
+  float opl = 0.0f, glass = 0.0f;
+  if constexpr (kOpl) opl = opl_in ? opl_in[i] : 0.0f;
   bool alive = true;
   for (uint32_t l = 0; l < lenses.count && alive; ++l) {
     // kTir: j counts the lens's segments -- INSIDE, then OUTSIDE while the ray reflects (the last may not)
@@ -2652,6 +2720,8 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
         st = refract_hit_t<kPower>(h, ri, s, d, j == 0 ? BZR_RR_INSIDE : BZR_RR_OUTSIDE, os, od, gain);
       if constexpr (kSpectral)
         if (!in_table) st = BZR_RR_NONE;
+      if constexpr (kOpl)
+        if (st != BZR_RR_NONE) opl_leg(s, os, ri, j != 0u, opl, glass);
       if constexpr (kTir) {
         if (st == kReflected) {  // inside still: the same lens again, the weight as it is
           s = os;
@@ -2677,6 +2747,10 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
   if constexpr (kPower) out_weight[i] = wgt;
   if constexpr (kTir)
     if (out_bounces) out_bounces[i] = bounces;
+  if constexpr (kOpl) {
+    out_opl[i] = opl;
+    if (out_glass) out_glass[i] = glass;
+  }
 }
 
 template <bool kFast>
@@ -3112,7 +3186,7 @@ bzr_status run_segment(bool fast, bzr_ctx *ctx, const MeshView &mv, const float 
 template <int kMode>
 bzr_status run_chain(bzr_ctx *ctx, const LensSet &set, const TraceJob &job, uint32_t flags, bool staged, uint32_t *pend,
                      uint32_t ch, Work &w) {
-  constexpr bool kTir = kMode == kModeTir;
+  constexpr bool kTir = has_tir(kMode);
   if (!staged) return run_fused<kMode>(ctx, set, job, flags);
   for (uint32_t off = 0; off < job.n; off += ch) {
     const uint32_t m = std::min(ch, job.n - off);
@@ -3138,6 +3212,9 @@ bzr_status run_chain(bzr_ctx *ctx, const LensSet &set, const TraceJob &job, uint
         o.ri_row = has_channels(kMode) ? job.ri_table + (size_t)l * job.nchan : nullptr;
         o.nchan = job.nchan;
         o.lossless = job.lossless;
+        o.opl = job.opl;
+        o.opl_in = job.opl_in;
+        o.glass = job.glass;
         if (bzr_status s = run_segment<kMode>(use_fast(flags), ctx, set.lens[l], o.first ? job.rays : job.out_rays, job.ld,
                                               off, m, o.first ? nullptr : (o.bounce_stage ? pend : job.status), o, w))
           return s;
@@ -3683,13 +3760,16 @@ extern "C" bzr_status bzr_refract(bzr_ctx *ctx, const bzr_mesh *mesh, float ri, 
 // table [nlens][nchan] and `channel` one byte per ray, a plain [n] row, host or device memory as the rays);
 // bzr_trace_chain_tir (kModeTir: kModeSpectral with a null `channel` allowed, + max_bounces and out_bounces, an
 // optional plain [n] row).  The staged kModeTir chain keeps one more word per ray, the pending row, in the scratch.
+// bzr_trace_chain_opl (kModeOpl: kModeTir + opl_in, may be null, out_opl and the optional out_glass, plain [n] rows).
 template <int kMode>
 static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
                               const float *rays, const float *weight_in, uint32_t n, float *out_rays, float *out_weight,
                               uint32_t *out_status, uint32_t *out_segments, uint32_t flags,
                               const uint8_t *channel = nullptr, uint32_t nchan = 0, uint32_t max_bounces = 0,
-                              uint32_t *out_bounces = nullptr) {
-  constexpr bool kPower = has_power(kMode), kSpectral = has_channels(kMode), kTir = kMode == kModeTir;
+                              uint32_t *out_bounces = nullptr, const float *opl_in = nullptr, float *out_opl = nullptr,
+                              float *out_glass = nullptr) {
+  constexpr bool kPower = has_power(kMode), kSpectral = has_channels(kMode), kTir = has_tir(kMode);
+  constexpr bool kOpl = kMode == kModeOpl;
   if (bzr_status s = check_flags(flags, true)) return s;
   if (!ctx) return set_error(BZR_ERR_INVALID_ARGUMENT, "null context");
   if (nlens == 0 || nlens > kMaxLenses) return set_error(BZR_ERR_INVALID_ARGUMENT, "nlens must be 1..8");
@@ -3713,8 +3793,8 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
   const float *d_rays = rays;
   float *d_out = out_rays;
   uint32_t *d_st = out_status, *d_seg = out_segments, *d_bnc = out_bounces, *d_pend = nullptr;
-  const float *d_win = weight_in;
-  float *d_w = out_weight;
+  const float *d_win = weight_in, *d_oin = opl_in;
+  float *d_w = out_weight, *d_opl = out_opl, *d_glass = out_glass;
   const uint8_t *d_ch = channel;
   const bool host = !(flags & BZR_DEVICE_PTRS), aos = (flags & BZR_RAYS_AOS) != 0;
   if (kSpectral)
@@ -3731,11 +3811,17 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
         if (host && aos) st.take(tmp, (size_t)n * 6);
         if (kTir && staged) st.take(d_pend, n);
         if (kTir && host && out_bounces) st.take(d_bnc, n);
+        if (kOpl && host) st.take(d_opl, n);
+        if (kOpl && host && out_glass) st.take(d_glass, n);
       }))
     return s;
   if (host && kPower && weight_in) {
     BZR_HIP(hipMemcpyAsync(d_w, weight_in, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     d_win = d_w;
+  }
+  if (host && kOpl && opl_in) {
+    BZR_HIP(hipMemcpyAsync(d_opl, opl_in, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    d_oin = d_opl;
   }
   if (c) {
     BZR_HIP(hipMemcpyAsync(c, channel, n, hipMemcpyHostToDevice, ctx->stream));
@@ -3746,8 +3832,9 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     d_rays = r;
   }
   if (use_scan(flags)) {
-    launch(ctx, BZR_KERNEL_CHAIN_SCAN, k_chain_scan<kTir ? 3 : (kSpectral ? 2 : (kPower ? 1 : 0))>, dim3(grid_for(n)), set,
-           d_rays, n, d_out, d_st, d_seg, d_win, d_w, d_ch, (const float *)ctx->ri_table, nchan, d_bnc, max_bounces);
+    launch(ctx, BZR_KERNEL_CHAIN_SCAN, k_chain_scan<kOpl ? 4 : (kTir ? 3 : (kSpectral ? 2 : (kPower ? 1 : 0)))>,
+           dim3(grid_for(n)), set, d_rays, n, d_out, d_st, d_seg, d_win, d_w, d_ch, (const float *)ctx->ri_table, nchan, d_bnc,
+           max_bounces, d_oin, d_opl, d_glass);
     BZR_HIP(hipGetLastError());
   } else {
     TraceJob job{};
@@ -3763,6 +3850,9 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     job.nchan = nchan;
     job.bounces = d_bnc;
     job.max_bounces = max_bounces;
+    job.opl = d_opl;
+    job.opl_in = d_oin;
+    job.glass = d_glass;
     Work w;
     const uint32_t ch = staged ? chunk_for(ctx, n) : 0u;
     if (staged)
@@ -3777,6 +3867,9 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     if (kPower) BZR_HIP(hipMemcpyAsync(out_weight, d_w, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (kTir && out_bounces)
       BZR_HIP(hipMemcpyAsync(out_bounces, d_bnc, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (kOpl) BZR_HIP(hipMemcpyAsync(out_opl, d_opl, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (kOpl && out_glass)
+      BZR_HIP(hipMemcpyAsync(out_glass, d_glass, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     BZR_HIP(hipStreamSynchronize(ctx->stream));
   }
   return BZR_OK;
@@ -3811,6 +3904,19 @@ extern "C" bzr_status bzr_trace_chain_tir(bzr_ctx *ctx, const bzr_mesh *const *l
                                           uint32_t *out_bounces, uint32_t flags) {
   return trace_chain<kModeTir>(ctx, lenses, ri_table, nlens, rays, weight_in, n, out_rays, out_weight, out_status,
                                out_segments, flags, channel, nchan, max_bounces, out_bounces);
+}
+
+extern "C" bzr_status bzr_trace_chain_opl(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                          uint32_t nlens, uint32_t nchan, const float *rays, const uint8_t *channel,
+                                          const float *weight_in, const float *opl_in, uint32_t n, uint32_t max_bounces,
+                                          float *out_rays, float *out_weight, uint32_t *out_status,
+                                          uint32_t *out_segments, uint32_t *out_bounces, float *out_opl, float *out_glass,
+                                          uint32_t flags) {
+  // (both ahead of the context check: they need no device to be refused)
+  if (!out_opl) return set_error(BZR_ERR_INVALID_ARGUMENT, "null out_opl");
+  if (max_bounces > BZR_MAX_BOUNCES) return set_error(BZR_ERR_INVALID_ARGUMENT, "max_bounces must be 0..8");
+  return trace_chain<kModeOpl>(ctx, lenses, ri_table, nlens, rays, weight_in, n, out_rays, out_weight, out_status,
+                               out_segments, flags, channel, nchan, max_bounces, out_bounces, opl_in, out_opl, out_glass);
 }
 
 // ------------------------------------------------------------ test hook: normalized()

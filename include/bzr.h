@@ -296,6 +296,33 @@ bzr_status bzr_trace_chain_tir(bzr_ctx *ctx, const bzr_mesh *const *lenses, cons
                                uint32_t nchan, const float *rays_soa, const uint8_t *channel, const float *weight_in,
                                uint32_t n, uint32_t max_bounces, float *out_rays_soa, float *out_weight,
                                uint32_t *out_status, uint32_t *out_segments, uint32_t *out_bounces, uint32_t flags);
+/* ---- optical path length ----
+ * bzr_trace_chain_tir with two per-ray accumulators: out_opl [n], the optical path length sum n l over the ray's
+ * legs, and out_glass [n] (may be NULL), the geometric length of the legs inside glass, summed over the lenses.
+ * opl_in [n] (may be NULL: every ray starts at 0; may be out_opl) is the path the rays arrive with.  All three are
+ * plain float rows like out_weight: host or device memory as the rays, in either ray layout.
+ * For every segment that ends in a successful refraction or in a reflection, with s the segment's origin, p the
+ * winning hit's point and ri the value Snell's step used (ri_table[l][channel]):
+ *   e = p - s (per component)   z = e0 e0 + (e1 e1 + e2 e2)   len = sqrt(z)
+ *   refract(INSIDE) segment  (the leg lies in air):     opl = opl + len
+ *   refract(OUTSIDE) segment (the leg lies in glass,    glass = glass + len;  m = ri len;  opl = opl + m
+ *                             bounce segments included)
+ * in IEEE binary32 without contraction, the square root correctly rounded, under BZR_MODE_FAST too (it belongs to
+ * the chain step, like the Fresnel term).  The leg is the distance between the points the chain continues from, not
+ * the hit's t: t is BezierIntersection's value from before the last Newton step and differs from that distance by
+ * up to 1e-3 relative, while the hit point lies on the surface, where the path length is stationary (Fermat).
+ * A segment that ends NONE -- a miss, the wrong side, the grazing limit 0.99 <= s2 < 1, a refused reflection, a NaN
+ * -- adds nothing: out_opl is the optical length of exactly the polyline from the input origin to out_rays' origin,
+ * plus opl_in, and out_glass the part of that polyline inside glass.  A ray with a non-finite component and a ray
+ * whose channel is at or above nchan keep opl_in and get glass 0.
+ * out_rays, out_weight, out_status, out_segments and out_bounces are bzr_trace_chain_tir's bit for bit, for every
+ * max_bounces including 0, and so are the argument rules; a NULL out_opl returns BZR_ERR_INVALID_ARGUMENT before any
+ * output is touched.  The illumination entry points, the multi-GPU plan and bzr_refract carry no path length. */
+bzr_status bzr_trace_chain_opl(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table, uint32_t nlens,
+                               uint32_t nchan, const float *rays_soa, const uint8_t *channel, const float *weight_in,
+                               const float *opl_in, uint32_t n, uint32_t max_bounces, float *out_rays_soa,
+                               float *out_weight, uint32_t *out_status, uint32_t *out_segments, uint32_t *out_bounces,
+                               float *out_opl, float *out_glass, uint32_t flags);
 /* Refractive index from a dispersion formula, on the host (no context, no device): evaluated in binary64 and
  * rounded once to float.  wavelength_um [n] in micrometres, out_ri [n].
  *   BZR_DISPERSION_CAUCHY     n = A + B / l^2 + C / l^4           coeff = A, B[, C]             ncoeff 2 or 3

@@ -471,6 +471,12 @@ void traceChainTir(std::vector<BezierLens const *> const &lenses, std::vector<fl
                    uint8_t const *channels, float const *weights, std::size_t n, uint32_t maxBounces, Ray *outRays,
                    float *outWeights, RefractionResult *outStatus, uint32_t *outSegments = nullptr,
                    uint32_t *outBounces = nullptr, Context *ctx = nullptr);
+// traceChainTir with the rays' optical path length (bzr_trace_chain_opl): outOpl[i] = opl[i] (null: 0; may be outOpl)
+// + the sum of index x length over ray i's legs, outGlass[i] (may be null) its geometric length inside glass.
+void traceChainOpl(std::vector<BezierLens const *> const &lenses, std::vector<float> const &riTable, Ray const *rays,
+                   uint8_t const *channels, float const *weights, float const *opl, std::size_t n, uint32_t maxBounces,
+                   Ray *outRays, float *outWeights, RefractionResult *outStatus, float *outOpl, float *outGlass = nullptr,
+                   uint32_t *outSegments = nullptr, uint32_t *outBounces = nullptr, Context *ctx = nullptr);
 // The same chain over several devices from one process (bzr_trace_tiled): tiles of tileRays
 // consecutive rays dealt round-robin to `ctxs` (one per device, distinct), results in input order.
 void traceChainTiled(std::vector<Context *> const &ctxs, std::vector<BezierLens const *> const &lenses,
