@@ -86,6 +86,14 @@ def _surface_normal(cp, da, db, b):
     return _unit(np.cross(ca, cb))
 
 
+def _rays64(rays):
+    """The rays in binary64: a binary64 array as it is (tests/chain64.py carries its rays unrounded from segment to
+    segment), anything else through its float32 values."""
+    if isinstance(rays, np.ndarray) and rays.dtype == np.float64:
+        return rays
+    return np.asarray(rays, dtype=np.float32).astype(np.float64)
+
+
 def patch_intersect64(patches, idx, limit, rays, gated=False):
     """BezierTriangle::intersect for the triples (patches[idx[k]], rays[:, k], limit[k]) in binary64.
 
@@ -96,7 +104,7 @@ def patch_intersect64(patches, idx, limit, rays, gated=False):
     gate barycentrics' least distance from 0 and 1), all as computed when the gate passes and zero when it fails."""
     rec = np.asarray(patches, dtype=np.float32)[np.asarray(idx, dtype=np.int64)].astype(np.float64)
     limit = np.asarray(limit)
-    r = np.asarray(rays, dtype=np.float32).astype(np.float64)
+    r = _rays64(rays)
     s, d = r[:3].T, r[3:].T
     n, c = rec[:, 0:3], rec[:, 3]
     div = rec[:, 4:16].reshape(-1, 3, 4)
@@ -173,9 +181,10 @@ def intersect64(patches, rays, gate):
 
     Returns a namespace over the rays: what (INTERSECT or NONE), patch (0xFFFFFFFF for a miss), t, point, cs, bary,
     normal, and well: the winner is well-conditioned (and so is the cThis evaluation that named it, for a retry) and
-    its t lies below the finite t of every candidate on another patch by more than SEPARATION_WELL x span."""
+    its t lies below the finite t of every candidate on another patch by more than SEPARATION_WELL x span.
+    Binary64 rays are taken as they are; the gate matrix is then that of their float32 roundings."""
     patches = np.asarray(patches, dtype=np.float32)
-    rays = np.asarray(rays, dtype=np.float32)
+    rays = _rays64(rays)
     nr = rays.shape[1]
     span = mesh_span(patches)
     neigh = np.ascontiguousarray(patches).view(np.uint32)[:, 16:19]

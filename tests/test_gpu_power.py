@@ -204,7 +204,7 @@ def eight(orc):
 def test_fast_mode(bzr, ctx, scenes, pipe_name):
     """FAST changes the Newton stage only: rays, status and segments are bzr_trace_chain's FAST ones bit for bit, and
     the Fresnel term itself stays exact.  How far the FAST weights lie from the parity ones is recorded (printed, and
-    in DESIGN.md (c)), not asserted: nothing derives a bound for it."""
+    in DESIGN.md (c)); the distance from the truth is what tests/test_gpu_fast_chain64.py asserts."""
     _, ris, dms, rays, _, ones, _ = scenes["cfg2"]
     mode = flags_of(bzr, pipe_name) | bzr.MODE_FAST
     plain = bzr.trace_chain(ctx, dms, ris, rays, mode=mode)

@@ -91,7 +91,7 @@ def test_uniform_table_is_the_power_chain(bzr, ctx, scenes, path):
 @pytest.mark.parametrize("pipe_name", ("fused", "staged"))
 def test_fast_mode(bzr, ctx, scenes, pipe_name):
     """FAST with a uniform table is trace_chain_power's FAST result bit for bit.  With mixed channels, how far the
-    FAST weights lie from the parity ones is recorded (printed), not asserted: nothing derives a bound for it."""
+    FAST weights lie from the parity ones is recorded (printed); the distance from the truth is what tests/test_gpu_fast_chain64.py asserts."""
     _, table, dms, rays, channel, _, ones, _, _ = scenes["cfg4"]
     mode = flags_of(bzr, pipe_name) | bzr.MODE_FAST
     want = bzr.trace_chain_power(ctx, dms, [1.3, 1.3], rays, mode=mode)

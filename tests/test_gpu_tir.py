@@ -125,8 +125,8 @@ def test_zero_budget_fast(bzr, ctx, scenes, pipe_name):
 @pytest.mark.parametrize("pipe_name", ("fused", "staged"))
 @pytest.mark.parametrize("name", list(TABLES))
 def test_fast_with_bounces(bzr, ctx, scenes, name, pipe_name):
-    """Structure only.  The share of rays that agree with parity is recorded (printed), not asserted: nothing derives
-    a bound for it."""
+    """Structure only.  The share of rays that agree with parity is recorded (printed); the share with the
+    binary64 chain's structure and the distance from the truth are what tests/test_gpu_fast_chain64.py asserts."""
     _, table, dms, rays, channel, _, ones, _ = scenes[name]
     mb, nl = 4, len(dms)
     mode = flags_of(bzr, pipe_name) | bzr.MODE_FAST
