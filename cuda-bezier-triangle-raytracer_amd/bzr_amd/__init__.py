@@ -80,6 +80,7 @@ _SIGS = {
     "bzr_trace_chain_spectral": [_P, _P, _P, _U32, _U32, _P, _P, _P, _U32, _P, _P, _P, _P, _U32],
     "bzr_trace_chain_tir": [_P, _P, _P, _U32, _U32, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _U32],
     "bzr_trace_chain_opl": [_P, _P, _P, _U32, _U32, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _U32],
+    "bzr_trace_chain_media": [_P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _U32],
     "bzr_dispersion_index": [_I32, _P, _U32, _P, _U32, _P],
     "bzr_trace_tiled": [_P, _U32, _P, _P, _U32, _P, _U32, _U32, _P, _P, _P, _U32],
     "bzr_tiled_create": [_P, _U32, _U32, _U32, _U32, _I32, ctypes.POINTER(_P)],
@@ -132,7 +133,8 @@ _SIGS = {
 }
 # entry points added without an ABI bump: an explicitly chosen earlier build (BZR_LIBRARY) may lack them
 _ADDED = ("bzr_trace_chain_power", "bzr_illuminate_power", "bzr_trace_chain_spectral", "bzr_illuminate_spectral",
-          "bzr_dispersion_index", "bzr_trace_chain_tir", "bzr_illuminate_tir", "bzr_trace_chain_opl")
+          "bzr_dispersion_index", "bzr_trace_chain_tir", "bzr_illuminate_tir", "bzr_trace_chain_opl",
+          "bzr_trace_chain_media")
 _RET = {"bzr_last_error": ctypes.c_char_p, "bzr_abi_version": _I32}
 
 _lib = None
@@ -551,6 +553,47 @@ def trace_chain_opl(ctx: Context, lenses, ri_table, rays, channel=None, weight=N
         _check(lib().bzr_trace_chain_opl(ctx.handle, ctypes.cast(handles, _P), table.ctypes.data if table.size else None,
                                          nl, nchan, r.ptr, c.ptr, wi.ptr, pi.ptr, n, int(max_bounces), o.ptr, w.ptr,
                                          s.ptr, g.ptr, b.ptr, p.ptr, q.ptr, res | mode))
+    return out_rays, out_weight, out_status, out_segments, out_bounces, out_opl, out_glass
+
+
+def trace_chain_media(ctx: Context, lenses, ri_table, gap_table, rays, channel=None, weight=None, opl=None, max_bounces=4,
+                      out_rays=None, out_weight=None, out_status=None, out_segments=None, out_bounces=None, out_opl=None,
+                      out_glass=None, mode=MODE_PARITY):
+    """trace_chain_opl with a medium in front of, between and behind the lenses -> the same seven-tuple.  gap_table
+    [nlens + 1, nchan] float32 (host): row l is the index in front of lens l, the last row the index behind the last
+    lens; None is vacuum, and with every entry 1 the result is trace_chain_opl's bit for bit.  Going into lens l a ray
+    of channel c refracts with eta = gap[l, c] / ri[l, c], coming out (and in the reflection test) with ri[l, c] /
+    gap[l + 1, c]; a leg in front of a lens adds gap[l, c] x its length to opl, glass counts lens glass only.  Every
+    entry must be finite and above 0 (bzr.h bzr_trace_chain_media)."""
+    n = _n_of(rays, mode)
+    nl = len(lenses)
+    handles = (_P * nl)(*[m.handle for m in lenses])
+    table, nchan = _ri_table(ri_table, nl)
+    gap = None
+    if gap_table is not None:
+        gap = np.ascontiguousarray(gap_table, dtype=np.float32)
+        if gap.shape != (nl + 1, nchan):
+            raise BzrError(f"gap_table must be [nlens + 1 = {nl + 1}, nchan = {nchan}], got {gap.shape}")
+    out_rays = _empty_like(rays, 6, np.float32, mode) if out_rays is None else out_rays
+    out_weight = _empty_like(rays, 0, np.float32, mode) if out_weight is None else out_weight
+    out_status = _empty_like(rays, 0, np.uint32, mode) if out_status is None else out_status
+    out_segments = _empty_like(rays, 0, np.uint32, mode) if out_segments is None else out_segments
+    out_bounces = _empty_like(rays, 0, np.uint32, mode) if out_bounces is None else out_bounces
+    out_opl = _empty_like(rays, 0, np.float32, mode) if out_opl is None else out_opl
+    if out_glass is False:
+        out_glass = None
+    elif out_glass is None:
+        out_glass = _empty_like(rays, 0, np.float32, mode)
+    r, c, wi, pi = _Buf(rays, np.float32), _Buf(channel, np.uint8), _Buf(weight, np.float32), _Buf(opl, np.float32)
+    o, w = _Buf(out_rays, np.float32, True), _Buf(out_weight, np.float32, True)
+    s, g, b = _Buf(out_status, np.uint32, True), _Buf(out_segments, np.uint32, True), _Buf(out_bounces, np.uint32, True)
+    p, q = _Buf(out_opl, np.float32, True), _Buf(out_glass, np.float32, True)
+    res = _residency(r, c, o, w, s, g, b, wi, pi, p, q)
+    with _stream_for(ctx, res):
+        _check(lib().bzr_trace_chain_media(ctx.handle, ctypes.cast(handles, _P), table.ctypes.data if table.size else None,
+                                           gap.ctypes.data if gap is not None and gap.size else None, nl, nchan, r.ptr,
+                                           c.ptr, wi.ptr, pi.ptr, n, int(max_bounces), o.ptr, w.ptr, s.ptr, g.ptr, b.ptr,
+                                           p.ptr, q.ptr, res | mode))
     return out_rays, out_weight, out_status, out_segments, out_bounces, out_opl, out_glass
 
 

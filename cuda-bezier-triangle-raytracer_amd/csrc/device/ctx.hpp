@@ -52,6 +52,9 @@ struct bzr_ctx {
   // must outlive them whatever the next call stages (trace.hip upload_ri_table).
   float *ri_table = nullptr;
   std::vector<float> ri_table_host;
+  // kModeMedia's gap table [nlens + 1][nchan] lies in the same buffer behind the index table's rows, with a host copy
+  // of its own: the two halves are compared and rewritten separately (trace.hip upload_gap_table).
+  std::vector<float> gap_table_host;
 };
 
 // BZR_RAYS_AOS (frame_pack.hip): n rays between the reference's [n][6] records and the kernels' [6][n] rows,

@@ -23,6 +23,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstdlib>
 
 #include <cstdio>
@@ -337,6 +338,55 @@ __device__ __forceinline__ uint32_t tir_hit_t(const Hit &h, float ri, f3 s, f3 d
   return refract_hit_t<kGain>(h, ri, s, d, expected, o_s, o_d, gain);
 }
 
+// Snell's step between two media (kModeMedia): refract_hit_t with the step's eta handed in -- n0 / n1 for a segment
+// expected INSIDE, n1 / n2 for one expected OUTSIDE (media_eta) -- in place of 1 / ri and ri.  A hit on the other side
+// returns NONE whatever eta it was given.  s2, the refraction limit, the direction and the Fresnel term all come from
+// this eta, in refract_hit_t's order; with eta = 1 / ri and ri they are its bits.  (A sibling, not refract_hit_t
+// re-expressed: the instantiations of the older modes compile to the code they had.)
+template <bool kGain>
+__device__ __forceinline__ uint32_t refract_eta_t(const Hit &h, float eta, f3 s, f3 d, uint32_t expected, f3 &o_s,
+                                                  f3 &o_d, float &gain) {
+  o_s = s;
+  o_d = d;
+  uint32_t st = BZR_RR_NONE;
+  if (h.what == kIntersect) {
+    st = h.cs < 0.0f ? BZR_RR_INSIDE : BZR_RR_OUTSIDE;
+    o_s = h.point;
+    float s2 = eta * eta * (1.0f - h.cs * h.cs);
+    if constexpr (kGain) gain = fresnel_t(eta, h.cs, s2);
+    if (s2 < 0.99f) {
+      if (s2 > 1e-12f) {
+        float sgn = st == BZR_RR_INSIDE ? 1.0f : -1.0f;
+        f3 nn = scale(h.normal, sgn);
+        float c1 = fabsf(h.cs);
+        float c2 = sqrt_rn(1.0f - s2);
+        o_d = normalized(add(scale(d, eta), scale(nn, eta * c1 - c2)));
+      }
+    } else {
+      st = BZR_RR_NONE;
+    }
+  }
+  return st == expected ? st : BZR_RR_NONE;
+}
+// tir_hit_t's form of it: the reflection test reads the same eta (s2 = eta^2 (1 - cs^2) >= 1 on a segment expected
+// OUTSIDE), so a lens in a medium as dense as its glass reflects nothing.
+template <bool kGain>
+__device__ __forceinline__ uint32_t tir_eta_t(const Hit &h, float eta, f3 s, f3 d, uint32_t expected, bool may_reflect,
+                                              f3 &o_s, f3 &o_d, float &gain) {
+  const float s2 = eta * eta * (1.0f - h.cs * h.cs);
+  if (expected == BZR_RR_OUTSIDE && may_reflect && h.what == kIntersect && h.cs >= 0.0f && s2 >= 1.0f) {
+    const float k = 2.0f * h.cs;
+    o_d = normalized(sub(d, scale(h.normal, k)));
+    o_s = h.point;
+    return kReflected;
+  }
+  return refract_eta_t<kGain>(h, eta, s, d, expected, o_s, o_d, gain);
+}
+// The segment's eta: one correctly rounded division, n0 / n1 going in, n1 / n2 coming out (bounce segments included).
+__device__ __forceinline__ float media_eta(float n0, float n1, float n2, bool outside) {
+  return div_rn(outside ? n1 : n0, outside ? n2 : n1);
+}
+
 // The optical path's per-leg step (kModeOpl), for a segment from origin s that ended in a refraction or a reflection
 // at the winning hit's point p: len = |p - s|, the polyline through the points the chain continues from (not the
 // hit's t, BezierIntersection's value from before the last Newton step).  A leg in air (the segment expected INSIDE)
@@ -352,6 +402,15 @@ __device__ __forceinline__ void opl_leg(f3 s, f3 p, float ri, bool in_glass, flo
   } else {
     opl = opl + len;
   }
+}
+// kModeMedia's form: the leg in front of the lens (expected INSIDE) lies in a medium of index n0 and adds m = n0 len
+// to opl; the leg in glass is opl_leg's.  `nm`: n1 in glass, n0 in front.  glass stays the length in lens glass.
+__device__ __forceinline__ void opl_leg_media(f3 s, f3 p, float nm, bool in_glass, float &opl, float &glass) {
+  const f3 e = sub(p, s);
+  const float len = sqrt_rn(dot(e, e));
+  if (in_glass) glass = glass + len;
+  const float m = nm * len;
+  opl = opl + m;
 }
 
 __device__ __forceinline__ void load_ray(const float *__restrict__ r, uint32_t n, uint32_t i, f3 &s, f3 &d) {
@@ -485,17 +544,24 @@ constexpr uint32_t kSlotWords = 12;  // t, point, cos, bary, normal, source patc
 // and traced against the same lens again, up to max_bounces times per lens.  A mode of its own once more.
 // kModeOpl: kModeTir with the ray's optical path length and its length inside glass (opl_leg), two more words per ray.
 // A mode of its own again: the other six compile to the code they had.
+// kModeMedia: kModeOpl with a medium in front of, between and behind the lenses -- gap_table[l][channel[i]] is the
+// index in front of lens l, row `count` the one behind the last lens.  Snell's step, the reflection test, the Fresnel
+// term (refract_eta_t, tir_eta_t) and the leg in front of a lens (opl_leg_media) read them.  A mode of its own once
+// more: the other seven compile to the code they had.
 enum OutMode {
-  kModeHits = 0, kModeRefract = 1, kModeStage = 2, kModePower = 3, kModeSpectral = 4, kModeTir = 5, kModeOpl = 6
+  kModeHits = 0, kModeRefract = 1, kModeStage = 2, kModePower = 3, kModeSpectral = 4, kModeTir = 5, kModeOpl = 6,
+  kModeMedia = 7
 };
+constexpr bool has_media(int mode) { return mode == kModeMedia; }
+constexpr bool has_opl(int mode) { return mode == kModeOpl || mode == kModeMedia; }
 constexpr bool is_stage(int mode) {
-  return mode == kModeStage || mode == kModePower || mode == kModeSpectral || mode == kModeTir || mode == kModeOpl;
+  return mode == kModeStage || mode == kModePower || mode == kModeSpectral || mode == kModeTir || has_opl(mode);
 }
 constexpr bool has_power(int mode) {
-  return mode == kModePower || mode == kModeSpectral || mode == kModeTir || mode == kModeOpl;
+  return mode == kModePower || mode == kModeSpectral || mode == kModeTir || has_opl(mode);
 }
-constexpr bool has_channels(int mode) { return mode == kModeSpectral || mode == kModeTir || mode == kModeOpl; }
-constexpr bool has_tir(int mode) { return mode == kModeTir || mode == kModeOpl; }
+constexpr bool has_channels(int mode) { return mode == kModeSpectral || mode == kModeTir || has_opl(mode); }
+constexpr bool has_tir(int mode) { return mode == kModeTir || has_opl(mode); }
 struct Out {
   float *hits;               // kModeHits: SoA [13][ld]
   float *rays;               // kModeRefract: output rays; kModeStage: rays in flight (in place)
@@ -524,6 +590,8 @@ struct Out {
   float *opl;
   const float *opl_in;       // first stage: the caller's path so far, or null -> 0
   float *glass;              // optional
+  // kModeMedia: the rows of the gap table [nchan] in front of this lens and behind it (device memory, like ri_row)
+  const float *gap_row, *gap_next;
 };
 
 template <int kMode>
@@ -535,13 +603,22 @@ __device__ __forceinline__ void emit(const Out &o, uint32_t ld, uint32_t gi, f3 
     float gain = 1.0f;
     float ri = o.ri;
     bool in_table = true;
+    uint32_t col = 0u;  // the ray's column of the tables
     if constexpr (has_channels(kMode)) {
       const uint32_t ch = (has_tir(kMode) && !o.channel) ? 0u : o.channel[gi];
       in_table = ch < o.nchan;
-      ri = o.ri_row[in_table ? ch : 0u];
+      col = in_table ? ch : 0u;
+      ri = o.ri_row[col];
     }
     uint32_t st;
-    if constexpr (has_tir(kMode))
+    float nm = ri;  // kModeMedia: the index of the medium this segment's leg lies in
+    if constexpr (has_media(kMode)) {
+      const bool outside = o.expected_all == BZR_RR_OUTSIDE;
+      const float n0 = o.gap_row[col];
+      if (!outside) nm = n0;
+      st = tir_eta_t<true>(h, media_eta(n0, ri, o.gap_next[col], outside), s, d, o.expected_all, in_table && o.may_reflect,
+                           os, od, gain);
+    } else if constexpr (has_tir(kMode))
       st = tir_hit_t<true>(h, ri, s, d, o.expected_all, in_table && o.may_reflect, os, od, gain);
     else
       st = refract_hit_t<has_power(kMode)>(h, ri, s, d, o.expected ? o.expected[gi] : o.expected_all, os, od, gain);
@@ -549,11 +626,14 @@ __device__ __forceinline__ void emit(const Out &o, uint32_t ld, uint32_t gi, f3 
       if (!in_table) st = BZR_RR_NONE;
       if (o.lossless) gain = 1.0f;
     }
-    if constexpr (kMode == kModeOpl) {  // (st: the expected status, kReflected or NONE; os: the hit's point)
+    if constexpr (has_opl(kMode)) {  // (st: the expected status, kReflected or NONE; os: the hit's point)
       if (o.first || st != BZR_RR_NONE) {
         float opl = o.first ? (o.opl_in ? o.opl_in[gi] : 0.0f) : o.opl[gi];
         float glass = (o.first || !o.glass) ? 0.0f : o.glass[gi];
-        if (st != BZR_RR_NONE) opl_leg(s, os, ri, o.expected_all == BZR_RR_OUTSIDE, opl, glass);
+        if (st != BZR_RR_NONE) {
+          if constexpr (has_media(kMode)) opl_leg_media(s, os, nm, o.expected_all == BZR_RR_OUTSIDE, opl, glass);
+          else opl_leg(s, os, ri, o.expected_all == BZR_RR_OUTSIDE, opl, glass);
+        }
         o.opl[gi] = opl;
         if (o.glass) o.glass[gi] = glass;
       }
@@ -1847,6 +1927,8 @@ struct TraceKeep<kModeOpl> {
   float opl[64];
   float glass[64];
 };
+template <>
+struct TraceKeep<kModeMedia> : TraceKeep<kModeOpl> {};  // kModeMedia keeps what kModeOpl keeps: no new word per lane
 // The bundle walk's set of leaf slots already queued in this wave-segment (bundle_batch `seen`), one bit per
 // slot: the refract and chain kernels walk the trees with split leaf boxes (MeshView swide).  The intersect
 // kernel's 6.7 KB per wave leave no room for it (24 waves x 7.7 KB > 160 KB), and the power, spectral and TIR
@@ -2363,6 +2445,7 @@ struct TraceJob {
   float *opl;                      // kModeOpl [n]: the traced rays' optical path length (may alias opl_in)
   const float *opl_in;             // kModeOpl [n]: the path the rays start with, or null -> 0
   float *glass;                    // kModeOpl, optional [n]: the rays' geometric length inside glass
+  const float *gap_table;          // kModeMedia [count + 1][nchan]: the index in front of lens l, row count behind the last
 };
 
 // kTraceWpe: amdgpu_waves_per_eu lower bound for k_trace.  The chain kernel needs 72 VGPRs
@@ -2477,7 +2560,7 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
     // The lane's counters (segments in the low half, reflections in the high half) and its weight wait in LDS.
     L.count[lane] = 0u;
     L.weight[lane] = 1.0f;
-    if constexpr (kMode == kModeOpl) {  // the lane's optical path and glass path wait there too
+    if constexpr (has_opl(kMode)) {  // the lane's optical path and glass path wait there too
       L.opl[lane] = 0.0f;
       L.glass[lane] = 0.0f;
     }
@@ -2501,7 +2584,7 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
         // (the caller's weight behind the first walk, as below: fetched ahead of the loop, all four kernels came out
         // with 36 B of scratch reserved)
         if (l == 0u && b == 0u && i < n && job.weight_in) L.weight[lane] = job.weight_in[i];
-        if constexpr (kMode == kModeOpl)
+        if constexpr (has_opl(kMode))
           if (l == 0u && b == 0u && i < n && job.opl_in) L.opl[lane] = job.opl_in[i];
         Hit h = no_hit();
         uint32_t patch = 0xFFFFFFFFu;
@@ -2511,13 +2594,28 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
         const float ri = job.ri_table[l * job.nchan + (in_table ? ch : 0u)];
         f3 os, od;
         float gain = 1.0f;
-        uint32_t r = tir_hit_t<true>(h, ri, s, d, b == 0u ? uint32_t(BZR_RR_INSIDE) : uint32_t(BZR_RR_OUTSIDE),
-                                     in_table && b <= job.max_bounces, os, od, gain);
+        uint32_t r;
+        float nm = ri;  // kModeMedia: the index of the medium this segment's leg lies in
+        if constexpr (has_media(kMode)) {
+          // the lane's n0 and n2 are read here like ri, behind the segment's passes: nothing new lives across a walk
+          const uint32_t c = l * job.nchan + (in_table ? ch : 0u);
+          const float n0 = job.gap_table[c];
+          if (b == 0u) nm = n0;
+          r = tir_eta_t<true>(h, media_eta(n0, ri, job.gap_table[c + job.nchan], b != 0u), s, d,
+                              b == 0u ? uint32_t(BZR_RR_INSIDE) : uint32_t(BZR_RR_OUTSIDE),
+                              in_table && b <= job.max_bounces, os, od, gain);
+        } else {
+          r = tir_hit_t<true>(h, ri, s, d, b == 0u ? uint32_t(BZR_RR_INSIDE) : uint32_t(BZR_RR_OUTSIDE),
+                              in_table && b <= job.max_bounces, os, od, gain);
+        }
         if (!in_table) r = BZR_RR_NONE;
         if (job.lossless) gain = 1.0f;
         if (act) {
-          if constexpr (kMode == kModeOpl)  // the leg from s to the hit (os), before s moves there
+          if constexpr (has_media(kMode)) {
+            if (r != BZR_RR_NONE) opl_leg_media(s, os, nm, b != 0u, L.opl[lane], L.glass[lane]);
+          } else if constexpr (kMode == kModeOpl) {  // the leg from s to the hit (os), before s moves there
             if (r != BZR_RR_NONE) opl_leg(s, os, ri, b != 0u, L.opl[lane], L.glass[lane]);
+          }
           L.count[lane] += r == kReflected ? 0x10001u : 1u;
           if (r == kReflected) {  // stays pending; the weight is not touched
             s = os;
@@ -2540,7 +2638,7 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
     wgt = L.weight[lane];
     if (traced && job.bounces) job.bounces[i] = seg >> 16;
     seg &= 0xFFFFu;
-    if constexpr (kMode == kModeOpl) {
+    if constexpr (has_opl(kMode)) {
       if (traced) {
         job.opl[i] = L.opl[lane];
         if (job.glass) job.glass[i] = L.glass[lane];
@@ -2676,8 +2774,8 @@ __global__ __launch_bounds__(kBlock) void k_refract_scan(MeshView m, const float
 // form, the index from ri_table[l][channel[i]].  kScan 3: kModeTir's form -- per lane, a lens's OUTSIDE segment is
 // repeated while the ray reflects, up to max_bounces times per lens; channel may be null (channel 0), out_bounces
 // is optional.  kScan 4: kModeOpl's form -- kScan 3 with the optical path and the glass path (opl_leg); opl_in may be
-// null (0) and may alias out_opl, out_glass is optional.  (An int, not an enum: instantiations 0 to 3 keep their
-// names.)
+// null (0) and may alias out_opl, out_glass is optional.  kScan 5: kModeMedia's form -- kScan 4 with gap_table [count +
+// 1][nchan] (tir_eta_t, opl_leg_media).  (An int, not an enum: instantiations 0 to 3 keep their names.)
 template <int kScan>
 __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const float *__restrict__ rays, uint32_t n,
                                                        float *__restrict__ out_rays, uint32_t *__restrict__ out_status,
@@ -2685,8 +2783,9 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
                                                        float *out_weight, const uint8_t *__restrict__ channel,
                                                        const float *__restrict__ ri_table, uint32_t nchan,
                                                        uint32_t *__restrict__ out_bounces, uint32_t max_bounces,
-                                                       const float *opl_in, float *out_opl, float *out_glass) {
-  constexpr bool kPower = kScan != 0, kSpectral = kScan >= 2, kTir = kScan >= 3, kOpl = kScan == 4;
+                                                       const float *opl_in, float *out_opl, float *out_glass,
+                                                       const float *__restrict__ gap_table) {
+  constexpr bool kPower = kScan != 0, kSpectral = kScan >= 2, kTir = kScan >= 3, kOpl = kScan >= 4, kMedia = kScan == 5;
   uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   f3 s, d;
@@ -2714,13 +2813,21 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
       float gain = 1.0f;
       float ri = lenses.lens[l].ri;
       if constexpr (kSpectral) ri = ri_table[l * nchan + ch];
-      if constexpr (kTir)
+      float nm = ri;
+      if constexpr (kMedia) {
+        const float n0 = gap_table[l * nchan + ch];
+        if (j == 0u) nm = n0;
+        st = tir_eta_t<true>(h, media_eta(n0, ri, gap_table[(l + 1u) * nchan + ch], j != 0u), s, d,
+                             j == 0 ? BZR_RR_INSIDE : BZR_RR_OUTSIDE, in_table && j <= max_bounces, os, od, gain);
+      } else if constexpr (kTir)
         st = tir_hit_t<true>(h, ri, s, d, j == 0 ? BZR_RR_INSIDE : BZR_RR_OUTSIDE, in_table && j <= max_bounces, os, od, gain);
       else
         st = refract_hit_t<kPower>(h, ri, s, d, j == 0 ? BZR_RR_INSIDE : BZR_RR_OUTSIDE, os, od, gain);
       if constexpr (kSpectral)
         if (!in_table) st = BZR_RR_NONE;
-      if constexpr (kOpl)
+      if constexpr (kMedia) {
+        if (st != BZR_RR_NONE) opl_leg_media(s, os, nm, j != 0u, opl, glass);
+      } else if constexpr (kOpl)
         if (st != BZR_RR_NONE) opl_leg(s, os, ri, j != 0u, opl, glass);
       if constexpr (kTir) {
         if (st == kReflected) {  // inside still: the same lens again, the weight as it is
@@ -3142,15 +3249,40 @@ bzr_status run_fused(bzr_ctx *ctx, const LensSet &set, const TraceJob &job, uint
 // device-pointer call may still read the old one); the copy itself is synchronous, so the caller's table is not
 // read after the call returns.  A frame loop with one table therefore uploads it once.
 constexpr uint32_t kMaxChannels = BZR_MAX_CHANNELS;
+// (one allocation: kModeMedia's gap table [nlens + 1][nchan] lies behind the index table's kMaxLenses rows)
+constexpr size_t kRiTableFloats = (size_t)kMaxLenses * kMaxChannels, kGapTableFloats = (size_t)(kMaxLenses + 1) * kMaxChannels;
 bzr_status upload_ri_table(bzr_ctx *ctx, const float *table, uint32_t nlens, uint32_t nchan) {
   const size_t count = (size_t)nlens * nchan;
-  if (!ctx->ri_table) BZR_HIP(hipMalloc(&ctx->ri_table, (size_t)kMaxLenses * kMaxChannels * sizeof(float)));
+  if (!ctx->ri_table) BZR_HIP(hipMalloc(&ctx->ri_table, (kRiTableFloats + kGapTableFloats) * sizeof(float)));
   if (ctx->ri_table_host.size() == count && std::memcmp(ctx->ri_table_host.data(), table, count * sizeof(float)) == 0)
     return BZR_OK;
   BZR_HIP(hipStreamSynchronize(ctx->stream));
   ctx->ri_table_host.clear();
   BZR_HIP(hipMemcpy(ctx->ri_table, table, count * sizeof(float), hipMemcpyHostToDevice));
   ctx->ri_table_host.assign(table, table + count);
+  return BZR_OK;
+}
+// kModeMedia's gap table beside it, under the same rule and with a host copy of its own: a call that changes only one
+// of the two tables rewrites that one, and the entry points that take no gap table never touch this half.  A null
+// table is vacuum, every entry 1.  (upload_ri_table, called first, has allocated the buffer.)
+bzr_status upload_gap_table(bzr_ctx *ctx, const float *table, uint32_t nlens, uint32_t nchan) {
+  const size_t count = (size_t)(nlens + 1) * nchan;
+  const std::vector<float> ones(table ? 0 : count, 1.0f);
+  if (!table) table = ones.data();
+  if (ctx->gap_table_host.size() == count && std::memcmp(ctx->gap_table_host.data(), table, count * sizeof(float)) == 0)
+    return BZR_OK;
+  BZR_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->gap_table_host.clear();
+  BZR_HIP(hipMemcpy(ctx->ri_table + kRiTableFloats, table, count * sizeof(float), hipMemcpyHostToDevice));
+  ctx->gap_table_host.assign(table, table + count);
+  return BZR_OK;
+}
+// Every used entry of a gap table finite and above zero (a null table is vacuum).
+bzr_status check_gap_table(const float *gap_table, uint32_t nlens, uint32_t nchan) {
+  if (!gap_table) return BZR_OK;
+  for (size_t k = 0; k < (size_t)(nlens + 1) * nchan; ++k)
+    if (!(gap_table[k] > 0.0f) || !std::isfinite(gap_table[k]))
+      return set_error(BZR_ERR_INVALID_ARGUMENT, "gap_table entries must be finite and > 0");
   return BZR_OK;
 }
 bzr_status check_channels(const float *ri_table, uint32_t nchan) {
@@ -3215,6 +3347,10 @@ bzr_status run_chain(bzr_ctx *ctx, const LensSet &set, const TraceJob &job, uint
         o.opl = job.opl;
         o.opl_in = job.opl_in;
         o.glass = job.glass;
+        if constexpr (has_media(kMode)) {
+          o.gap_row = job.gap_table + (size_t)l * job.nchan;
+          o.gap_next = o.gap_row + job.nchan;
+        }
         if (bzr_status s = run_segment<kMode>(use_fast(flags), ctx, set.lens[l], o.first ? job.rays : job.out_rays, job.ld,
                                               off, m, o.first ? nullptr : (o.bounce_stage ? pend : job.status), o, w))
           return s;
@@ -3761,15 +3897,16 @@ extern "C" bzr_status bzr_refract(bzr_ctx *ctx, const bzr_mesh *mesh, float ri, 
 // bzr_trace_chain_tir (kModeTir: kModeSpectral with a null `channel` allowed, + max_bounces and out_bounces, an
 // optional plain [n] row).  The staged kModeTir chain keeps one more word per ray, the pending row, in the scratch.
 // bzr_trace_chain_opl (kModeOpl: kModeTir + opl_in, may be null, out_opl and the optional out_glass, plain [n] rows).
+// bzr_trace_chain_media (kModeMedia: kModeOpl + `gap`, the media table [nlens + 1][nchan] in host memory, null: vacuum).
 template <int kMode>
 static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
                               const float *rays, const float *weight_in, uint32_t n, float *out_rays, float *out_weight,
                               uint32_t *out_status, uint32_t *out_segments, uint32_t flags,
                               const uint8_t *channel = nullptr, uint32_t nchan = 0, uint32_t max_bounces = 0,
                               uint32_t *out_bounces = nullptr, const float *opl_in = nullptr, float *out_opl = nullptr,
-                              float *out_glass = nullptr) {
+                              float *out_glass = nullptr, const float *gap = nullptr) {
   constexpr bool kPower = has_power(kMode), kSpectral = has_channels(kMode), kTir = has_tir(kMode);
-  constexpr bool kOpl = kMode == kModeOpl;
+  constexpr bool kOpl = has_opl(kMode), kMedia = has_media(kMode);
   if (bzr_status s = check_flags(flags, true)) return s;
   if (!ctx) return set_error(BZR_ERR_INVALID_ARGUMENT, "null context");
   if (nlens == 0 || nlens > kMaxLenses) return set_error(BZR_ERR_INVALID_ARGUMENT, "nlens must be 1..8");
@@ -3778,6 +3915,8 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     if (!kTir && !channel) return set_error(BZR_ERR_INVALID_ARGUMENT, "null channel row");
     if (!out_weight) return set_error(BZR_ERR_INVALID_ARGUMENT, "null out_weight");
     if (max_bounces > BZR_MAX_BOUNCES) return set_error(BZR_ERR_INVALID_ARGUMENT, "max_bounces must be 0..8");
+    if (kMedia)
+      if (bzr_status s = check_gap_table(gap, nlens, nchan)) return s;
   }
   if (!lenses || !ri) return set_error(BZR_ERR_INVALID_ARGUMENT, "null lens list");
   LensSet set{};
@@ -3799,6 +3938,8 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
   const bool host = !(flags & BZR_DEVICE_PTRS), aos = (flags & BZR_RAYS_AOS) != 0;
   if (kSpectral)
     if (bzr_status s = upload_ri_table(ctx, ri, nlens, nchan)) return s;
+  if (kMedia)
+    if (bzr_status s = upload_gap_table(ctx, gap, nlens, nchan)) return s;
   const bool staged = !use_scan(flags) && use_staged(flags, n, max_patches(set));
   float *r = nullptr, *tmp = nullptr;  // tmp, host + AoS: the records on the device, in and out
   uint8_t *c = nullptr;
@@ -3832,9 +3973,9 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     d_rays = r;
   }
   if (use_scan(flags)) {
-    launch(ctx, BZR_KERNEL_CHAIN_SCAN, k_chain_scan<kOpl ? 4 : (kTir ? 3 : (kSpectral ? 2 : (kPower ? 1 : 0)))>,
+    launch(ctx, BZR_KERNEL_CHAIN_SCAN, k_chain_scan<kMedia ? 5 : kOpl ? 4 : (kTir ? 3 : (kSpectral ? 2 : (kPower ? 1 : 0)))>,
            dim3(grid_for(n)), set, d_rays, n, d_out, d_st, d_seg, d_win, d_w, d_ch, (const float *)ctx->ri_table, nchan, d_bnc,
-           max_bounces, d_oin, d_opl, d_glass);
+           max_bounces, d_oin, d_opl, d_glass, kMedia ? (const float *)ctx->ri_table + kRiTableFloats : nullptr);
     BZR_HIP(hipGetLastError());
   } else {
     TraceJob job{};
@@ -3853,6 +3994,7 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     job.opl = d_opl;
     job.opl_in = d_oin;
     job.glass = d_glass;
+    job.gap_table = kMedia ? ctx->ri_table + kRiTableFloats : nullptr;
     Work w;
     const uint32_t ch = staged ? chunk_for(ctx, n) : 0u;
     if (staged)
@@ -3917,6 +4059,19 @@ extern "C" bzr_status bzr_trace_chain_opl(bzr_ctx *ctx, const bzr_mesh *const *l
   if (max_bounces > BZR_MAX_BOUNCES) return set_error(BZR_ERR_INVALID_ARGUMENT, "max_bounces must be 0..8");
   return trace_chain<kModeOpl>(ctx, lenses, ri_table, nlens, rays, weight_in, n, out_rays, out_weight, out_status,
                                out_segments, flags, channel, nchan, max_bounces, out_bounces, opl_in, out_opl, out_glass);
+}
+
+extern "C" bzr_status bzr_trace_chain_media(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                            const float *gap_table, uint32_t nlens, uint32_t nchan, const float *rays,
+                                            const uint8_t *channel, const float *weight_in, const float *opl_in,
+                                            uint32_t n, uint32_t max_bounces, float *out_rays, float *out_weight,
+                                            uint32_t *out_status, uint32_t *out_segments, uint32_t *out_bounces,
+                                            float *out_opl, float *out_glass, uint32_t flags) {
+  if (!out_opl) return set_error(BZR_ERR_INVALID_ARGUMENT, "null out_opl");
+  if (max_bounces > BZR_MAX_BOUNCES) return set_error(BZR_ERR_INVALID_ARGUMENT, "max_bounces must be 0..8");
+  return trace_chain<kModeMedia>(ctx, lenses, ri_table, nlens, rays, weight_in, n, out_rays, out_weight, out_status,
+                                 out_segments, flags, channel, nchan, max_bounces, out_bounces, opl_in, out_opl, out_glass,
+                                 gap_table);
 }
 
 // ------------------------------------------------------------ test hook: normalized()

@@ -323,6 +323,36 @@ bzr_status bzr_trace_chain_opl(bzr_ctx *ctx, const bzr_mesh *const *lenses, cons
                                const float *opl_in, uint32_t n, uint32_t max_bounces, float *out_rays_soa,
                                float *out_weight, uint32_t *out_status, uint32_t *out_segments, uint32_t *out_bounces,
                                float *out_opl, float *out_glass, uint32_t flags);
+/* ---- surrounding media ----
+ * bzr_trace_chain_opl with a medium in front of, between and behind the lenses: an immersed optic, an emitter under an
+ * encapsulant, a cemented joint.  gap_table [nlens + 1][nchan] is row-major float32 and always host memory, like
+ * ri_table: row l is the index of the medium in front of lens l, row nlens that of the medium behind the last lens;
+ * NULL means every entry is 1.0f (vacuum).  For ray i with channel c in lens l let n0 = gap_table[l][c], n1 =
+ * ri_table[l][c] and n2 = gap_table[l + 1][c].  Apart from the following the call is bzr_trace_chain_opl: the same
+ * outputs, argument rules, flags, BZR_RAYS_AOS, host and device pointers, pipeline choice and chunking.
+ *   refract(INSIDE) segment:   eta = n0 / n1, one correctly rounded binary32 division on the device (for 1 / ri);
+ *   refract(OUTSIDE) segment:  eta = n1 / n2, one correctly rounded division (for ri), bounce segments included;
+ *   everything derived from eta uses this eta: s2 = eta eta (1 - cs cs), the refraction limit s2 < 0.99, the
+ *     reflection test s2 >= 1 of bzr_trace_chain_tir and the Fresnel term of bzr_trace_chain_power, in their operation
+ *     order, without contraction and exact under BZR_MODE_FAST as there;
+ *   per-leg step: a refract(INSIDE) leg adds m = n0 len; opl = opl + m (for opl + len); a refract(OUTSIDE) leg is
+ *     unchanged, glass = glass + len; m = n1 len; opl = opl + m.  out_glass stays the geometric length inside lens
+ *     glass: the gap media do not count;
+ *   every used gap_table entry must be finite and > 0, else BZR_ERR_INVALID_ARGUMENT before any output is touched
+ *     (ri_table is not validated, as in the other entry points).
+ * Since x / 1 = x and 1 x = x exactly, a gap_table of ones or NULL gives bzr_trace_chain_opl's outputs bit for bit, in
+ * every mode and on every pipeline.  The limits:
+ *   The chain stays sequential.  A ray that leaves lens l is in medium l + 1 whichever surface it left through (only
+ *     bounced rays can leave through the front).
+ *   A front surface never reflects.  A refract(INSIDE) segment from a denser medium with s2 >= 0.99 is NONE (cfg2 with
+ *     1.6 in front of 1.3: 102 more rays end NONE after one segment than in vacuum).
+ *   The illumination entry points, the multi-GPU plan and bzr_refract take no media. */
+bzr_status bzr_trace_chain_media(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                 const float *gap_table, uint32_t nlens, uint32_t nchan, const float *rays_soa,
+                                 const uint8_t *channel, const float *weight_in, const float *opl_in, uint32_t n,
+                                 uint32_t max_bounces, float *out_rays_soa, float *out_weight, uint32_t *out_status,
+                                 uint32_t *out_segments, uint32_t *out_bounces, float *out_opl, float *out_glass,
+                                 uint32_t flags);
 /* Refractive index from a dispersion formula, on the host (no context, no device): evaluated in binary64 and
  * rounded once to float.  wavelength_um [n] in micrometres, out_ri [n].
  *   BZR_DISPERSION_CAUCHY     n = A + B / l^2 + C / l^4           coeff = A, B[, C]             ncoeff 2 or 3

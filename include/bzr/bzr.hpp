@@ -477,6 +477,14 @@ void traceChainOpl(std::vector<BezierLens const *> const &lenses, std::vector<fl
                    uint8_t const *channels, float const *weights, float const *opl, std::size_t n, uint32_t maxBounces,
                    Ray *outRays, float *outWeights, RefractionResult *outStatus, float *outOpl, float *outGlass = nullptr,
                    uint32_t *outSegments = nullptr, uint32_t *outBounces = nullptr, Context *ctx = nullptr);
+// traceChainOpl with a medium in front of, between and behind the lenses (bzr_trace_chain_media): gapTable
+// [lenses.size() + 1][nchan] row-major, row l the index in front of lens l, the last row the index behind the last
+// lens; an empty gapTable is vacuum.  Throws if gapTable is neither empty nor (lenses.size() + 1) x nchan long.
+void traceChainMedia(std::vector<BezierLens const *> const &lenses, std::vector<float> const &riTable,
+                     std::vector<float> const &gapTable, Ray const *rays, uint8_t const *channels, float const *weights,
+                     float const *opl, std::size_t n, uint32_t maxBounces, Ray *outRays, float *outWeights,
+                     RefractionResult *outStatus, float *outOpl, float *outGlass = nullptr, uint32_t *outSegments = nullptr,
+                     uint32_t *outBounces = nullptr, Context *ctx = nullptr);
 // The same chain over several devices from one process (bzr_trace_tiled): tiles of tileRays
 // consecutive rays dealt round-robin to `ctxs` (one per device, distinct), results in input order.
 void traceChainTiled(std::vector<Context *> const &ctxs, std::vector<BezierLens const *> const &lenses,
