@@ -124,6 +124,7 @@ _SIGS = {
     "bzr_debug_unit": [_P, _P, _U32, _P],
     "bzr_debug_div_heights": [_P, _P, _U32, _P],
     "bzr_debug_bundle_setup": [_P, _P, _P, _U32, _P],
+    "bzr_debug_pass_order": [_P, _P, _P, _U32, _P],
     "bzr_debug_fast_unit": [_P, _P, _U32, _P],
     "bzr_debug_wave_clock": [_P, _P, _U32],
     "bzr_debug_wave_clock_rate": [_P, _P, _U32],

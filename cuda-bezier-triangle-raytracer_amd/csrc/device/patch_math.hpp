@@ -236,9 +236,18 @@ using namespace exact;
 // BezierTriangle::intersect (reference/bezierTriangle.cpp:123-195).  limitNone: 0 = cThis, 1 = cNone.
 // kGated: the caller has already evaluated the planar gate (:124-131) with this same arithmetic and
 // it passed (the culled pipeline's candidates), so its early returns are skipped -- same result bits.
+// kGated == kGatePlane: the caller guarantees that every lane of the call either passed the planar gate of this
+// same record (planar_gate: the arithmetic of the lines below, barycentric test included) or has limitNone set.
+// The barycentric test then cannot turn a lane away -- a gated lane's fl(M ip) is the value that already passed,
+// a limitNone lane skips it -- so fl(M ip) and its six comparisons are not evaluated; plane_ray and the height
+// test stay, because limitNone lanes (retries, parked evaluations) have passed no gate.  Same result bits.
+// trace.hip trace_segment's main Newton site is such a caller: its lanes are `run0` (in the entry's gate ballot,
+// limitNone false), `joined` or `spec` (limitNone true), and the three are disjoint -- a retry joins only a leaf
+// whose ballot it is not in, and `spec` requires !run0 && !joined.
 // kFast: the gate stays exact (same candidates as the reference), the rest runs in fast::.
 // need: newton_tail's hook (whether the last iteration's normal is evaluated; default: always).
-template <bool kGated = false, bool kFast = false, typename P, typename Need = NormalAlways>
+constexpr int kGateFull = 0, kGateDone = 1, kGatePlane = 2;  // (false / true name the first two)
+template <int kGated = kGateFull, bool kFast = false, typename P, typename Need = NormalAlways>
 __device__ __forceinline__ Hit patch_intersect(const P &p, f3 s, f3 d, bool limitNone, Need need = Need()) {
   Hit h;
   h.t = 0.0f;
@@ -251,14 +260,26 @@ __device__ __forceinline__ Hit patch_intersect(const P &p, f3 s, f3 d, bool limi
   float ic, it;
   bool valid = plane_ray(p.n(), p.c(), s, d, ip, ic, it);
   (void)valid;
-  if (!kGated) {
+  if (kGated != kGateDone) {
     if (!(valid && fabsf(it) > -p.hin() && fabsf(it) > p.hout())) return h;
-    f3 b0 = matvec(p, ip);
-    if (!(limitNone || (b0.x >= 0.0f && b0.x <= 1.0f && b0.y >= 0.0f && b0.y <= 1.0f && b0.z >= 0.0f && b0.z <= 1.0f)))
-      return h;
+    if (kGated == kGateFull) {
+      f3 b0 = matvec(p, ip);
+      if (!(limitNone || (b0.x >= 0.0f && b0.x <= 1.0f && b0.y >= 0.0f && b0.y <= 1.0f && b0.z >= 0.0f && b0.z <= 1.0f)))
+        return h;
+    }
   }
   if constexpr (kFast) return fast::newton_tail(p, s, d, ic, it, need);
   else return newton_tail(p, s, d, ic, it, need);
+}
+// The whole planar gate of patch_intersect<kGateFull> with cThis, from the full record: what a kGatePlane caller
+// promises for its lanes without limitNone (the counting kernels check it).
+template <typename P>
+__device__ __forceinline__ bool patch_gate(const P &p, f3 s, f3 d) {
+  f3 ip;
+  float ic, it;
+  if (!(plane_ray(p.n(), p.c(), s, d, ip, ic, it) && fabsf(it) > -p.hin() && fabsf(it) > p.hout())) return false;
+  const f3 b0 = matvec(p, ip);
+  return b0.x >= 0.0f && b0.x <= 1.0f && b0.y >= 0.0f && b0.y <= 1.0f && b0.z >= 0.0f && b0.z <= 1.0f;
 }
 
 }  // namespace bzr_dev

@@ -38,6 +38,7 @@
 #include "bzr.h"
 #include "ctx.hpp"
 #include "patch_math.hpp"
+#include "pass_order.hpp"
 #include "emitter.hpp"
 
 using namespace bzr_dev;
@@ -1884,10 +1885,12 @@ struct TraceCtr {  // wave-uniform work counters (kCount)
 // normal and cosine only it reads are not evaluated.  On entering a lens most rays pass the gates of a front
 // and a back patch, and the back patch's pass loses once the front one has run.  The vote is wave-uniform
 // (__any over the lanes in the call) and takes the same decision consider() takes: no output bit depends on it.
-// A losing pass is only short when its lanes' winners ran before it, so with 1 a batch of collected leaves is
-// first put in the order of their gates' plane distance (each entry's first passing lane's), near side first:
-// a stable lane-parallel rank over the <= kEntries entries.  The winner is the minimum of (t order, scanned
-// patch) over a set, so the order of the passes cannot reach it.  2: the vote without the reorder.
+// A losing pass is only short when its lanes' winners ran before it, so with 1 a batch of collected leaves runs
+// in the order of their gates' plane distance (each entry's first passing lane's), near side first, ties as
+// collected.  The order is kept up while the batch is collected (batch_append: each arriving leaf takes its place
+// in one word of nibbles, pass_order.hpp) and the pass loop reads the entries through it; nothing is sorted or
+// moved afterwards.  The winner is the minimum of (t order, scanned patch) over a set, so the order of the passes
+// cannot reach it.  2: the vote without the reorder.
 // cfg4: 26 % of the passes short (17.6 % with 2), each 242 of 2 130 VALU shorter; bench.py 11 503 -> 11 699 Mrays/s,
 // lone frames 4.344 -> 4.271 ms (2: 4.299); cfg2 in flight +2.9 %, lone frames 0.400 -> 0.414 ms
 // (profiles/r07_bench_ab.jsonl, r07_ab_short_cfg{4,2}.jsonl).
@@ -2019,9 +2022,34 @@ struct PassVote {
   }
 };
 
-// Order key of a collected entry: the gate's plane distance of its first passing lane (pm: the gate ballot).
+// Order key of a collected entry: the gate's plane distance of its first passing lane (pm: the gate ballot), as
+// raw bits -- a passing lane's t is > 0 (planar_gate), and among positive floats (+inf included) the bits order
+// and tie as t_order does.
 __device__ __forceinline__ uint32_t entry_key(float gt, unsigned long long pm) {
-  return t_order(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(gt), (int)__builtin_ctzll(pm))));
+  return (uint32_t)__builtin_amdgcn_readlane(__float_as_int(gt), (int)__builtin_ctzll(pm));
+}
+static_assert(kEntries <= kOrderEntries, "a batch's order is one word of nibbles (pass_order.hpp)");
+// Entry `ne` of the batch being collected (patch index, gate ballot and order key; all arguments but `lane` are
+// wave-uniform) goes to the list as collected, and the batch's order word takes it in: near side first (kOrder:
+// the stable ascending order of the keys, pass_order.hpp) or as collected.  The keys of the earlier entries are
+// read back one per lane; the order itself lives in two scalar registers, and no entry is moved.
+template <bool kOrder, typename Lds>
+__device__ __forceinline__ void batch_append(Lds &L, uint32_t ne, unsigned long long &order, uint32_t id,
+                                             unsigned long long pm, uint32_t key, uint32_t lane) {
+  uint32_t front = ne;
+  if constexpr (kOrder) {
+    front = 0u;
+    if (ne) {
+      __builtin_amdgcn_wave_barrier();
+      front = popc64(__ballot(L.ekey[lane & (kEntries - 1u)] <= key) & ((1ull << ne) - 1ull));
+    }
+  }
+  order = order_insert(order, ne, front);
+  if (lane == 0u) {
+    L.eid[ne] = id;
+    L.emask[ne] = pm;
+    if constexpr (kOrder) L.ekey[ne] = key;
+  }
 }
 
 // The lane's winner back from LDS (best != ~0).
@@ -2137,6 +2165,7 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
 #endif
   for (;;) {
     uint32_t ne = 0;  // collected leaves (uniform)
+    unsigned long long order = 0ull;  // nibble p: the entry whose pass runs p-th (uniform; pass_order.hpp)
     __builtin_amdgcn_s_setprio(3);  // the walk is latency-bound: issue it ahead of Newton passes
 #if BZR_TRACE_BUNDLE
     while (bwalk && ne < kEntries) {
@@ -2152,15 +2181,7 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
         }
         const unsigned long long pm = __ballot(pass);
         if (pm) {
-          const uint32_t key = kOrder ? entry_key(gt, pm) : 0u;
-          (void)key;
-          if (lane == 0u) {
-            L.eid[ne] = r[15];
-            L.emask[ne] = pm;
-#if BZR_TRACE_SHORT == 1
-            L.ekey[ne] = key;
-#endif
-          }
+          batch_append<kOrder>(L, ne, order, r[15], pm, kOrder ? entry_key(gt, pm) : 0u, lane);
           ++ne;
         }
         continue;
@@ -2235,15 +2256,7 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
           }
           const unsigned long long pm = __ballot(pass);
           if (pm) {
-            const uint32_t key = kOrder ? entry_key(gt, pm) : 0u;
-            (void)key;
-            if (lane == 0u) {
-              L.eid[ne] = r[15];
-              L.emask[ne] = pm;
-#if BZR_TRACE_SHORT == 1
-              L.ekey[ne] = key;
-#endif
-            }
+            batch_append<kOrder>(L, ne, order, r[15], pm, kOrder ? entry_key(gt, pm) : 0u, lane);
             ++ne;
           }
         } else {
@@ -2278,15 +2291,7 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
       }
       const unsigned long long pm = __ballot(pass);
       if (pm) {
-        const uint32_t key = kOrder ? entry_key(gt, pm) : 0u;
-        (void)key;
-        if (lane == 0u) {
-          L.eid[ne] = b;
-          L.emask[ne] = pm;
-#if BZR_TRACE_SHORT == 1
-          L.ekey[ne] = key;
-#endif
-        }
+        batch_append<kOrder>(L, ne, order, b, pm, kOrder ? entry_key(gt, pm) : 0u, lane);
         ++ne;
       }
     }
@@ -2313,58 +2318,41 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
       ne = 1;
       ++scan;
     }
-    // the collected leaves' passes, in order
+    // the collected leaves' passes, in the batch's order: the next entry is the order word's lowest nibble, and
+    // `todo` (uniform, one bit per entry; ne <= 16) holds the entries whose passes are still to come -- what the
+    // join and park logic below looks among.  (The full scan's single entry: order 0, entry 0.)
     __builtin_amdgcn_s_setprio(0);
-    if (kOrder && ne >= 2u) {
-      // near side first: lane e < ne ranks entry e among the batch's keys (stable: ties keep their order) and
-      // moves its index and ballot to that place; the join and park logic below sees the permuted list only
-      const uint32_t slot = lane & (kEntries - 1u);
-#if BZR_TRACE_SHORT == 1
-      const uint32_t ekey = L.ekey[slot];
-#else
-      const uint32_t ekey = 0u;
-#endif
-      uint32_t rank = 0;  // < ne for the lanes below ne: a permutation of [0, ne)
-      for (uint32_t j = 0; j < ne; ++j) {
-        const uint32_t kj = (uint32_t)__builtin_amdgcn_readlane((int)ekey, (int)j);
-        rank += (kj < ekey || (kj == ekey && j < lane)) ? 1u : 0u;
-      }
-      const uint32_t id = L.eid[slot];
-      const unsigned long long em = L.emask[slot];
-      __builtin_amdgcn_wave_barrier();
-      if (lane < ne) {
-        L.eid[rank] = id;
-        L.emask[rank] = em;
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-    for (uint32_t e = 0; e < ne; ++e) {
-      const uint32_t b = __builtin_amdgcn_readfirstlane(L.eid[e]);
+    for (uint32_t todo = (1u << ne) - 1u; todo; order >>= 4) {
+      const uint32_t ei = order_at(order, 0u);
+      todo ^= 1u << ei;
+      const bool more = todo != 0u;
+      const uint32_t b = __builtin_amdgcn_readfirstlane(L.eid[ei]);
       const auto hp = uniform_patch(m.full, b);
-      const bool run0 = lane_bit(uniform_u64(L.emask[e]), lane);
+      const bool run0 = lane_bit(uniform_u64(L.emask[ei]), lane);
       const bool joined = join == b;  // an earlier leaf's retry on this one
       const uint32_t sidx = joined ? join_src : b;
       if (joined) join = kNo;
       bool spec = false;  // park this leaf's cNone result for lanes of later leaves that neighbour it
-      if (kPark && e + 1u < ne) {
+      if (kPark && more) {
         unsigned long long sm = 0ull;
 #pragma unroll
         for (uint32_t side = 0; side < 3u; ++side) {
           const uint32_t nb = __float_as_uint(hp.r[rec::kNeigh + side]);
-          const unsigned long long later = __ballot(lane > e && lane < ne && L.eid[lane & (kEntries - 1u)] == nb);
+          const unsigned long long later = __ballot(L.eid[lane & (kEntries - 1u)] == nb) & todo;
           if (later) sm |= uniform_u64(L.emask[__builtin_ctzll(later)]);
         }
         spec = lane_bit(sm, lane) && !run0 && !joined && parked_nb == kNo;
       }
       if (kCount) {
         ++ctr.rounds;
-        ctr.pairs += popc64(__ballot(run0));
+        // (kGatePlane's promise, checked here: a run0 lane that the record's own gate turns away is no pair)
+        ctr.pairs += popc64(__ballot(run0 && patch_gate(hp, s, d)));
         ctr.follows += popc64(__ballot(joined));
       }
       uint32_t what = kNone;
       bool skipped = false;
       if (run0 || joined || spec) {
-        const Hit h = patch_intersect<false, kFast>(hp, s, d, joined || spec, PassVote{best, sidx, spec, &skipped});
+        const Hit h = patch_intersect<kGatePlane, kFast>(hp, s, d, joined || spec, PassVote{best, sidx, spec, &skipped});
         if (spec) {
           park(h, L, lane);
           parked_nb = b;
@@ -2388,7 +2376,7 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
           if (!__any(fl)) continue;
         }
         // the neighbour among the leaves still to come: the retry joins its pass
-        const unsigned long long later = __ballot(lane > e && lane < ne && L.eid[lane & (kEntries - 1u)] == nb);
+        const unsigned long long later = __ballot(L.eid[lane & (kEntries - 1u)] == nb) & todo;
         if (later) {
           const unsigned long long fm = uniform_u64(L.emask[__builtin_ctzll(later)]);
           if (fl && join == kNo && !lane_bit(fm, lane)) {
@@ -4121,6 +4109,33 @@ __global__ __launch_bounds__(64) void k_debug_bundle_setup(const float *__restri
   if (lane < kBundleWords) o[lane] = bl[lane];
   if (lane == kBundleWords) o[lane] = spread;
 }
+// The fused pass loop's near-first order (batch_append), one wave and one key sequence per block: entry e of
+// sequence w has key keys[16 w + e], patch index e and the ballot kDebugBallot * (e + 1); row w of out = the batch in
+// the order its passes would run, 3 words per place (index, ballot low, ballot high; 0xFFFFFFFF past the length).
+constexpr unsigned long long kDebugBallot = 0x9E3779B97F4A7C15ull;
+struct DebugBatchLds {
+  unsigned long long emask[kEntries];
+  uint32_t eid[kEntries];
+  uint32_t ekey[kEntries];
+};
+__global__ __launch_bounds__(64) void k_debug_pass_order(const uint32_t *__restrict__ keys,
+                                                         const uint32_t *__restrict__ len, uint32_t *__restrict__ out) {
+  __shared__ DebugBatchLds L;
+  const uint32_t lane = threadIdx.x, w = blockIdx.x;
+  const uint32_t n = min(__builtin_amdgcn_readfirstlane(len[w]), kEntries);
+  unsigned long long order = 0ull;
+  for (uint32_t e = 0; e < n; ++e)
+    batch_append<true>(L, e, order, e, kDebugBallot * (e + 1u), __builtin_amdgcn_readfirstlane(keys[kEntries * w + e]),
+                       lane);
+  __builtin_amdgcn_wave_barrier();
+  if (lane < kEntries) {
+    const uint32_t ei = order_at(order, lane);
+    uint32_t *o = out + (size_t)3 * (kEntries * w + lane);
+    o[0] = lane < n ? L.eid[ei] : 0xFFFFFFFFu;
+    o[1] = lane < n ? (uint32_t)L.emask[ei] : 0xFFFFFFFFu;
+    o[2] = lane < n ? (uint32_t)(L.emask[ei] >> 32) : 0xFFFFFFFFu;
+  }
+}
 // BZR_MODE_FAST's primitives (patch_math.hpp namespace fast): row 0 div_rn(a0, a1), row 1 sqrt_rn(|a0|), rows 2..4
 // normalized(a).
 __global__ __launch_bounds__(kBlock) void k_debug_fast_unit(const float *__restrict__ a, uint32_t n,
@@ -4166,6 +4181,18 @@ extern "C" bzr_status bzr_debug_bundle_setup(void *ctxp, const float *rays, cons
   if (n % 64u) return set_error(BZR_ERR_INVALID_ARGUMENT, "n must be whole waves of 64 rays");
   DeviceGuard g(ctx->device);
   hipLaunchKernelGGL(k_debug_bundle_setup, dim3(n / 64u), dim3(64), 0, ctx->stream, rays, active, n, out);
+  BZR_HIP(hipGetLastError());
+  return BZR_OK;
+}
+
+extern "C" bzr_status bzr_debug_pass_order(void *ctxp, const uint32_t *keys, const uint32_t *len, uint32_t n,
+                                           uint32_t *out) {
+  bzr_ctx *ctx = static_cast<bzr_ctx *>(ctxp);
+  if (!ctx) return set_error(BZR_ERR_INVALID_ARGUMENT, "null context");
+  if (n == 0) return BZR_OK;
+  if (!keys || !len || !out) return set_error(BZR_ERR_INVALID_ARGUMENT, "null buffer");
+  DeviceGuard g(ctx->device);
+  hipLaunchKernelGGL(k_debug_pass_order, dim3(n), dim3(64), 0, ctx->stream, keys, len, out);
   BZR_HIP(hipGetLastError());
   return BZR_OK;
 }

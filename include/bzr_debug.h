@@ -83,6 +83,13 @@ int32_t bzr_debug_div_heights(void *ctx, const float *a, uint32_t n, float *out)
  * hi; direction box lo, hi; finite flag; 1 / Dl', 1 / Dh'; mixed flags) and the returned direction spread.
  * Asynchronous on the context's stream. */
 int32_t bzr_debug_bundle_setup(void *ctx, const float *rays, const uint8_t *active, uint32_t n, float *out);
+/* Device check of the fused pass loop's near-first order (trace.hip batch_append / batch_store over pass_order.hpp:
+ * the insertion the trace kernels run while they collect a batch of leaves).  n key sequences, one wave each: `keys`
+ * device memory [n][16], `len` device memory [n] (<= 16 entries used), `out` device memory [n][16][3].  Entry e of a
+ * sequence carries patch index e and the ballot 0x9E3779B97F4A7C15 * (e + 1); out[w][p] = the index and the ballot
+ * (low, high word) of the entry at place p of the list the passes read -- the stable ascending order of the keys --
+ * and 0xFFFFFFFF words at and past len[w].  Asynchronous on the context's stream. */
+int32_t bzr_debug_pass_order(void *ctx, const uint32_t *keys, const uint32_t *len, uint32_t n, uint32_t *out);
 /* Device check of BZR_MODE_FAST's primitives (patch_math.hpp namespace fast): `a` device memory [3][n], `out`
  * device memory [5][n]: row 0 fast::div_rn(a0, a1), row 1 fast::sqrt_rn(|a0|), rows 2-4 fast::normalized(a).
  * Asynchronous on the context's stream. */
