@@ -81,6 +81,9 @@ _SIGS = {
     "bzr_trace_chain_tir": [_P, _P, _P, _U32, _U32, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _U32],
     "bzr_trace_chain_opl": [_P, _P, _P, _U32, _U32, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _U32],
     "bzr_trace_chain_media": [_P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _U32],
+    "bzr_trace_chain_absorb": [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P,
+                               _U32],
+    "bzr_absorption_from_transmittance": [_P, _U32, ctypes.c_double, _P],
     "bzr_dispersion_index": [_I32, _P, _U32, _P, _U32, _P],
     "bzr_trace_tiled": [_P, _U32, _P, _P, _U32, _P, _U32, _U32, _P, _P, _P, _U32],
     "bzr_tiled_create": [_P, _U32, _U32, _U32, _U32, _I32, ctypes.POINTER(_P)],
@@ -100,6 +103,8 @@ _SIGS = {
     "bzr_illuminate_spectral": [_P, _P, _P, _U32, _U32, _P, ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _U32],
     "bzr_illuminate_tir": [_P, _P, _P, _U32, _U32, _P, ctypes.c_uint64, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P,
                            _U32],
+    "bzr_illuminate_media": [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, ctypes.c_uint64, _P, _P, _U32, _P, _P, _P, _P, _P,
+                             _P, _P, _P, _U32],
     "bzr_mesh_bounding_sphere": [_P, _P],
     "bzr_trimesh_create": [ctypes.POINTER(_P)],
     "bzr_trimesh_destroy": [_P],
@@ -131,11 +136,13 @@ _SIGS = {
     "bzr_debug_chunk_plan": [ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(_U32), ctypes.POINTER(_U32)],
     "bzr_debug_chunk_cap": [_P, _U32, ctypes.POINTER(_U32)],
     "bzr_debug_fresnel": [_P, _P, _U32, _P],
+    "bzr_debug_attenuation": [_P, _P, _U32, _P],
 }
 # entry points added without an ABI bump: an explicitly chosen earlier build (BZR_LIBRARY) may lack them
 _ADDED = ("bzr_trace_chain_power", "bzr_illuminate_power", "bzr_trace_chain_spectral", "bzr_illuminate_spectral",
           "bzr_dispersion_index", "bzr_trace_chain_tir", "bzr_illuminate_tir", "bzr_trace_chain_opl",
-          "bzr_trace_chain_media")
+          "bzr_trace_chain_media", "bzr_trace_chain_absorb", "bzr_absorption_from_transmittance",
+          "bzr_illuminate_media", "bzr_debug_attenuation")
 _RET = {"bzr_last_error": ctypes.c_char_p, "bzr_abi_version": _I32}
 
 _lib = None
@@ -598,6 +605,76 @@ def trace_chain_media(ctx: Context, lenses, ri_table, gap_table, rays, channel=N
     return out_rays, out_weight, out_status, out_segments, out_bounces, out_opl, out_glass
 
 
+def _absorb_table(table, name, nl, nchan):
+    """An absorption table [nlens, nchan] as contiguous float32, or None."""
+    if table is None:
+        return None
+    a = np.ascontiguousarray(table, dtype=np.float32)
+    if a.shape != (nl, nchan):
+        raise BzrError(f"{name} must be [nlens = {nl}, nchan = {nchan}], got {a.shape}")
+    return a
+
+
+def _gap_table(gap_table, nl, nchan):
+    if gap_table is None:
+        return None
+    gap = np.ascontiguousarray(gap_table, dtype=np.float32)
+    if gap.shape != (nl + 1, nchan):
+        raise BzrError(f"gap_table must be [nlens + 1 = {nl + 1}, nchan = {nchan}], got {gap.shape}")
+    return gap
+
+
+def _table_ptr(a):
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def trace_chain_absorb(ctx: Context, lenses, ri_table, gap_table, glass_absorb, gap_absorb, rays, channel=None, weight=None,
+                       opl=None, max_bounces=4, out_rays=None, out_weight=None, out_status=None, out_segments=None,
+                       out_bounces=None, out_opl=None, out_glass=None, mode=MODE_PARITY):
+    """trace_chain_media with Beer-Lambert absorption along the legs -> the same seven-tuple.  glass_absorb and
+    gap_absorb [nlens, nchan] float32 (host): the Napierian absorption coefficient per unit length of lens l's glass and
+    of the medium in front of lens l (gap_table's row l); None is all zero, and with both zero the result is
+    trace_chain_media's bit for bit.  Every leg that ends in a refraction or a reflection multiplies the weight by
+    att(a x its length) ahead of the Fresnel term; only the weight depends on the two tables.  Every entry must be
+    finite and not below 0 (bzr.h bzr_trace_chain_absorb)."""
+    n = _n_of(rays, mode)
+    nl = len(lenses)
+    handles = (_P * nl)(*[m.handle for m in lenses])
+    table, nchan = _ri_table(ri_table, nl)
+    gap = _gap_table(gap_table, nl, nchan)
+    ga, pa = _absorb_table(glass_absorb, "glass_absorb", nl, nchan), _absorb_table(gap_absorb, "gap_absorb", nl, nchan)
+    out_rays = _empty_like(rays, 6, np.float32, mode) if out_rays is None else out_rays
+    out_weight = _empty_like(rays, 0, np.float32, mode) if out_weight is None else out_weight
+    out_status = _empty_like(rays, 0, np.uint32, mode) if out_status is None else out_status
+    out_segments = _empty_like(rays, 0, np.uint32, mode) if out_segments is None else out_segments
+    out_bounces = _empty_like(rays, 0, np.uint32, mode) if out_bounces is None else out_bounces
+    out_opl = _empty_like(rays, 0, np.float32, mode) if out_opl is None else out_opl
+    if out_glass is False:
+        out_glass = None
+    elif out_glass is None:
+        out_glass = _empty_like(rays, 0, np.float32, mode)
+    r, c, wi, pi = _Buf(rays, np.float32), _Buf(channel, np.uint8), _Buf(weight, np.float32), _Buf(opl, np.float32)
+    o, w = _Buf(out_rays, np.float32, True), _Buf(out_weight, np.float32, True)
+    s, g, b = _Buf(out_status, np.uint32, True), _Buf(out_segments, np.uint32, True), _Buf(out_bounces, np.uint32, True)
+    p, q = _Buf(out_opl, np.float32, True), _Buf(out_glass, np.float32, True)
+    res = _residency(r, c, o, w, s, g, b, wi, pi, p, q)
+    with _stream_for(ctx, res):
+        _check(lib().bzr_trace_chain_absorb(ctx.handle, ctypes.cast(handles, _P), table.ctypes.data if table.size else None,
+                                            _table_ptr(gap), _table_ptr(ga), _table_ptr(pa), nl, nchan, r.ptr, c.ptr,
+                                            wi.ptr, pi.ptr, n, int(max_bounces), o.ptr, w.ptr, s.ptr, g.ptr, b.ptr, p.ptr,
+                                            q.ptr, res | mode))
+    return out_rays, out_weight, out_status, out_segments, out_bounces, out_opl, out_glass
+
+
+def absorption_from_transmittance(internal_transmittance, thickness: float) -> np.ndarray:
+    """Absorption coefficients a = -ln(T) / thickness, float32, from a catalogue's internal transmittance T at a
+    thickness, per unit of the length the thickness is given in.  Host only (bzr.h bzr_absorption_from_transmittance)."""
+    t = np.ascontiguousarray(internal_transmittance, np.float64)
+    out = np.empty(t.shape, np.float32)
+    _check(lib().bzr_absorption_from_transmittance(t.ctypes.data, t.size, float(thickness), out.ctypes.data))
+    return out
+
+
 def dispersion_index(model: int, coeff, wavelength_um) -> np.ndarray:
     """Refractive index at each wavelength (micrometres) from a dispersion formula, float32: DISPERSION_CAUCHY
     (coeff A, B[, C]: n = A + B / l^2 + C / l^4) or DISPERSION_SELLMEIER (coeff B1, C1, B2, C2, ...:
@@ -899,6 +976,29 @@ def illuminate_tir(ctx: Context, lenses, ri_table, em: Emitter, total_rays: int,
     [nchan, LEDGER_ROWS, LEDGER_FIELDS], every traced ray of channel c in row min(bounces, MAX_BOUNCES) under
     LEDGER_LOST (ended NONE) or LEDGER_EXITED (left the last lens), and under LEDGER_LANDED too if it met the target;
     "power" sums the rays' final weights in the maps' 32.32 fixed point (bzr.h bzr_illuminate_tir)."""
+    return _illuminate_reflecting(ctx, lenses, ri_table, None, em, total_rays, target, max_bounces, emission, surface,
+                                  flux, hist, reflected_flux, reflected_hist, mode)
+
+
+def illuminate_media(ctx: Context, lenses, ri_table, gap_table, glass_absorb, gap_absorb, em: Emitter, total_rays: int,
+                     target: Target, max_bounces=4, emission=EMISSION_LAMBERT, surface=SURFACE_FRESNEL, flux=None,
+                     hist=None, reflected_flux=None, reflected_hist=None, mode=MODE_PARITY):
+    """illuminate_tir over trace_chain_absorb's chain -> the same seven-tuple.  gap_table [nlens + 1, nchan] and
+    glass_absorb / gap_absorb [nlens, nchan] are trace_chain_absorb's (None: vacuum, all zero).  The emitter sits in the
+    medium gap_table[0]; the leg from the last lens to the target is neither refracted again nor attenuated.  With
+    absorption the ledger's LOST + EXITED power falls short of EMITTED - CULLED under SURFACE_LOSSLESS by what the media
+    absorbed; with vacuum and zero tables every output is illuminate_tir's bit for bit (bzr.h bzr_illuminate_media)."""
+    nl = len(lenses)
+    _, nchan = _ri_table(ri_table, nl)
+    media = (_gap_table(gap_table, nl, nchan), _absorb_table(glass_absorb, "glass_absorb", nl, nchan),
+             _absorb_table(gap_absorb, "gap_absorb", nl, nchan))
+    return _illuminate_reflecting(ctx, lenses, ri_table, media, em, total_rays, target, max_bounces, emission, surface,
+                                  flux, hist, reflected_flux, reflected_hist, mode)
+
+
+def _illuminate_reflecting(ctx, lenses, ri_table, media, em, total_rays, target, max_bounces, emission, surface, flux, hist,
+                           reflected_flux, reflected_hist, mode):
+    """illuminate_tir (media None) or illuminate_media (media = the gap table and the two absorption tables)."""
     nl = len(lenses)
     handles = (_P * nl)(*[m.handle for m in lenses])
     table, nchan = _ri_table(ri_table, nl)
@@ -925,11 +1025,14 @@ def illuminate_tir(ctx: Context, lenses, ri_table, em: Emitter, total_rays: int,
     stats, power = (ctypes.c_uint64 * (4 * rows))(), (ctypes.c_uint64 * (4 * rows))()
     ledger = {k: np.zeros((rows, LEDGER_ROWS, LEDGER_FIELDS), np.uint64) for k in ("count", "power")}
     res = _residency(f, h, rf, rh)
+    tail = (nl, nchan, ctypes.byref(em), int(total_rays), ctypes.byref(target), ctypes.byref(rad), int(max_bounces), f.ptr,
+            h.ptr, rf.ptr, rh.ptr, stats, power, ledger["count"].ctypes.data, ledger["power"].ctypes.data, res | mode)
     with _stream_for(ctx, res):
-        _check(lib().bzr_illuminate_tir(ctx.handle, handles, table.ctypes.data if table.size else None, nl, nchan,
-                                        ctypes.byref(em), int(total_rays), ctypes.byref(target), ctypes.byref(rad),
-                                        int(max_bounces), f.ptr, h.ptr, rf.ptr, rh.ptr, stats, power,
-                                        ledger["count"].ctypes.data, ledger["power"].ctypes.data, res | mode))
+        if media is None:
+            _check(lib().bzr_illuminate_tir(ctx.handle, handles, table.ctypes.data if table.size else None, *tail))
+        else:
+            _check(lib().bzr_illuminate_media(ctx.handle, handles, table.ctypes.data if table.size else None,
+                                              *[_table_ptr(a) for a in media], *tail))
     return (flux, hist, reflected_flux, reflected_hist,
             [dict(zip(ILLUM_STATS, [int(x) for x in stats[4 * c:4 * c + 4]])) for c in range(nchan)],
             [dict(zip(ILLUM_STATS, [int(x) for x in power[4 * c:4 * c + 4]])) for c in range(nchan)],
@@ -950,6 +1053,17 @@ def debug_fresnel(eta, cs) -> np.ndarray:
         raise BzrError("eta and cs must be 1-D arrays of one length")
     out = np.empty(e.shape, np.float32)
     _check(lib().bzr_debug_fresnel(e.ctypes.data, c.ctypes.data, e.size, out.ctypes.data))
+    return out
+
+
+def debug_attenuation(x, ctx: Context = None) -> np.ndarray:
+    """bzr_debug_attenuation: the chain's Beer-Lambert term att(x) for x >= 0 (or NaN), evaluated on the host (ctx None)
+    or by one kernel on the context's device; the two agree bit for bit."""
+    a = np.ascontiguousarray(x, np.float32)
+    if a.ndim != 1:
+        raise BzrError("x must be a 1-D array")
+    out = np.empty(a.shape, np.float32)
+    _check(lib().bzr_debug_attenuation(ctx.handle if ctx is not None else None, a.ctypes.data, a.size, out.ctypes.data))
     return out
 
 

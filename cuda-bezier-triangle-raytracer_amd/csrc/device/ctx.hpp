@@ -55,6 +55,9 @@ struct bzr_ctx {
   // kModeMedia's gap table [nlens + 1][nchan] lies in the same buffer behind the index table's rows, with a host copy
   // of its own: the two halves are compared and rewritten separately (trace.hip upload_gap_table).
   std::vector<float> gap_table_host;
+  // kModeAbsorb's two absorption tables [nlens][nchan] lie behind the gap table, each part with its own host copy
+  // (trace.hip upload_absorb_table).
+  std::vector<float> glass_absorb_host, gap_absorb_host;
 };
 
 // BZR_RAYS_AOS (frame_pack.hip): n rays between the reference's [n][6] records and the kernels' [6][n] rows,

@@ -127,6 +127,8 @@ constexpr uint32_t kFollow2 = 2u, kNone = 3u, kIntersect = 4u;
 namespace exact {
 __device__ __forceinline__ float div_rn(float a, float b) { return a / b; }
 __device__ __forceinline__ float sqrt_rn(float a) { return __builtin_sqrtf(a); }
+__device__ __forceinline__ float bits_f32(uint32_t u) { return __uint_as_float(u); }
+__device__ __forceinline__ float rint_even(float y) { return __builtin_rintf(y); }  // v_rndne_f32
 
 // The two sequences above, as LLVM lowers them for gfx950, minus their range handling:
 //   sqrt: v_sqrt_f32, then the neighbours s -/+ 1 ulp are tested with fma residuals; LLVM first scales
@@ -215,6 +217,8 @@ namespace fast {
 #pragma clang fp contract(fast)
 __device__ __forceinline__ float div_rn(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 __device__ __forceinline__ float sqrt_rn(float a) { return __builtin_amdgcn_sqrtf(a); }
+__device__ __forceinline__ float bits_f32(uint32_t u) { return __uint_as_float(u); }
+__device__ __forceinline__ float rint_even(float y) { return __builtin_rintf(y); }
 __device__ __forceinline__ bool sqrt_above_hundredth(float z) { return sqrt_rn(z) > 0.01f; }
 __device__ __forceinline__ f3 unit_or_self(f3 a, float z) {
   if (!(z > 0.0f)) return a;

@@ -3,13 +3,15 @@
 //                     correctly rounded div/sqrt: bit-identical to the oracle (BZR_MODE_PARITY)
 //   namespace fast    the same expressions with FMA contraction and the hardware's approximate
 //                     reciprocal / square root (BZR_MODE_FAST, the Newton stage only)
-// Each namespace defines div_rn, sqrt_rn, sqrt_above_hundredth, unit_or_self(a, |a|^2) and
-// div_heights(hIn, hOut, cos, hIn / cos, hOut / cos) before including this file.
+// Each namespace defines div_rn, sqrt_rn, sqrt_above_hundredth, unit_or_self(a, |a|^2),
+// div_heights(hIn, hOut, cos, hIn / cos, hOut / cos), bits_f32(u) (the float with these bits) and rint_even(y)
+// (round to the nearest integer, ties to even) before including this file.
 //   plane_ray        reference/3dGeomUtil.h:279-296 (+ deviations D1/D2, DESIGN.md)
 //   interpolate      reference/bezierTriangle.cpp:105-121
 //   surface_normal   reference/bezierTriangle.cpp:197-233
 //   newton_tail      reference/bezierTriangle.cpp:132-195
 //   fresnel_t        no reference counterpart: the transmittance of a refraction (DESIGN.md (a), ray power)
+//   att              no reference counterpart: the Beer-Lambert term of one leg (DESIGN.md (a), absorption)
 __device__ __forceinline__ f3 add(f3 a, f3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
 __device__ __forceinline__ f3 sub(f3 a, f3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
 __device__ __forceinline__ f3 scale(f3 a, float s) { return mk(a.x * s, a.y * s, a.z * s); }
@@ -32,6 +34,36 @@ __device__ __forceinline__ float fresnel_t(float eta, float cs, float s2) {
   const float b = eta * c2;
   const float rp = div_rn(b - c1, b + c1);
   return 1.0f - 0.5f * (rs * rs + rp * rp);
+}
+
+// Beer-Lambert attenuation of one leg, att(x) ~ exp(-x) for x = a len >= 0 (DESIGN.md (a), absorption).  No
+// correctly rounded expf exists to lean on, so the term is defined by its operations, each rounded once in binary32:
+// y = x log2(e); k = rint(y), an integer in 0 .. 125; f = y - k, exact, |f| <= 1/2; 2^-f by a degree-7 Horner
+// polynomial with c_j = float((-ln 2)^j / j!); times 2^-k, an exact scaling.  y >= 125 (and a NaN) gives 0, so the
+// result is 0 or normal.  c_0 = 1: att(0) = 1.  Not monotone in the last bit.
+__device__ __forceinline__ float att(float x) {
+  const float y0 = x * bits_f32(0x3FB8AA3Bu);
+  const bool live = y0 < 125.0f;
+  const float y = live ? y0 : 0.0f;  // (a select, not a branch: the dead lanes run the polynomial on 0)
+  const float k = rint_even(y);
+  const float f = y - k;
+  float p = bits_f32(0xb77fe5feu);
+  p = p * f;
+  p = p + bits_f32(0x39218489u);
+  p = p * f;
+  p = p + bits_f32(0xbaaec3ffu);
+  p = p * f;
+  p = p + bits_f32(0x3c1d955bu);
+  p = p * f;
+  p = p + bits_f32(0xbd635847u);
+  p = p * f;
+  p = p + bits_f32(0x3e75fdf0u);
+  p = p * f;
+  p = p + bits_f32(0xbf317218u);
+  p = p * f;
+  p = p + 1.0f;
+  const float r = p * bits_f32((127u - (uint32_t)(int32_t)k) << 23);
+  return live ? r : 0.0f;
 }
 
 template <typename P>

@@ -413,6 +413,22 @@ __device__ __forceinline__ void opl_leg_media(f3 s, f3 p, float nm, bool in_glas
   const float m = nm * len;
   opl = opl + m;
 }
+// kModeAbsorb's form: opl_leg_media that also hands back the leg's length, for the Beer-Lambert term.  (A sibling: the
+// older instantiations keep the function they had.)
+__device__ __forceinline__ float opl_leg_absorb(f3 s, f3 p, float nm, bool in_glass, float &opl, float &glass) {
+  const f3 e = sub(p, s);
+  const float len = sqrt_rn(dot(e, e));
+  if (in_glass) glass = glass + len;
+  const float m = nm * len;
+  opl = opl + m;
+  return len;
+}
+// The leg's attenuation: att(a len), and exactly 1 where the coefficient is 0 (the select keeps 0 x inf out of the
+// weight, so zero tables give kModeMedia's bits whatever the leg).
+__device__ __forceinline__ float leg_attenuation(float a, float len) {
+  const float x = a * len;
+  return a > 0.0f ? att(x) : 1.0f;
+}
 
 __device__ __forceinline__ void load_ray(const float *__restrict__ r, uint32_t n, uint32_t i, f3 &s, f3 &d) {
   s = mk(r[i], r[(size_t)n + i], r[(size_t)2 * n + i]);
@@ -549,12 +565,22 @@ constexpr uint32_t kSlotWords = 12;  // t, point, cos, bary, normal, source patc
 // index in front of lens l, row `count` the one behind the last lens.  Snell's step, the reflection test, the Fresnel
 // term (refract_eta_t, tir_eta_t) and the leg in front of a lens (opl_leg_media) read them.  A mode of its own once
 // more: the other seven compile to the code they had.
+// The context's table buffer (upload_ri_table): the index table, kModeMedia's gap table kGapPart floats long, then
+// kModeAbsorb's two parts of kAbsorbPart floats each, the glass's and the front media's.  A kModeAbsorb job reaches
+// both through its gap_table pointer: with a pointer of their own in TraceJob the two non-counting k_trace<kModeAbsorb>
+// came out with 36 B of scratch reserved (never accessed), in every order of the tail that was tried (DESIGN (a)).
+constexpr uint32_t kGapPart = (kMaxLenses + 1u) * BZR_MAX_CHANNELS, kAbsorbPart = kMaxLenses * BZR_MAX_CHANNELS;
+// kModeAbsorb: kModeMedia with Beer-Lambert absorption -- every leg that ends in a refraction or a reflection
+// multiplies the weight by att(a len) (leg_attenuation), a = gap_absorb[l][channel[i]] in front of lens l and
+// glass_absorb[l][channel[i]] inside it, ahead of the Fresnel gain; a reflection now touches the weight.  A mode of its
+// own again: the other eight compile to the code they had.
 enum OutMode {
   kModeHits = 0, kModeRefract = 1, kModeStage = 2, kModePower = 3, kModeSpectral = 4, kModeTir = 5, kModeOpl = 6,
-  kModeMedia = 7
+  kModeMedia = 7, kModeAbsorb = 8
 };
-constexpr bool has_media(int mode) { return mode == kModeMedia; }
-constexpr bool has_opl(int mode) { return mode == kModeOpl || mode == kModeMedia; }
+constexpr bool has_absorb(int mode) { return mode == kModeAbsorb; }
+constexpr bool has_media(int mode) { return mode == kModeMedia || has_absorb(mode); }
+constexpr bool has_opl(int mode) { return mode == kModeOpl || has_media(mode); }
 constexpr bool is_stage(int mode) {
   return mode == kModeStage || mode == kModePower || mode == kModeSpectral || mode == kModeTir || has_opl(mode);
 }
@@ -593,6 +619,8 @@ struct Out {
   float *glass;              // optional
   // kModeMedia: the rows of the gap table [nchan] in front of this lens and behind it (device memory, like ri_row)
   const float *gap_row, *gap_next;
+  // kModeAbsorb: this lens's rows of the two absorption tables [nchan] (device memory): its glass, the medium in front
+  const float *glass_absorb, *gap_absorb;
 };
 
 template <int kMode>
@@ -627,12 +655,17 @@ __device__ __forceinline__ void emit(const Out &o, uint32_t ld, uint32_t gi, f3 
       if (!in_table) st = BZR_RR_NONE;
       if (o.lossless) gain = 1.0f;
     }
+    float leg_att = 1.0f;  // kModeAbsorb: the leg's attenuation
     if constexpr (has_opl(kMode)) {  // (st: the expected status, kReflected or NONE; os: the hit's point)
       if (o.first || st != BZR_RR_NONE) {
         float opl = o.first ? (o.opl_in ? o.opl_in[gi] : 0.0f) : o.opl[gi];
         float glass = (o.first || !o.glass) ? 0.0f : o.glass[gi];
         if (st != BZR_RR_NONE) {
-          if constexpr (has_media(kMode)) opl_leg_media(s, os, nm, o.expected_all == BZR_RR_OUTSIDE, opl, glass);
+          if constexpr (has_absorb(kMode)) {
+            const bool outside = o.expected_all == BZR_RR_OUTSIDE;
+            const float len = opl_leg_absorb(s, os, nm, outside, opl, glass);
+            leg_att = leg_attenuation((outside ? o.glass_absorb : o.gap_absorb)[col], len);
+          } else if constexpr (has_media(kMode)) opl_leg_media(s, os, nm, o.expected_all == BZR_RR_OUTSIDE, opl, glass);
           else opl_leg(s, os, ri, o.expected_all == BZR_RR_OUTSIDE, opl, glass);
         }
         o.opl[gi] = opl;
@@ -655,7 +688,16 @@ __device__ __forceinline__ void emit(const Out &o, uint32_t ld, uint32_t gi, f3 
     }
     o.status[gi] = st;
     if (is_stage(kMode) && o.segments) o.segments[gi] = o.first ? 1u : o.segments[gi] + 1u;
-    if constexpr (has_power(kMode)) {  // the first stage writes every ray's weight, later ones the refracted rays'
+    if constexpr (has_absorb(kMode)) {  // the leg attenuates a reflected ray too; the gain belongs to a refraction only
+      if (o.first || st != BZR_RR_NONE) {
+        float w = o.first ? (o.weight_in ? o.weight_in[gi] : 1.0f) : o.weight[gi];
+        if (st != BZR_RR_NONE) {
+          w = w * leg_att;
+          if (!reflected) w = w * gain;
+        }
+        o.weight[gi] = w;
+      }
+    } else if constexpr (has_power(kMode)) {  // the first stage writes every ray's weight, later ones the refracted rays'
       if (o.first || (st != BZR_RR_NONE && !reflected)) {
         float w = o.first ? (o.weight_in ? o.weight_in[gi] : 1.0f) : o.weight[gi];
         if (st != BZR_RR_NONE) w = w * gain;
@@ -1932,6 +1974,8 @@ struct TraceKeep<kModeOpl> {
 };
 template <>
 struct TraceKeep<kModeMedia> : TraceKeep<kModeOpl> {};  // kModeMedia keeps what kModeOpl keeps: no new word per lane
+template <>
+struct TraceKeep<kModeAbsorb> : TraceKeep<kModeMedia> {};  // and so does kModeAbsorb
 // The bundle walk's set of leaf slots already queued in this wave-segment (bundle_batch `seen`), one bit per
 // slot: the refract and chain kernels walk the trees with split leaf boxes (MeshView swide).  The intersect
 // kernel's 6.7 KB per wave leave no room for it (24 waves x 7.7 KB > 160 KB), and the power, spectral and TIR
@@ -2434,6 +2478,8 @@ struct TraceJob {
   const float *opl_in;             // kModeOpl [n]: the path the rays start with, or null -> 0
   float *glass;                    // kModeOpl, optional [n]: the rays' geometric length inside glass
   const float *gap_table;          // kModeMedia [count + 1][nchan]: the index in front of lens l, row count behind the last
+                                   // kModeAbsorb: and, kGapPart floats behind it, glass_absorb [count][nchan], and
+                                   // kAbsorbPart floats behind that gap_absorb [count][nchan] (the context's buffer)
 };
 
 // kTraceWpe: amdgpu_waves_per_eu lower bound for k_trace.  The chain kernel needs 72 VGPRs
@@ -2599,22 +2645,32 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
         if (!in_table) r = BZR_RR_NONE;
         if (job.lossless) gain = 1.0f;
         if (act) {
-          if constexpr (has_media(kMode)) {
+          float leg_att = 1.0f;  // kModeAbsorb: the leg's attenuation
+          if constexpr (has_absorb(kMode)) {
+            // the lane's coefficient is read where n0 and n2 were, behind the segment's passes
+            if (r != BZR_RR_NONE) {
+              const float len = opl_leg_absorb(s, os, nm, b != 0u, L.opl[lane], L.glass[lane]);
+              const uint32_t c = l * job.nchan + (in_table ? ch : 0u);
+              leg_att = leg_attenuation(job.gap_table[kGapPart + (b != 0u ? 0u : kAbsorbPart) + c], len);
+            }
+          } else if constexpr (has_media(kMode)) {
             if (r != BZR_RR_NONE) opl_leg_media(s, os, nm, b != 0u, L.opl[lane], L.glass[lane]);
           } else if constexpr (kMode == kModeOpl) {  // the leg from s to the hit (os), before s moves there
             if (r != BZR_RR_NONE) opl_leg(s, os, ri, b != 0u, L.opl[lane], L.glass[lane]);
           }
           L.count[lane] += r == kReflected ? 0x10001u : 1u;
-          if (r == kReflected) {  // stays pending; the weight is not touched
+          if (r == kReflected) {  // stays pending; the weight is not touched (kModeAbsorb: but for the leg)
             s = os;
             d = od;
+            if constexpr (has_absorb(kMode)) L.weight[lane] = L.weight[lane] * leg_att;
           } else {
             pend = b == 0u && r != BZR_RR_NONE;
             if (r == BZR_RR_NONE) alive = false;
             else {
               s = os;
               d = od;
-              L.weight[lane] = L.weight[lane] * gain;
+              if constexpr (has_absorb(kMode)) L.weight[lane] = (L.weight[lane] * leg_att) * gain;
+              else L.weight[lane] = L.weight[lane] * gain;
             }
           }
         }
@@ -2763,7 +2819,8 @@ __global__ __launch_bounds__(kBlock) void k_refract_scan(MeshView m, const float
 // repeated while the ray reflects, up to max_bounces times per lens; channel may be null (channel 0), out_bounces
 // is optional.  kScan 4: kModeOpl's form -- kScan 3 with the optical path and the glass path (opl_leg); opl_in may be
 // null (0) and may alias out_opl, out_glass is optional.  kScan 5: kModeMedia's form -- kScan 4 with gap_table [count +
-// 1][nchan] (tir_eta_t, opl_leg_media).  (An int, not an enum: instantiations 0 to 3 keep their names.)
+// 1][nchan] (tir_eta_t, opl_leg_media).  kScan 6: kModeAbsorb's form -- kScan 5 with the two absorption tables
+// [count][nchan] (leg_attenuation).  (An int, not an enum: instantiations 0 to 3 keep their names.)
 template <int kScan>
 __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const float *__restrict__ rays, uint32_t n,
                                                        float *__restrict__ out_rays, uint32_t *__restrict__ out_status,
@@ -2772,8 +2829,11 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
                                                        const float *__restrict__ ri_table, uint32_t nchan,
                                                        uint32_t *__restrict__ out_bounces, uint32_t max_bounces,
                                                        const float *opl_in, float *out_opl, float *out_glass,
-                                                       const float *__restrict__ gap_table) {
-  constexpr bool kPower = kScan != 0, kSpectral = kScan >= 2, kTir = kScan >= 3, kOpl = kScan >= 4, kMedia = kScan == 5;
+                                                       const float *__restrict__ gap_table,
+                                                       const float *__restrict__ glass_absorb,
+                                                       const float *__restrict__ gap_absorb) {
+  constexpr bool kPower = kScan != 0, kSpectral = kScan >= 2, kTir = kScan >= 3, kOpl = kScan >= 4, kMedia = kScan >= 5;
+  constexpr bool kAbsorb = kScan == 6;
   uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   f3 s, d;
@@ -2813,7 +2873,12 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
         st = refract_hit_t<kPower>(h, ri, s, d, j == 0 ? BZR_RR_INSIDE : BZR_RR_OUTSIDE, os, od, gain);
       if constexpr (kSpectral)
         if (!in_table) st = BZR_RR_NONE;
-      if constexpr (kMedia) {
+      if constexpr (kAbsorb) {
+        if (st != BZR_RR_NONE) {
+          const float len = opl_leg_absorb(s, os, nm, j != 0u, opl, glass);
+          wgt = wgt * leg_attenuation((j != 0u ? glass_absorb : gap_absorb)[l * nchan + ch], len);
+        }
+      } else if constexpr (kMedia) {
         if (st != BZR_RR_NONE) opl_leg_media(s, os, nm, j != 0u, opl, glass);
       } else if constexpr (kOpl)
         if (st != BZR_RR_NONE) opl_leg(s, os, ri, j != 0u, opl, glass);
@@ -3238,10 +3303,13 @@ bzr_status run_fused(bzr_ctx *ctx, const LensSet &set, const TraceJob &job, uint
 // read after the call returns.  A frame loop with one table therefore uploads it once.
 constexpr uint32_t kMaxChannels = BZR_MAX_CHANNELS;
 // (one allocation: kModeMedia's gap table [nlens + 1][nchan] lies behind the index table's kMaxLenses rows)
-constexpr size_t kRiTableFloats = (size_t)kMaxLenses * kMaxChannels, kGapTableFloats = (size_t)(kMaxLenses + 1) * kMaxChannels;
+constexpr size_t kRiTableFloats = (size_t)kMaxLenses * kMaxChannels, kGapTableFloats = kGapPart;
+// (and kModeAbsorb's two tables [nlens][nchan] behind those: the glass part, then the gap part)
+constexpr size_t kAbsorbTableFloats = kAbsorbPart;
+constexpr size_t kGlassAbsorbAt = kRiTableFloats + kGapTableFloats, kGapAbsorbAt = kGlassAbsorbAt + kAbsorbTableFloats;
 bzr_status upload_ri_table(bzr_ctx *ctx, const float *table, uint32_t nlens, uint32_t nchan) {
   const size_t count = (size_t)nlens * nchan;
-  if (!ctx->ri_table) BZR_HIP(hipMalloc(&ctx->ri_table, (kRiTableFloats + kGapTableFloats) * sizeof(float)));
+  if (!ctx->ri_table) BZR_HIP(hipMalloc(&ctx->ri_table, (kGapAbsorbAt + kAbsorbTableFloats) * sizeof(float)));
   if (ctx->ri_table_host.size() == count && std::memcmp(ctx->ri_table_host.data(), table, count * sizeof(float)) == 0)
     return BZR_OK;
   BZR_HIP(hipStreamSynchronize(ctx->stream));
@@ -3263,6 +3331,28 @@ bzr_status upload_gap_table(bzr_ctx *ctx, const float *table, uint32_t nlens, ui
   ctx->gap_table_host.clear();
   BZR_HIP(hipMemcpy(ctx->ri_table + kRiTableFloats, table, count * sizeof(float), hipMemcpyHostToDevice));
   ctx->gap_table_host.assign(table, table + count);
+  return BZR_OK;
+}
+// kModeAbsorb's two parts behind it, each under the same rule with a host copy of its own (`host`, of the part at
+// float offset `at`): compared and rewritten on its own, and never touched by the entry points that take no
+// absorption.  A null table is all zero.
+bzr_status upload_absorb_table(bzr_ctx *ctx, const float *table, uint32_t nlens, uint32_t nchan, size_t at,
+                               std::vector<float> &host) {
+  const size_t count = (size_t)nlens * nchan;
+  const std::vector<float> zeros(table ? 0 : count, 0.0f);
+  if (!table) table = zeros.data();
+  if (host.size() == count && std::memcmp(host.data(), table, count * sizeof(float)) == 0) return BZR_OK;
+  BZR_HIP(hipStreamSynchronize(ctx->stream));
+  host.clear();
+  BZR_HIP(hipMemcpy(ctx->ri_table + at, table, count * sizeof(float), hipMemcpyHostToDevice));
+  host.assign(table, table + count);
+  return BZR_OK;
+}
+// Every used entry of an absorption table finite and not below zero (a null table is all zero).
+bzr_status check_absorb_table(const float *table, uint32_t nlens, uint32_t nchan, const char *what) {
+  if (!table) return BZR_OK;
+  for (size_t k = 0; k < (size_t)nlens * nchan; ++k)
+    if (!(table[k] >= 0.0f) || !std::isfinite(table[k])) return set_error(BZR_ERR_INVALID_ARGUMENT, what);
   return BZR_OK;
 }
 // Every used entry of a gap table finite and above zero (a null table is vacuum).
@@ -3307,6 +3397,9 @@ template <int kMode>
 bzr_status run_chain(bzr_ctx *ctx, const LensSet &set, const TraceJob &job, uint32_t flags, bool staged, uint32_t *pend,
                      uint32_t ch, Work &w) {
   constexpr bool kTir = has_tir(kMode);
+  // kModeAbsorb reads its two absorption parts through gap_table (kGapPart): the pointer must be the context's
+  if (has_absorb(kMode) && job.gap_table != ctx->ri_table + kRiTableFloats)
+    return set_error(BZR_ERR_INVALID_ARGUMENT, "kModeAbsorb: gap_table must be the context's table buffer");
   if (!staged) return run_fused<kMode>(ctx, set, job, flags);
   for (uint32_t off = 0; off < job.n; off += ch) {
     const uint32_t m = std::min(ch, job.n - off);
@@ -3338,6 +3431,10 @@ bzr_status run_chain(bzr_ctx *ctx, const LensSet &set, const TraceJob &job, uint
         if constexpr (has_media(kMode)) {
           o.gap_row = job.gap_table + (size_t)l * job.nchan;
           o.gap_next = o.gap_row + job.nchan;
+        }
+        if constexpr (has_absorb(kMode)) {
+          o.glass_absorb = job.gap_table + kGapPart + (size_t)l * job.nchan;
+          o.gap_absorb = o.glass_absorb + kAbsorbPart;
         }
         if (bzr_status s = run_segment<kMode>(use_fast(flags), ctx, set.lens[l], o.first ? job.rays : job.out_rays, job.ld,
                                               off, m, o.first ? nullptr : (o.bounce_stage ? pend : job.status), o, w))
@@ -3886,15 +3983,18 @@ extern "C" bzr_status bzr_refract(bzr_ctx *ctx, const bzr_mesh *mesh, float ri, 
 // optional plain [n] row).  The staged kModeTir chain keeps one more word per ray, the pending row, in the scratch.
 // bzr_trace_chain_opl (kModeOpl: kModeTir + opl_in, may be null, out_opl and the optional out_glass, plain [n] rows).
 // bzr_trace_chain_media (kModeMedia: kModeOpl + `gap`, the media table [nlens + 1][nchan] in host memory, null: vacuum).
+// bzr_trace_chain_absorb (kModeAbsorb: kModeMedia + `glass_abs` and `gap_abs`, the absorption tables [nlens][nchan] in
+// host memory, null: all zero).
 template <int kMode>
 static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
                               const float *rays, const float *weight_in, uint32_t n, float *out_rays, float *out_weight,
                               uint32_t *out_status, uint32_t *out_segments, uint32_t flags,
                               const uint8_t *channel = nullptr, uint32_t nchan = 0, uint32_t max_bounces = 0,
                               uint32_t *out_bounces = nullptr, const float *opl_in = nullptr, float *out_opl = nullptr,
-                              float *out_glass = nullptr, const float *gap = nullptr) {
+                              float *out_glass = nullptr, const float *gap = nullptr, const float *glass_abs = nullptr,
+                              const float *gap_abs = nullptr) {
   constexpr bool kPower = has_power(kMode), kSpectral = has_channels(kMode), kTir = has_tir(kMode);
-  constexpr bool kOpl = has_opl(kMode), kMedia = has_media(kMode);
+  constexpr bool kOpl = has_opl(kMode), kMedia = has_media(kMode), kAbsorb = has_absorb(kMode);
   if (bzr_status s = check_flags(flags, true)) return s;
   if (!ctx) return set_error(BZR_ERR_INVALID_ARGUMENT, "null context");
   if (nlens == 0 || nlens > kMaxLenses) return set_error(BZR_ERR_INVALID_ARGUMENT, "nlens must be 1..8");
@@ -3905,6 +4005,7 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     if (max_bounces > BZR_MAX_BOUNCES) return set_error(BZR_ERR_INVALID_ARGUMENT, "max_bounces must be 0..8");
     if (kMedia)
       if (bzr_status s = check_gap_table(gap, nlens, nchan)) return s;
+    // (kAbsorb: bzr_trace_chain_absorb has checked its two tables already, ahead of the context check)
   }
   if (!lenses || !ri) return set_error(BZR_ERR_INVALID_ARGUMENT, "null lens list");
   LensSet set{};
@@ -3928,6 +4029,10 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     if (bzr_status s = upload_ri_table(ctx, ri, nlens, nchan)) return s;
   if (kMedia)
     if (bzr_status s = upload_gap_table(ctx, gap, nlens, nchan)) return s;
+  if (kAbsorb) {
+    if (bzr_status s = upload_absorb_table(ctx, glass_abs, nlens, nchan, kGlassAbsorbAt, ctx->glass_absorb_host)) return s;
+    if (bzr_status s = upload_absorb_table(ctx, gap_abs, nlens, nchan, kGapAbsorbAt, ctx->gap_absorb_host)) return s;
+  }
   const bool staged = !use_scan(flags) && use_staged(flags, n, max_patches(set));
   float *r = nullptr, *tmp = nullptr;  // tmp, host + AoS: the records on the device, in and out
   uint8_t *c = nullptr;
@@ -3961,9 +4066,12 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     d_rays = r;
   }
   if (use_scan(flags)) {
-    launch(ctx, BZR_KERNEL_CHAIN_SCAN, k_chain_scan<kMedia ? 5 : kOpl ? 4 : (kTir ? 3 : (kSpectral ? 2 : (kPower ? 1 : 0)))>,
+    launch(ctx, BZR_KERNEL_CHAIN_SCAN,
+           k_chain_scan<kAbsorb ? 6 : kMedia ? 5 : kOpl ? 4 : (kTir ? 3 : (kSpectral ? 2 : (kPower ? 1 : 0)))>,
            dim3(grid_for(n)), set, d_rays, n, d_out, d_st, d_seg, d_win, d_w, d_ch, (const float *)ctx->ri_table, nchan, d_bnc,
-           max_bounces, d_oin, d_opl, d_glass, kMedia ? (const float *)ctx->ri_table + kRiTableFloats : nullptr);
+           max_bounces, d_oin, d_opl, d_glass, kMedia ? (const float *)ctx->ri_table + kRiTableFloats : nullptr,
+           kAbsorb ? (const float *)ctx->ri_table + kGlassAbsorbAt : nullptr,
+           kAbsorb ? (const float *)ctx->ri_table + kGapAbsorbAt : nullptr);
     BZR_HIP(hipGetLastError());
   } else {
     TraceJob job{};
@@ -4062,8 +4170,33 @@ extern "C" bzr_status bzr_trace_chain_media(bzr_ctx *ctx, const bzr_mesh *const 
                                  gap_table);
 }
 
+extern "C" bzr_status bzr_trace_chain_absorb(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                             const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                             uint32_t nlens, uint32_t nchan, const float *rays, const uint8_t *channel,
+                                             const float *weight_in, const float *opl_in, uint32_t n,
+                                             uint32_t max_bounces, float *out_rays, float *out_weight,
+                                             uint32_t *out_status, uint32_t *out_segments, uint32_t *out_bounces,
+                                             float *out_opl, float *out_glass, uint32_t flags) {
+  if (!out_opl) return set_error(BZR_ERR_INVALID_ARGUMENT, "null out_opl");
+  if (max_bounces > BZR_MAX_BOUNCES) return set_error(BZR_ERR_INVALID_ARGUMENT, "max_bounces must be 0..8");
+  // (the tables too are refused ahead of the context check, where their extent is valid; trace_chain checks the rest)
+  if (nlens >= 1 && nlens <= kMaxLenses && nchan >= 1 && nchan <= kMaxChannels) {
+    if (bzr_status s = check_absorb_table(glass_absorb, nlens, nchan, "glass_absorb entries must be finite and >= 0")) return s;
+    if (bzr_status s = check_absorb_table(gap_absorb, nlens, nchan, "gap_absorb entries must be finite and >= 0")) return s;
+  }
+  return trace_chain<kModeAbsorb>(ctx, lenses, ri_table, nlens, rays, weight_in, n, out_rays, out_weight, out_status,
+                                  out_segments, flags, channel, nchan, max_bounces, out_bounces, opl_in, out_opl, out_glass,
+                                  gap_table, glass_absorb, gap_absorb);
+}
+
 // ------------------------------------------------------------ test hook: normalized()
 namespace {
+// The chain's Beer-Lambert term (patch_math_body.inc att), one value per lane.
+__global__ __launch_bounds__(kBlock) void k_debug_attenuation(const float *__restrict__ x, uint32_t n,
+                                                              float *__restrict__ out) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) out[i] = att(x[i]);
+}
 // Row k of out (k < 3): the product's exact normalized() (patch_math.hpp unit_or_self, shared-reciprocal chain
 // where its guard allows); rows 3..5: sqrt_rn / div_rn per component (the compiler's own lowering).
 __global__ __launch_bounds__(kBlock) void k_debug_unit(const float *__restrict__ a, uint32_t n,
@@ -4149,6 +4282,28 @@ __global__ __launch_bounds__(kBlock) void k_debug_fast_unit(const float *__restr
   for (int k = 0; k < 5; ++k) out[(size_t)k * n + i] = r[k];
 }
 }  // namespace
+
+extern "C" void bzr_internal_attenuation_host(const float *x, uint32_t n, float *out);  // host (capi_host.cpp)
+// Host pointers in and out either way; with a context the values go through the staging buffer and one kernel.
+extern "C" bzr_status bzr_debug_attenuation(void *ctxp, const float *x, uint32_t n, float *out) {
+  bzr_ctx *ctx = static_cast<bzr_ctx *>(ctxp);
+  if (n == 0) return BZR_OK;
+  if (!x || !out) return set_error(BZR_ERR_INVALID_ARGUMENT, "null buffer");
+  if (!ctx) {
+    bzr_internal_attenuation_host(x, n, out);
+    return BZR_OK;
+  }
+  DeviceGuard g(ctx->device);
+  float *d_x = nullptr, *d_out = nullptr;
+  if (bzr_status s = carve_buffer(ctx->scratch, ctx->scratch_bytes, [&](Staging &st) { st.take(d_x, n), st.take(d_out, n); }))
+    return s;
+  BZR_HIP(hipMemcpyAsync(d_x, x, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_debug_attenuation, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, d_x, n, d_out);
+  BZR_HIP(hipGetLastError());
+  BZR_HIP(hipMemcpyAsync(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  BZR_HIP(hipStreamSynchronize(ctx->stream));
+  return BZR_OK;
+}
 
 extern "C" bzr_status bzr_debug_fast_unit(void *ctxp, const float *a, uint32_t n, float *out) {
   bzr_ctx *ctx = static_cast<bzr_ctx *>(ctxp);
@@ -4628,11 +4783,17 @@ extern "C" bzr_status bzr_emit(bzr_ctx *ctx, const bzr_emitter *em, uint64_t fir
 // bzr_illuminate_spectral: nchan > 0, `ri` is the index table [nlens][nchan], and flux, hist, stats and power hold
 // nchan maps / rows of four, one per channel (NC below is 1 otherwise).
 // bzr_illuminate_tir: spectral with `tir`, the chain that reflects (kModeTir) and what only that call returns.
+// bzr_illuminate_media: the same with tir->media, the chain that reflects, refracts between media and absorbs
+// (kModeAbsorb); k_land_tir lands its rays as they are (the weights carry everything).
 struct IllumTir {
   uint32_t max_bounces;
   uint64_t *rflux;          // the stray-light maps [nchan][cells], host or device memory like flux; each may be null
   uint32_t *rhist;
   uint64_t *count, *power;  // the ledger [nchan][BZR_LEDGER_ROWS][BZR_LEDGER_FIELDS], host memory; each may be null
+  // bzr_illuminate_media: the chain is kModeAbsorb's, with the gap table [nlens + 1][nchan] and the two absorption
+  // tables [nlens][nchan] (host memory, each may be null: vacuum, all zero)
+  bool media = false;
+  const float *gap = nullptr, *glass_absorb = nullptr, *gap_absorb = nullptr;
 };
 static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
                              const bzr_emitter *em, uint64_t total_rays, const bzr_target *tg, const bzr_radiometry *rad,
@@ -4644,6 +4805,14 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   if (tir && tir->max_bounces > BZR_MAX_BOUNCES) return set_error(BZR_ERR_INVALID_ARGUMENT, "max_bounces must be 0..8");
   if (spectral)
     if (bzr_status s = check_channels(ri, nchan)) return s;
+  const bool media = tir && tir->media;
+  if (media) {
+    if (bzr_status s = check_gap_table(tir->gap, nlens, nchan)) return s;
+    if (bzr_status s = check_absorb_table(tir->glass_absorb, nlens, nchan, "glass_absorb entries must be finite and >= 0"))
+      return s;
+    if (bzr_status s = check_absorb_table(tir->gap_absorb, nlens, nchan, "gap_absorb entries must be finite and >= 0"))
+      return s;
+  }
   const uint32_t NC = spectral ? nchan : 1u;
   if (!lenses || !ri || !tg || (!with_power && !hist)) return set_error(BZR_ERR_INVALID_ARGUMENT, "null argument");
   if (with_power) {
@@ -4667,6 +4836,13 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   DeviceGuard g(ctx->device);
   if (spectral)
     if (bzr_status s = upload_ri_table(ctx, ri, nlens, nchan)) return s;
+  if (media) {
+    if (bzr_status s = upload_gap_table(ctx, tir->gap, nlens, nchan)) return s;
+    if (bzr_status s = upload_absorb_table(ctx, tir->glass_absorb, nlens, nchan, kGlassAbsorbAt, ctx->glass_absorb_host))
+      return s;
+    if (bzr_status s = upload_absorb_table(ctx, tir->gap_absorb, nlens, nchan, kGapAbsorbAt, ctx->gap_absorb_host))
+      return s;
+  }
   // target plane (normal = axis_u x axis_v normalised, constant = n . origin) and cell sizes, in the
   // oracle's operation order
   const float *au = tg->axis_u, *av = tg->axis_v;
@@ -4692,11 +4868,13 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   unsigned long long *d_stats = nullptr, *d_power = nullptr;  // the four counts and, with_power, the four power sums
   unsigned long long *d_flux = reinterpret_cast<unsigned long long *>(flux);
   uint8_t *d_ch = nullptr;  // spectral: the batch's channel row
-  // tir: the batch's bounce row and, staged, the chain's pending row directly behind it (one memset clears both);
-  // the ledger; the stray-light maps of a host caller
+  // tir: the batch's bounce row and, staged, the chain's pending row behind it (one memset clears both); the ledger;
+  // the stray-light maps of a host caller.  media: the chain's optical path row between the two, under the same
+  // memset -- scratch that nothing returns (no glass row: the chain's is optional)
   const size_t ledger = (size_t)BZR_LEDGER_ROWS * BZR_LEDGER_FIELDS * NC;
   const bool staged = use_staged(flags, B, nb);
   uint32_t *d_bnc = nullptr, *d_pend = nullptr, *d_rhist = tir ? tir->rhist : nullptr;
+  float *d_opl = nullptr;
   unsigned long long *d_rflux = tir ? reinterpret_cast<unsigned long long *>(tir->rflux) : nullptr;
   unsigned long long *d_lcount = nullptr, *d_lpower = nullptr;
   if (bzr_status s = carve_buffer(ctx->scratch, ctx->scratch_bytes, [&](Staging &st) {
@@ -4707,6 +4885,7 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
         if (with_power && host) st.take(d_flux, maps);
         if (spectral) st.take(d_ch, B);
         if (tir) st.take(d_bnc, B);
+        if (media) st.take(d_opl, B);
         if (tir && staged) st.take(d_pend, B);
         if (tir) st.take(d_lcount, ledger), st.take(d_lpower, ledger);
         if (tir && host && tir->rflux) st.take(d_rflux, maps);
@@ -4729,9 +4908,10 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   // The in-place job has alive_in set, so the chain has no first stage: nothing in it writes a culled ray's bounce
   // word (either pipeline) or pending word (staged), and a staged bounce stage traces every ray whose pending word is
   // set.  Both rows are therefore cleared before every batch's chain, by one memset on the context's stream (chosen
-  // over a store in k_emit, whose instantiations for the other entry points stay as they are).
-  const size_t tir_rows = !tir ? 0 : staged ? (size_t)(reinterpret_cast<char *>(d_pend + B) - reinterpret_cast<char *>(d_bnc))
-                                            : (size_t)B * 4;
+  // over a store in k_emit, whose instantiations for the other entry points stay as they are).  The media chain's
+  // optical path row is in the same case: its first stage would have written every ray's word, later stages add to it.
+  const uint32_t *const last_row = staged ? d_pend : media ? reinterpret_cast<uint32_t *>(d_opl) : d_bnc;
+  const size_t tir_rows = !tir ? 0 : (size_t)(reinterpret_cast<const char *>(last_row + B) - reinterpret_cast<char *>(d_bnc));
   Work w;
   if (staged)
     if (bzr_status s = ensure_work(ctx, B, nb, w)) return s;
@@ -4740,7 +4920,8 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   const uint32_t lambert = with_power && rad->emission == BZR_EMISSION_LAMBERT ? 1u : 0u;
   // the mode, chosen once: the chain's (a lossless surface leaves the weights as emitted: the plain chain; the
   // spectral chain refracts per channel with a lossless surface too: its run-time flag) and the two kernels'
-  auto *const chain = tir        ? &run_chain<kModeTir>
+  auto *const chain = media      ? &run_chain<kModeAbsorb>
+                      : tir      ? &run_chain<kModeTir>
                       : spectral ? &run_chain<kModeSpectral>
                       : fresnel  ? &run_chain<kModePower>
                                  : &run_chain<kModeStage>;
@@ -4765,6 +4946,10 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
     job.lossless = fresnel ? 0u : 1u;
     job.bounces = d_bnc;
     job.max_bounces = tir ? tir->max_bounces : 0u;
+    if (media) {
+      job.opl = d_opl;
+      job.gap_table = ctx->ri_table + kRiTableFloats;
+    }
     if (bzr_status s = chain(ctx, set, job, flags, staged, d_pend, B, w)) return s;
     if (tir)
       hipLaunchKernelGGL(k_land_tir, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg,
@@ -4844,6 +5029,23 @@ extern "C" bzr_status bzr_illuminate_tir(bzr_ctx *ctx, const bzr_mesh *const *le
                                          uint32_t flags) {
   if (!rad) return set_error(BZR_ERR_INVALID_ARGUMENT, "null radiometry");
   const IllumTir tir{max_bounces, reflected_flux_q32, reflected_hist, ledger_count, ledger_power_q32};
+  return illuminate(ctx, lenses, ri_table, nlens, em, total_rays, tg, rad, flux_q32, hist, stats, power_q32, flags, true,
+                    nchan, &tir);
+}
+
+extern "C" bzr_status bzr_illuminate_media(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                           const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                           uint32_t nlens, uint32_t nchan, const bzr_emitter *em, uint64_t total_rays,
+                                           const bzr_target *tg, const bzr_radiometry *rad, uint32_t max_bounces,
+                                           uint64_t *flux_q32, uint32_t *hist, uint64_t *reflected_flux_q32,
+                                           uint32_t *reflected_hist, uint64_t *stats, uint64_t *power_q32,
+                                           uint64_t *ledger_count, uint64_t *ledger_power_q32, uint32_t flags) {
+  if (!rad) return set_error(BZR_ERR_INVALID_ARGUMENT, "null radiometry");
+  IllumTir tir{max_bounces, reflected_flux_q32, reflected_hist, ledger_count, ledger_power_q32};
+  tir.media = true;
+  tir.gap = gap_table;
+  tir.glass_absorb = glass_absorb;
+  tir.gap_absorb = gap_absorb;
   return illuminate(ctx, lenses, ri_table, nlens, em, total_rays, tg, rad, flux_q32, hist, stats, power_q32, flags, true,
                     nchan, &tir);
 }

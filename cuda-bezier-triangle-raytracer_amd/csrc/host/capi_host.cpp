@@ -208,6 +208,9 @@ int32_t bzr_debug_fresnel(const float *eta, const float *cs, uint32_t n, float *
   return BZR_OK;
 }
 
+// bzr_debug_attenuation's host half (trace.hip holds the entry point and its device half).
+void bzr_internal_attenuation_host(const float *x, uint32_t n, float *out) { bzr_host::attenuation(x, n, out); }
+
 // Every value is computed before the first is written: a rejected call leaves out_ri as it was.
 bzr_status bzr_dispersion_index(int32_t model, const double *coeff, uint32_t ncoeff, const double *wavelength_um,
                                 uint32_t n, float *out_ri) {
@@ -240,6 +243,29 @@ bzr_status bzr_dispersion_index(int32_t model, const double *coeff, uint32_t nco
     if (!std::isfinite(v) || !std::isfinite(ri[i])) return bad("index is not finite");
   }
   if (n) std::memcpy(out_ri, ri.data(), (std::size_t)n * sizeof(float));
+  return BZR_OK;
+}
+
+// As above: nothing is written unless every coefficient is good.
+bzr_status bzr_absorption_from_transmittance(const double *internal_transmittance, uint32_t n, double thickness,
+                                             float *out_a) {
+  if (!std::isfinite(thickness) || !(thickness > 0.0)) return bad("thickness must be finite and positive");
+  if ((!internal_transmittance || !out_a) && n) return bad("null argument");
+  std::vector<float> a;
+  try {
+    a.resize(n);
+  } catch (std::bad_alloc const &) {
+    bzr_internal_set_error("out of memory");
+    return BZR_ERR_OUT_OF_MEMORY;
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    const double t = internal_transmittance[i];
+    if (!(t > 0.0) || !(t <= 1.0)) return bad("internal transmittance must be in (0, 1]");
+    const double v = t == 1.0 ? 0.0 : -std::log(t) / thickness;
+    a[i] = static_cast<float>(v);
+    if (!std::isfinite(v) || !std::isfinite(a[i])) return bad("absorption coefficient is not finite");
+  }
+  if (n) std::memcpy(out_a, a.data(), (std::size_t)n * sizeof(float));
   return BZR_OK;
 }
 

@@ -12,6 +12,7 @@
 //   meshIntersect   BezierMesh::intersect       reference/bezierMesh.cpp:206-227 (brute force, index order)
 //   lensRefract     BezierLens::refract         reference/bezierLens.cpp:4-34
 //   lensRefractPower  the same with the refraction's Fresnel transmittance (patch_math_body.inc fresnel_t)
+//   attenuation     the chain's Beer-Lambert term (patch_math_body.inc att), for bzr_debug_attenuation
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -63,6 +64,12 @@ constexpr int kNeigh = 16, kWords = 66;
 namespace exact {
 inline float div_rn(float a, float b) { return a / b; }
 inline float sqrt_rn(float a) { return std::sqrt(a); }
+inline float bits_f32(uint32_t u) {
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+inline float rint_even(float y) { return std::nearbyint(y); }  // the default rounding mode: ties to even
 inline bool sqrt_above_hundredth(float z) { return sqrt_rn(z) > 0.01f; }  // norm(perp) > 0.01f
 inline f3 unit_or_self(f3 a, float z) {  // Eigen normalized(): a / sqrt(z) when z > 0
   if (!(z > 0.0f)) return a;
@@ -165,6 +172,11 @@ void fresnel_pairs(const float *eta, const float *cs, uint32_t n, float *t_out) 
     const float s2 = eta[i] * eta[i] * (1.0f - cs[i] * cs[i]);
     t_out[i] = s2 < 0.99f ? fresnel_t(eta[i], cs[i], s2) : 0.0f;
   }
+}
+
+// bzr_debug_attenuation without a context: the shared Beer-Lambert text.
+void attenuation(const float *x, uint32_t n, float *out) {
+  for (uint32_t i = 0; i < n; ++i) out[i] = att(x[i]);
 }
 
 // newton_tail's hook answering "not needed" (bzr_debug_newton_short)

@@ -13,6 +13,8 @@ namespace bzr_host {
 void newton_short_pair(const float *record, const float ray[6], bool limitNone, float full[12], float skipped[12]);
 // The Fresnel transmittance of n (eta, cos) pairs, 0 where Snell's step does not refract (bzr_debug_fresnel).
 void fresnel_pairs(const float *eta, const float *cs, uint32_t n, float *t_out);
+// The Beer-Lambert term att(x[i]) of n values (bzr_debug_attenuation with a null context).
+void attenuation(const float *x, uint32_t n, float *out);
 }  // namespace bzr_host
 
 namespace bzr {

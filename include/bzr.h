@@ -346,13 +346,49 @@ bzr_status bzr_trace_chain_opl(bzr_ctx *ctx, const bzr_mesh *const *lenses, cons
  *     bounced rays can leave through the front).
  *   A front surface never reflects.  A refract(INSIDE) segment from a denser medium with s2 >= 0.99 is NONE (cfg2 with
  *     1.6 in front of 1.3: 102 more rays end NONE after one segment than in vacuum).
- *   The illumination entry points, the multi-GPU plan and bzr_refract take no media. */
+ *   bzr_illuminate, bzr_illuminate_power, bzr_illuminate_spectral, bzr_illuminate_tir, the multi-GPU plan and
+ *     bzr_refract take no media; bzr_illuminate_media (below) is the illumination over this chain with absorption. */
 bzr_status bzr_trace_chain_media(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
                                  const float *gap_table, uint32_t nlens, uint32_t nchan, const float *rays_soa,
                                  const uint8_t *channel, const float *weight_in, const float *opl_in, uint32_t n,
                                  uint32_t max_bounces, float *out_rays_soa, float *out_weight, uint32_t *out_status,
                                  uint32_t *out_segments, uint32_t *out_bounces, float *out_opl, float *out_glass,
                                  uint32_t flags);
+/* ---- absorption ----
+ * bzr_trace_chain_media with Beer-Lambert absorption along the legs.  Two tables follow gap_table, row-major float32
+ * in host memory like ri_table: glass_absorb[nlens][nchan], the Napierian absorption coefficient of lens l's glass for
+ * channel c per unit of the scene's length, and gap_absorb[nlens][nchan], the same for the medium in front of lens l
+ * (gap_table's row l; the chain has no leg behind the last lens, so there is no row nlens).  Either may be NULL: all
+ * zero.  Every used entry must be finite and >= 0, else BZR_ERR_INVALID_ARGUMENT before any output is touched.
+ * The step runs for every segment that ends in a successful refraction or in a reflection -- the segments whose leg
+ * enters out_opl -- with that leg's len, a = gap_absorb[l][c] on a refract(INSIDE) segment and glass_absorb[l][c] on a
+ * refract(OUTSIDE) one, bounce segments included:
+ *   x = a len;  A = a > 0 ? att(x) : 1.0f;  w = w A (the light travels the leg), then w = w T (it meets the surface:
+ *   the Fresnel term as in bzr_trace_chain_power; a reflection has no T, and now applies A alone).
+ * att(x) stands for exp(-x) and is defined by its operations, IEEE binary32 without contraction, exact under
+ * BZR_MODE_FAST too (it belongs to the chain step):
+ *   y = x * 0x3FB8AA3B (log2 e);  !(y < 125) -> 0 (a NaN too);  k = rint(y), ties to even;  f = y - k (exact);
+ *   p = c7; for j = 6 .. 0: p = p * f; p = p + c_j;  att = p * 2^-k (exact),
+ *   c_j = float((-ln 2)^j / j!) = 3f800000 bf317218 3e75fdf0 bd635847 3c1d955b baaec3ff 39218489 b77fe5fe.
+ * att(0) = 1, every result is 0 or a normal number in (0, 1], the relative error against exp(-x) is at most
+ * 2^-23 (1 + y) where exp(-x) > 1e-37, and the recipe is not monotone in the last bit.
+ * A segment that ends NONE attenuates nothing; a ray with a non-finite component or a channel at or above nchan keeps
+ * its weight.  A weight may reach 0: such a ray is traced on like any other.  out_rays, out_status, out_segments,
+ * out_bounces, out_opl and out_glass never depend on the two tables, and with both NULL or zero every output is
+ * bzr_trace_chain_media's bit for bit, in every mode and on every pipeline (the select on a > 0 keeps 0 x inf out of
+ * the weight). */
+bzr_status bzr_trace_chain_absorb(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                  const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                  uint32_t nlens, uint32_t nchan, const float *rays_soa, const uint8_t *channel,
+                                  const float *weight_in, const float *opl_in, uint32_t n, uint32_t max_bounces,
+                                  float *out_rays_soa, float *out_weight, uint32_t *out_status, uint32_t *out_segments,
+                                  uint32_t *out_bounces, float *out_opl, float *out_glass, uint32_t flags);
+/* Absorption coefficients from a glass catalogue's internal transmittance, on the host (no context, no device):
+ * out_a[i] = -ln(internal_transmittance[i]) / thickness, evaluated in binary64 and rounded once to float, per unit of
+ * the length `thickness` is given in.  A transmittance outside (0, 1], a thickness that is not finite and positive or
+ * a result that is not finite return BZR_ERR_INVALID_ARGUMENT with nothing written. */
+bzr_status bzr_absorption_from_transmittance(const double *internal_transmittance, uint32_t n, double thickness,
+                                             float *out_a);
 /* Refractive index from a dispersion formula, on the host (no context, no device): evaluated in binary64 and
  * rounded once to float.  wavelength_um [n] in micrometres, out_ri [n].
  *   BZR_DISPERSION_CAUCHY     n = A + B / l^2 + C / l^4           coeff = A, B[, C]             ncoeff 2 or 3
@@ -542,6 +578,26 @@ bzr_status bzr_illuminate_tir(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
                               uint64_t *reflected_flux_q32, uint32_t *reflected_hist,
                               uint64_t *stats, uint64_t *power_q32,
                               uint64_t *ledger_count, uint64_t *ledger_power_q32, uint32_t flags);
+/* bzr_illuminate_tir over the chain of bzr_trace_chain_absorb: the same outputs with the same meanings, emitter stream,
+ * sphere cull (geometric, unchanged), batching rule and flags.  gap_table [nlens + 1][nchan], glass_absorb and
+ * gap_absorb [nlens][nchan] are that call's (host memory, each may be NULL: vacuum, all zero) and are checked as there.
+ * The emitter sits in the medium gap_table[0]: the leg from the emitter to the first lens is attenuated with
+ * gap_absorb[0].  The leg from the last lens to the target is neither refracted again nor attenuated: row nlens of
+ * gap_table is the medium the rays leave into and land in.  rad->surface == BZR_SURFACE_LOSSLESS takes the Fresnel
+ * term out and leaves the absorption in.
+ * The ledger's count identities all hold.  With absorption its power line changes: under BZR_SURFACE_LOSSLESS
+ * sum_r (LOST + EXITED) power no longer equals power_q32[c][EMITTED] - power_q32[c][CULLED]; the difference is what
+ * the media absorbed before the rays ended.
+ * With gap_table of ones or NULL and both absorption tables zero or NULL every output is bzr_illuminate_tir's bit for
+ * bit. */
+bzr_status bzr_illuminate_media(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                uint32_t nlens, uint32_t nchan, const bzr_emitter *em, uint64_t total_rays,
+                                const bzr_target *target, const bzr_radiometry *rad, uint32_t max_bounces,
+                                uint64_t *flux_q32, uint32_t *hist,
+                                uint64_t *reflected_flux_q32, uint32_t *reflected_hist,
+                                uint64_t *stats, uint64_t *power_q32,
+                                uint64_t *ledger_count, uint64_t *ledger_power_q32, uint32_t flags);
 /* The bounding sphere bzr_illuminate culls with: center xyz, radius. */
 bzr_status bzr_mesh_bounding_sphere(const bzr_mesh *mesh, float out[4]);
 

@@ -485,6 +485,15 @@ void traceChainMedia(std::vector<BezierLens const *> const &lenses, std::vector<
                      float const *opl, std::size_t n, uint32_t maxBounces, Ray *outRays, float *outWeights,
                      RefractionResult *outStatus, float *outOpl, float *outGlass = nullptr, uint32_t *outSegments = nullptr,
                      uint32_t *outBounces = nullptr, Context *ctx = nullptr);
+// traceChainMedia with Beer-Lambert absorption along the legs (bzr_trace_chain_absorb): glassAbsorb and gapAbsorb
+// [lenses.size()][nchan] row-major, the absorption coefficient of lens l's glass and of the medium in front of it per
+// unit length; an empty table is all zero.  Throws if either is neither empty nor lenses.size() x nchan long.
+void traceChainAbsorb(std::vector<BezierLens const *> const &lenses, std::vector<float> const &riTable,
+                      std::vector<float> const &gapTable, std::vector<float> const &glassAbsorb,
+                      std::vector<float> const &gapAbsorb, Ray const *rays, uint8_t const *channels, float const *weights,
+                      float const *opl, std::size_t n, uint32_t maxBounces, Ray *outRays, float *outWeights,
+                      RefractionResult *outStatus, float *outOpl, float *outGlass = nullptr, uint32_t *outSegments = nullptr,
+                      uint32_t *outBounces = nullptr, Context *ctx = nullptr);
 // The same chain over several devices from one process (bzr_trace_tiled): tiles of tileRays
 // consecutive rays dealt round-robin to `ctxs` (one per device, distinct), results in input order.
 void traceChainTiled(std::vector<Context *> const &ctxs, std::vector<BezierLens const *> const &lenses,

@@ -126,6 +126,11 @@ int32_t bzr_debug_newton_short(const void *patches, uint32_t n, uint32_t stride,
  * bzr_trace_chain_power documents in bzr.h): for each of n pairs (eta[i], cs[i]), s2 = eta^2 (1 - cs^2) as Snell's
  * step computes it and t_out[i] = T, or 0 where s2 >= 0.99 (no refraction).  No device.  Returns 0 on success. */
 int32_t bzr_debug_fresnel(const float *eta, const float *cs, uint32_t n, float *t_out);
+/* The chain's Beer-Lambert term (patch_math_body.inc att, the text bzr_trace_chain_absorb documents in bzr.h):
+ * out[i] = att(x[i]) for x[i] >= 0 (or NaN).  x and out are host memory.  With ctx == NULL the host's compilation of
+ * the text evaluates it (no device); otherwise ctx is a bzr_ctx* (bzr.h) and one small kernel on its device does,
+ * synchronously.  The two agree bit for bit.  Returns 0 on success. */
+int32_t bzr_debug_attenuation(void *ctx, const float *x, uint32_t n, float *out);
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@
 on the cfg2 lens, emitter just behind it (inside the lens's bounding sphere, so nothing is culled and
 every ray is traced).  Prints one JSON line: emitted rays / s and the landed fraction.
 
-usage: bench_illum.py [total_rays] [--power] [--tir [max_bounces]]
+usage: bench_illum.py [total_rays] [--power] [--tir [max_bounces]] [--media]
 --power times bzr_illuminate_power (Lambert emitter, Fresnel surfaces: k_emit<true> -> chain with weights ->
 k_land<true>, 64-bit flux cells) beside bzr_illuminate on the same rays, alternating, and prints one more JSON line
 with both; the chain kernels' share comes from the context's event timing in a separate pass, the rest of a call is
@@ -12,7 +12,11 @@ under a kernel-trace profiler.
 --tir [max_bounces] (default 4) prints one more JSON line: on a wide emitter 1 unit in front of the lens (inside its
 sphere: nothing is culled) with the indices 1.3 / 1.5 / 1.8 / 2.4, bzr_illuminate_spectral, bzr_illuminate_tir at budget
 0 and bzr_illuminate_tir at max_bounces on the same rays, alternating; the ratios are the cost of the reflecting chain's
-plumbing (the per-batch row clear, k_land_tir's ledger) and of the bounce segments."""
+plumbing (the per-batch row clear, k_land_tir's ledger) and of the bounce segments.
+--media prints one more JSON line: on the same wide emitter, bzr_illuminate_tir and bzr_illuminate_media (an encapsulant
+of index 1.41 / 1.333 / 1.2 / 1 in front of the lens, absorbing, and absorbing glass) at four reflections on the same
+emitted rays, alternating.  The media change which rays refract and reflect, so the ratio compares two workloads;
+whole-call times scatter by +- 15 % here."""
 import json
 import statistics
 import sys
@@ -28,8 +32,8 @@ from bzr_amd.configs import CONFIGS, build_lens  # noqa: E402
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a != "--power"]
-    power = "--power" in sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a not in ("--power", "--media")]
+    power, media = "--power" in sys.argv[1:], "--media" in sys.argv[1:]
     tir = None
     if "--tir" in args:
         k = args.index("--tir")
@@ -51,6 +55,8 @@ def main():
                       "stats": stats, "landed_fraction": round(stats["landed"] / total, 5)}))
     if tir is not None:
         bench_tir(ctx, dm, tg, total, tir)
+    if media:
+        bench_media(ctx, dm, tg, total)
     if not power:
         return
 
@@ -129,6 +135,51 @@ def bench_tir(ctx, dm, tg, total, max_bounces):
                                  "tir_0": sum(s["landed"] for s in out["illuminate_tir_0"][0]),
                                  top: sum(s["landed"] for s in stats), "reflected": int(count[1:, 2].sum())},
                       "ledger_rows_lost_exited_landed": count.tolist()}))
+
+
+def bench_media(ctx, dm, tg, total, max_bounces=4):
+    row1 = [1.3, 1.5, 1.8, 2.4]
+    gaps, glass, front = [[1.41, 1.333, 1.2, 1.0], [1.0] * 4], [[0.05, 0.7, 0.4, 200.0]], [[0.3, 0.02, 0.0, 0.1]]
+    em = bzr_amd.Emitter(origin=(8.0, -3.0, -1.5), edge_u=(0.0, 6.0, 0.0), edge_v=(0.0, 0.0, 3.0), parts_u=4, parts_v=4,
+                         points_per_part=1024, rays_per_point=1024, belts=16, seed=1)
+    calls = {"illuminate_tir": lambda n: bzr_amd.illuminate_tir(ctx, [dm], [row1], em, n, tg, max_bounces=max_bounces)[4:],
+             "illuminate_media_vacuum": lambda n: bzr_amd.illuminate_media(ctx, [dm], [row1], None, None, None, em, n, tg,
+                                                                          max_bounces=max_bounces)[4:],
+             "illuminate_media": lambda n: bzr_amd.illuminate_media(ctx, [dm], [row1], gaps, glass, front, em, n, tg,
+                                                                   max_bounces=max_bounces)[4:]}
+    wall, out = {k: [] for k in calls}, {}
+    for call in calls.values():
+        call(1 << 20)  # warm-up
+    names = list(calls)
+    for r in range(6):  # alternating and rotated, as bench_tir
+        for name in names[r % 3:] + names[:r % 3]:
+            t0 = time.perf_counter()
+            out[name] = calls[name](total)
+            wall[name].append(time.perf_counter() - t0)
+    chain = {}
+    for name in names:
+        ctx.timing(True)
+        ctx.timing_report()
+        calls[name](total)
+        chain[name] = sum(v[0] for v in ctx.timing_report().values()) / 1e3
+        ctx.timing(False)
+    med = {k: statistics.median(v) for k, v in wall.items()}
+    same = out["illuminate_tir"][0] == out["illuminate_media_vacuum"][0] and \
+        out["illuminate_tir"][1] == out["illuminate_media_vacuum"][1]
+    print(json.dumps({"workload": "illuminate_media beside illuminate_tir, cfg2 lens, emitter at x=8 (no cull), "
+                                  "indices 1.3/1.5/1.8/2.4, 512^2 target",
+                      "rays": total, "max_bounces": max_bounces,
+                      "seconds": {k: round(v, 4) for k, v in med.items()},
+                      "seconds_min_max": {k: [round(min(v), 4), round(max(v), 4)] for k, v in wall.items()},
+                      "mrays_per_s": {k: round(total / v / 1e6, 1) for k, v in med.items()},
+                      "chain_kernels_seconds": {k: round(v, 4) for k, v in chain.items()},
+                      "media_vacuum_over_tir": round(med["illuminate_media_vacuum"] / med["illuminate_tir"], 4),
+                      "media_over_tir": round(med["illuminate_media"] / med["illuminate_tir"], 4),
+                      "vacuum_stats_and_power_same_as_tir": bool(same),
+                      "landed": {k: sum(s["landed"] for s in v[0]) for k, v in out.items()},
+                      "landed_power_fraction": {k: round(sum(p["landed"] for p in v[1]) /
+                                                         max(sum(p["emitted"] for p in v[1]), 1), 5)
+                                                for k, v in out.items()}}))
 
 
 if __name__ == "__main__":
