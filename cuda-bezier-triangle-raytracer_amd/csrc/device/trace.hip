@@ -4718,6 +4718,8 @@ bzr_status check_emitter(const bzr_emitter *em) {
   if (!em) return set_error(BZR_ERR_INVALID_ARGUMENT, "null emitter");
   if (!em->parts_u || !em->parts_v || !em->points_per_part || !em->rays_per_point)
     return set_error(BZR_ERR_INVALID_ARGUMENT, "emitter counts must be positive");
+  // belt_tables' bound, ahead of every carve sized from belts
+  if (em->belts == 0 || em->belts > 4096) return set_error(BZR_ERR_INVALID_ARGUMENT, "belts must be 1..4096");
   return BZR_OK;
 }
 

@@ -486,7 +486,30 @@ bzr_status bzr_mesh_interpolate(bzr_ctx *ctx, const bzr_mesh *mesh, int32_t divi
  * UniformHemisphere::getRandom does (reference/hostUtil.cpp:16-29: cos(incidence) uniform in
  * [0,1), turn uniform in [0, 2*pi)) from a counter-based generator (splitmix64 of seed and ray
  * index), so any ray range can be generated independently; `belts` sets the hemisphere patch
- * numbering of UniformHemisphere(belts) (reference/hostUtil.cpp:3-14). */
+ * numbering of UniformHemisphere(belts) (reference/hostUtil.cpp:3-14).
+ *
+ * Ray j (a 64-bit ray number, j = first + i in bzr_emit) in full, so that a caller can restate it on the host; the
+ * device evaluates the real-valued steps in binary32, a restatement agrees with it to rounding:
+ *   uniforms   U(key, stream) is a pair (u, v) of 24-bit uniforms in [0, 1).  With 64-bit unsigned arithmetic (mod 2^64)
+ *                z = seed + 0x9E3779B97F4A7C15 * (2 * key + stream + 1)
+ *                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  h = z ^ (z >> 31)
+ *              (the splitmix64 finaliser), u = (h >> 40) / 2^24 (bits 40..63) and v = ((h >> 16) & 0xFFFFFF) / 2^24
+ *              (bits 16..39).
+ *   direction  (ci, tf) = U(j, 0): ci the cosine of the incidence, tf the turn as a fraction of a full turn.  With
+ *              si = sqrt(1 - ci^2) the direction is (ci, si cos(2 pi tf), si sin(2 pi tf)), normalised.
+ *   origin     the point number is j / rays_per_point (integer division) and (u, v) = U(point number, 1): all the
+ *              rays of a point share one origin.  The part is (j / (points_per_part * rays_per_point)) mod
+ *              (parts_u * parts_v), u fastest: pu = part mod parts_u, pv = part / parts_u.  Then a = (pu + u) / parts_u,
+ *              b = (pv + v) / parts_v and the origin is origin + a * edge_u + b * edge_v.
+ *   patch      belts is in 1..4096 (anything else: BZR_ERR_INVALID_ARGUMENT before anything is allocated or written).
+ *              Belt i (0 <= i < belts) spans the incidences [i, i + 1) * (pi / 2) / belts and holds
+ *              count[i] = ceil(4 * belts * sin((2 i + 1) pi / (4 * belts))) patches of equal turn width, numbered from
+ *              first[i] = count[0] + ... + count[i - 1].  (As the reference evaluates it: the sine's argument is the
+ *              binary32 value of (2 i + 1) / (4 belts) * pi, each of its steps rounded to binary32, the sine and the
+ *              product are binary64.  A binary64 argument gives another count where the product lies within rounding
+ *              of an integer: for one belt of 4096.)  The ray's belt is the one its incidence acos(ci) lies in
+ *              (the last one at ci = 0), its patch number first[belt] + min(floor(tf * count[belt]), count[belt] - 1).
+ *              A ray within rounding of a belt's or a patch's edge may be numbered on either side of it. */
 typedef struct bzr_emitter {
   float origin[3], edge_u[3], edge_v[3];
   uint32_t parts_u, parts_v, points_per_part, rays_per_point, belts;
@@ -495,7 +518,14 @@ typedef struct bzr_emitter {
 /* The illuminated rectangle: origin + a*axis_u + b*axis_v (unit, orthogonal axes), a in
  * [0, size_u), b in [0, size_v), bins_u x bins_v counting cells (row-major, u fastest).  A ray that
  * leaves the last lens (status OUTSIDE) lands where Plane::intersect (reference/3dGeomUtil.h:279-296)
- * meets the plane through origin with normal axis_u x axis_v. */
+ * meets the plane through origin with normal axis_u x axis_v.
+ *
+ * The cell rule: with n = axis_u x axis_v normalised, a ray (start s, direction d) meets the plane when
+ * |d . n| >= 1e-5 and t = (n . origin - n . s) / (d . n) > 0, at p = s + t d.  Its coordinates are
+ * a = (p - origin) . axis_u and b = (p - origin) . axis_v; it lands when 0 <= a < size_u and 0 <= b < size_v, in cell
+ * iu = min(floor(a / cell_u), bins_u - 1), iv = min(floor(b / cell_v), bins_v - 1) with cell_u = size_u / bins_u and
+ * cell_v = size_v / bins_v, and is counted in hist[iv][iu] (index iv * bins_u + iu).  All in binary32: a ray within
+ * rounding of a cell's or the target's edge may fall on either side of it. */
 typedef struct bzr_target {
   float origin[3], axis_u[3], axis_v[3];
   float size_u, size_v;
