@@ -105,6 +105,13 @@ _SIGS = {
                            _U32],
     "bzr_illuminate_media": [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, ctypes.c_uint64, _P, _P, _U32, _P, _P, _P, _P, _P,
                              _P, _P, _P, _U32],
+    "bzr_farfield_bin": [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _U32],
+    "bzr_illuminate_farfield": [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, ctypes.c_uint64, _P, _P, _U32, _P, _P, _P, _P, _P,
+                                _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P],
+    "bzr_farfield_cell": [_P, _P, _P],
+    "bzr_farfield_directions": [_P, _P, _P, _P],
+    "bzr_farfield_intensity": [_P, _P, _U32, ctypes.c_double, _P],
+    "bzr_debug_farfield_cells": [_P, _P, _U32, _P],
     "bzr_mesh_bounding_sphere": [_P, _P],
     "bzr_trimesh_create": [ctypes.POINTER(_P)],
     "bzr_trimesh_destroy": [_P],
@@ -137,12 +144,14 @@ _SIGS = {
     "bzr_debug_chunk_cap": [_P, _U32, ctypes.POINTER(_U32)],
     "bzr_debug_fresnel": [_P, _P, _U32, _P],
     "bzr_debug_attenuation": [_P, _P, _U32, _P],
+    "bzr_debug_farfield_rounds": [_P, _I32],
 }
 # entry points added without an ABI bump: an explicitly chosen earlier build (BZR_LIBRARY) may lack them
 _ADDED = ("bzr_trace_chain_power", "bzr_illuminate_power", "bzr_trace_chain_spectral", "bzr_illuminate_spectral",
           "bzr_dispersion_index", "bzr_trace_chain_tir", "bzr_illuminate_tir", "bzr_trace_chain_opl",
           "bzr_trace_chain_media", "bzr_trace_chain_absorb", "bzr_absorption_from_transmittance",
-          "bzr_illuminate_media", "bzr_debug_attenuation")
+          "bzr_illuminate_media", "bzr_debug_attenuation", "bzr_farfield_bin", "bzr_illuminate_farfield",
+          "bzr_farfield_cell", "bzr_farfield_directions", "bzr_farfield_intensity", "bzr_debug_farfield_cells")
 _RET = {"bzr_last_error": ctypes.c_char_p, "bzr_abi_version": _I32}
 
 _lib = None
@@ -997,46 +1006,179 @@ def illuminate_media(ctx: Context, lenses, ri_table, gap_table, glass_absorb, ga
 
 
 def _illuminate_reflecting(ctx, lenses, ri_table, media, em, total_rays, target, max_bounces, emission, surface, flux, hist,
-                           reflected_flux, reflected_hist, mode):
-    """illuminate_tir (media None) or illuminate_media (media = the gap table and the two absorption tables)."""
+                           reflected_flux, reflected_hist, mode, far=None):
+    """illuminate_tir (media None), illuminate_media (media = the gap table and the two absorption tables) or
+    illuminate_farfield (far = the frame and its three maps, each map or None; target may then be None)."""
     nl = len(lenses)
     handles = (_P * nl)(*[m.handle for m in lenses])
     table, nchan = _ri_table(ri_table, nl)
-    shape = (nchan, target.bins_v, target.bins_u)
-    if flux is None:
-        flux = np.zeros(shape, np.uint64)
+    rows = max(nchan, 1)
+    first = flux  # the buffer whose residency the maps made here follow
+    if far is not None:
+        first = next((a for a in (flux, hist, reflected_flux, reflected_hist) + tuple(far[1:]) if a is not None), None)
 
-    def like_flux(a, np_dtype, torch_dtype):
+    def like(a, shape, np_dtype, torch_dtype):
         if a is not None:
             return a
-        if _is_tensor(flux):
+        if _is_tensor(first):
             import torch
 
-            return torch.zeros(shape, dtype=getattr(torch, torch_dtype), device=flux.device)
+            return torch.zeros(shape, dtype=getattr(torch, torch_dtype), device=first.device)
         return np.zeros(shape, np_dtype)
 
-    hist = like_flux(hist, np.uint32, "int32")
-    reflected_flux = like_flux(reflected_flux, np.uint64, "int64")
-    reflected_hist = like_flux(reflected_hist, np.uint32, "int32")
+    if target is not None:
+        shape = (nchan, target.bins_v, target.bins_u)
+        flux = like(flux, shape, np.uint64, "int64")
+        first = flux if first is None else first
+        hist = like(hist, shape, np.uint32, "int32")
+        reflected_flux = like(reflected_flux, shape, np.uint64, "int64")
+        reflected_hist = like(reflected_hist, shape, np.uint32, "int32")
     f, h = _Buf(flux, np.uint64, True), _Buf(hist, np.uint32, True)
     rf, rh = _Buf(reflected_flux, np.uint64, True), _Buf(reflected_hist, np.uint32, True)
+    bufs = [f, h, rf, rh]
+    far_out = None
+    if far is not None:
+        frame = far[0]
+        fshape = (nchan, frame.bins_v, frame.bins_u)
+        far_out = {"flux": like(far[1], fshape, np.uint64, "int64"), "hist": like(far[2], fshape, np.uint32, "int32"),
+                   "reflected_flux": like(far[3], fshape, np.uint64, "int64")}
+        ff, fh = _Buf(far_out["flux"], np.uint64, True), _Buf(far_out["hist"], np.uint32, True)
+        frf = _Buf(far_out["reflected_flux"], np.uint64, True)
+        bufs += [ff, fh, frf]
+        fstats, fpower = (ctypes.c_uint64 * (2 * rows))(), (ctypes.c_uint64 * (2 * rows))()
     rad = Radiometry(int(emission), int(surface))
-    rows = max(nchan, 1)
     stats, power = (ctypes.c_uint64 * (4 * rows))(), (ctypes.c_uint64 * (4 * rows))()
     ledger = {k: np.zeros((rows, LEDGER_ROWS, LEDGER_FIELDS), np.uint64) for k in ("count", "power")}
-    res = _residency(f, h, rf, rh)
-    tail = (nl, nchan, ctypes.byref(em), int(total_rays), ctypes.byref(target), ctypes.byref(rad), int(max_bounces), f.ptr,
+    res = _residency(*bufs)
+    tail = (nl, nchan, ctypes.byref(em), int(total_rays), ctypes.byref(target) if target is not None else None,
+            ctypes.byref(rad), int(max_bounces), f.ptr,
             h.ptr, rf.ptr, rh.ptr, stats, power, ledger["count"].ctypes.data, ledger["power"].ctypes.data, res | mode)
     with _stream_for(ctx, res):
-        if media is None:
+        if far is not None:
+            _check(lib().bzr_illuminate_farfield(ctx.handle, handles, table.ctypes.data if table.size else None,
+                                                 *[_table_ptr(a) for a in media], *tail, ctypes.byref(frame), ff.ptr,
+                                                 fh.ptr, frf.ptr, fstats, fpower))
+        elif media is None:
             _check(lib().bzr_illuminate_tir(ctx.handle, handles, table.ctypes.data if table.size else None, *tail))
         else:
             _check(lib().bzr_illuminate_media(ctx.handle, handles, table.ctypes.data if table.size else None,
                                               *[_table_ptr(a) for a in media], *tail))
-    return (flux, hist, reflected_flux, reflected_hist,
-            [dict(zip(ILLUM_STATS, [int(x) for x in stats[4 * c:4 * c + 4]])) for c in range(nchan)],
-            [dict(zip(ILLUM_STATS, [int(x) for x in power[4 * c:4 * c + 4]])) for c in range(nchan)],
-            {k: v[:nchan] for k, v in ledger.items()})
+    seven = (flux, hist, reflected_flux, reflected_hist,
+             [dict(zip(ILLUM_STATS, [int(x) for x in stats[4 * c:4 * c + 4]])) for c in range(nchan)],
+             [dict(zip(ILLUM_STATS, [int(x) for x in power[4 * c:4 * c + 4]])) for c in range(nchan)],
+             {k: v[:nchan] for k, v in ledger.items()})
+    if far is None:
+        return seven
+    far_out["stats"] = [dict(zip(FAR_STATS, [int(x) for x in fstats[2 * c:2 * c + 2]])) for c in range(nchan)]
+    far_out["power"] = [dict(zip(FAR_STATS, [int(x) for x in fpower[2 * c:2 * c + 2]])) for c in range(nchan)]
+    return seven + (far_out,)
+
+
+# ------------------------------------------------------------ far field
+class FarField(ctypes.Structure):
+    """bzr_farfield: unit, orthogonal axis_u / axis_v (the pole is axis_u x axis_v), the map [-extent, extent)^2 of the
+    Lambert azimuthal equal-area projection about the pole (0 < extent <= sqrt(2)), bins_u x bins_v cells of equal
+    solid angle."""
+    _fields_ = [("axis_u", _F * 3), ("axis_v", _F * 3), ("extent", _F), ("bins_u", _U32), ("bins_v", _U32)]
+
+
+FAR_STATS = ("seen", "binned")  # BZR_FAR_* ids
+SQRT2 = float(np.float32(np.sqrt(2.0)))  # the largest extent: the float at or below sqrt(2), 0x3FB504F3
+
+
+def farfield_bin(ctx: Context, far: FarField, rays, weight=None, status=None, channel=None, nchan=1, flux=None,
+                 hist=None, mode=MODE_PARITY):
+    """bzr_farfield_bin: bins a traced batch (rays [6, n] as trace_chain_* returns them; weight, status, channel [n] or
+    None) by direction.  Returns (flux uint64 [nchan, bins_v, bins_u] in 32.32 fixed point, hist uint32 of the same
+    shape -- accumulated into the arrays given --, stats: a list of nchan dicts {"seen", "binned"}, power: the same
+    with the sums of q(w)).  numpy arrays or device tensors, all on one side."""
+    n = _n_of(rays)
+    shape = (int(nchan), far.bins_v, far.bins_u)
+    if flux is None:
+        if _is_tensor(rays):
+            import torch
+
+            flux = torch.zeros(shape, dtype=torch.int64, device=rays.device)
+        else:
+            flux = np.zeros(shape, np.uint64)
+    if hist is None:
+        if _is_tensor(flux):
+            import torch
+
+            hist = torch.zeros(shape, dtype=torch.int32, device=flux.device)
+        else:
+            hist = np.zeros(shape, np.uint32)
+    r, w, s = _Buf(rays, np.float32), _Buf(weight, np.float32), _Buf(status, np.uint32)
+    c, f, h = _Buf(channel, np.uint8), _Buf(flux, np.uint64, True), _Buf(hist, np.uint32, True)
+    for name, a in (("weight", weight), ("status", status), ("channel", channel)):
+        if a is not None and tuple(a.shape if _is_tensor(a) else np.shape(a)) != (n,):
+            raise BzrError(f"{name} must be [{n}]")
+    rows = max(int(nchan), 1)
+    stats, power = (ctypes.c_uint64 * (2 * rows))(), (ctypes.c_uint64 * (2 * rows))()
+    res = _residency(r, w, s, c, f, h)
+    with _stream_for(ctx, res):
+        _check(lib().bzr_farfield_bin(ctx.handle, ctypes.byref(far), r.ptr, w.ptr, s.ptr, c.ptr, n, int(nchan), f.ptr,
+                                      h.ptr, stats, power, res | mode))
+    return (flux, hist, [dict(zip(FAR_STATS, [int(x) for x in stats[2 * k:2 * k + 2]])) for k in range(int(nchan))],
+            [dict(zip(FAR_STATS, [int(x) for x in power[2 * k:2 * k + 2]])) for k in range(int(nchan))])
+
+
+def illuminate_farfield(ctx: Context, lenses, ri_table, gap_table, glass_absorb, gap_absorb, em: Emitter, total_rays: int,
+                        target, far: FarField, max_bounces=4, emission=EMISSION_LAMBERT, surface=SURFACE_FRESNEL,
+                        flux=None, hist=None, reflected_flux=None, reflected_hist=None, far_flux=None, far_hist=None,
+                        far_reflected_flux=None, mode=MODE_PARITY):
+    """illuminate_media with a far-field frame -> illuminate_media's seven-tuple plus a dict of the far outputs: "flux",
+    "hist" and "reflected_flux" [nchan, far.bins_v, far.bins_u] (every traced ray that left the last lens, binned by
+    direction with its final weight; the reflected map holds those with at least one reflection), "stats" and "power":
+    lists of nchan dicts {"seen", "binned"}, "seen" being the channel's exited count / power.  target None: no near
+    maps (the first four entries are None, the near maps must not be given) and the landed entries are 0."""
+    nl = len(lenses)
+    _, nchan = _ri_table(ri_table, nl)
+    media = (_gap_table(gap_table, nl, nchan), _absorb_table(glass_absorb, "glass_absorb", nl, nchan),
+             _absorb_table(gap_absorb, "gap_absorb", nl, nchan))
+    if target is None and any(a is not None for a in (flux, hist, reflected_flux, reflected_hist)):
+        raise BzrError("target maps given without a target")
+    return _illuminate_reflecting(ctx, lenses, ri_table, media, em, total_rays, target, max_bounces, emission, surface,
+                                  flux, hist, reflected_flux, reflected_hist, mode,
+                                  far=(far, far_flux, far_hist, far_reflected_flux))
+
+
+def farfield_cell(far: FarField, directions) -> np.ndarray:
+    """bzr_farfield_cell on the host (the device's twin, bit for bit): directions [n, 3] (or [3]) float32 -> int32 cell
+    indices iv * bins_u + iu, -1 where a direction is not binned."""
+    d = np.ascontiguousarray(directions, np.float32)
+    one = d.ndim == 1
+    d = d.reshape(-1, 3)
+    out = np.empty(len(d), np.int32)
+    _check(lib().bzr_debug_farfield_cells(ctypes.byref(far), d.ctypes.data, len(d), out.ctypes.data))
+    return out[0] if one else out
+
+
+def farfield_directions(far: FarField):
+    """Each cell centre in float64: (unit directions [bins_v, bins_u, 3], polar angle from the pole [bins_v, bins_u],
+    azimuth atan2(Y, X) [bins_v, bins_u]), radians."""
+    d = np.empty((far.bins_v, far.bins_u, 3), np.float64)
+    polar, azimuth = np.empty((far.bins_v, far.bins_u), np.float64), np.empty((far.bins_v, far.bins_u), np.float64)
+    _check(lib().bzr_farfield_directions(ctypes.byref(far), d.ctypes.data, polar.ctypes.data, azimuth.ctypes.data))
+    return d, polar, azimuth
+
+
+def farfield_intensity(far: FarField, flux, scale: float = 1.0) -> np.ndarray:
+    """Power per steradian: scale x flux / 2^32 / cell solid angle, float64 of flux's shape ([..., bins_v, bins_u]);
+    scale = 1 / emitted power gives a normalised pattern."""
+    a = np.ascontiguousarray(flux.cpu().numpy() if _is_tensor(flux) else flux).view(np.uint64)
+    if a.shape[-2:] != (far.bins_v, far.bins_u):
+        raise BzrError(f"flux must be [..., {far.bins_v}, {far.bins_u}], got {a.shape}")
+    out = np.empty(a.shape, np.float64)
+    nmaps = a.size // (far.bins_v * far.bins_u)
+    _check(lib().bzr_farfield_intensity(ctypes.byref(far), a.ctypes.data, nmaps, float(scale), out.ctypes.data))
+    return out
+
+
+def debug_farfield_rounds(ctx: Context, rounds: int):
+    """bzr_debug_farfield_rounds: k_land_far's combine rounds for the following calls (0: per-lane atomics, 64:
+    unbounded, negative: the default)."""
+    _check(lib().bzr_debug_farfield_rounds(ctx.handle, int(rounds)))
 
 
 def flux_to_float(flux) -> np.ndarray:
@@ -1189,5 +1331,6 @@ class TriMesh:
 __all__ = [
     "BzrError", "Context", "DeviceMesh", "TriMesh", "intersect", "patch_intersect", "refract", "trace_chain", "interpolate",
     "Emitter", "Target", "emit", "illuminate", "bounding_sphere",
+    "FarField", "farfield_bin", "illuminate_farfield", "farfield_cell", "farfield_directions", "farfield_intensity",
     "device_count", "lib", "exported_symbols", "LIB_PATH",
 ]

@@ -58,6 +58,7 @@ struct bzr_ctx {
   // kModeAbsorb's two absorption tables [nlens][nchan] lie behind the gap table, each part with its own host copy
   // (trace.hip upload_absorb_table).
   std::vector<float> glass_absorb_host, gap_absorb_host;
+  int32_t far_rounds = -1;  // test hook (bzr_debug_farfield_rounds): k_land_far's combine rounds, < 0: the default
 };
 
 // BZR_RAYS_AOS (frame_pack.hip): n rays between the reference's [n][6] records and the kernels' [6][n] rows,

@@ -116,4 +116,27 @@ __device__ __forceinline__ int32_t target_cell(const bzr_target &tg, f3 n, float
   return (int32_t)(iv * tg.bins_u + iu);
 }
 
+// The far-field frame as the kernels take it (include/bzr.h bzr_farfield): the pole, the two axes, R, S = R + R and
+// the cell sizes S / bins, all made on the host.
+struct FarFrame {
+  float n[3], au[3], av[3];
+  float r, s, cu, cv;
+  uint32_t bins_u, bins_v;
+};
+// Far-field cell of direction d, false if it is not binned: the Lambert azimuthal equal-area projection about the
+// pole, operation by operation as bzr.h states it -- correctly rounded in both modes.
+__device__ __forceinline__ bool farfield_cell(const FarFrame &f, f3 d, uint32_t &cell) {
+  const float mu = exact::dot(d, mk(f.n[0], f.n[1], f.n[2]));
+  const float a = exact::dot(d, mk(f.au[0], f.au[1], f.au[2])), b = exact::dot(d, mk(f.av[0], f.av[1], f.av[2]));
+  const float g = 1.0f + mu;
+  const float k = exact::sqrt_rn(exact::div_rn(2.0f, g));
+  const float u = a * k + f.r, v = b * k + f.r;
+  if (!(g > 0.0f && u >= 0.0f && u < f.s && v >= 0.0f && v < f.s)) return false;
+  uint32_t iu = (uint32_t)exact::div_rn(u, f.cu), iv = (uint32_t)exact::div_rn(v, f.cv);
+  if (iu >= f.bins_u) iu = f.bins_u - 1u;
+  if (iv >= f.bins_v) iv = f.bins_v - 1u;
+  cell = iv * f.bins_u + iu;
+  return true;
+}
+
 }  // namespace bzr_dev

@@ -4693,6 +4693,75 @@ __global__ __launch_bounds__(kBlock) void k_land_tir(bzr_target tg, float4 plane
   keyed_rows<BZR_LEDGER_FIELDS, BZR_LEDGER_FIELDS>(traced, ch * BZR_LEDGER_ROWS + row, in, q, t.count, t.power);
 }
 
+// The far-field landing kernel (bzr_farfield_bin, bzr_illuminate_farfield): one thread per ray, binned by direction
+// (emitter.hpp farfield_cell).  A ray is seen when `status` is null or its status is OUTSIDE, and its channel (0
+// without `channel`) is below nchan; a seen ray that is binned adds q(w) (w = 1 without `weight`) to flux[key] and one
+// count to hist[key], key = channel * cells + cell (each map may be null), and to rflux[key] too when `bounces` says
+// it reflected (both null in bzr_farfield_bin).  stats and power are [nchan][2] (SEEN, BINNED; null: not kept),
+// reduced per channel like channel_rows' rows.
+// Far fields are peaked: a collimator sends most of a wave's lanes to a few keys, and 64-bit atomics on one address
+// serialise.  So up to `rounds` times the lowest pending lane names a key, the lanes that hold it are summed
+// (wave_sum_u64; a key held by one lane skips the sum) and that lane alone adds the totals; the lanes still pending
+// after that issue their own atomics, so a diffuse wave does not pay 64 rounds.  Integer sums: the same bits for
+// every `rounds` (0: plain per-lane atomics).
+__global__ __launch_bounds__(kBlock) void k_land_far(FarFrame f, uint32_t cells, const float *__restrict__ rays,
+                                                     uint32_t ld, uint32_t n, const uint32_t *__restrict__ status,
+                                                     const float *__restrict__ weight,
+                                                     const uint8_t *__restrict__ channel, uint32_t nchan,
+                                                     const uint32_t *__restrict__ bounces,
+                                                     unsigned long long *__restrict__ flux, uint32_t *__restrict__ hist,
+                                                     unsigned long long *__restrict__ rflux,
+                                                     unsigned long long *__restrict__ stats,
+                                                     unsigned long long *__restrict__ power, uint32_t rounds) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  bool seen = false, binned = false, refl = false;
+  unsigned long long q = 0ull;
+  uint32_t ch = 0u, key = 0u;
+  if (i < n && (!status || status[i] == BZR_RR_OUTSIDE)) {
+    if (channel) ch = channel[i];
+    if (ch < nchan) {
+      seen = true;
+      q = power_q32(weight ? weight[i] : 1.0f);
+      const f3 d = mk(rays[(size_t)3 * ld + i], rays[(size_t)4 * ld + i], rays[(size_t)5 * ld + i]);
+      uint32_t cell;
+      if (farfield_cell(f, d, cell)) {
+        binned = true;
+        key = ch * cells + cell;
+        refl = rflux && bounces[i] != 0u;
+      }
+    }
+  }
+  const uint32_t lane = threadIdx.x & 63u;
+  unsigned long long todo = __ballot(binned);
+  for (uint32_t r = 0; r < rounds && todo; ++r) {
+    const uint32_t lead = (uint32_t)__ffsll((long long)todo) - 1u;
+    const uint32_t k = __shfl(key, (int)lead, 64);
+    const bool mine = binned && key == k;
+    const unsigned long long held = __ballot(mine), bounced = __ballot(mine && refl);
+    unsigned long long tq = q, tr = q;
+    if (held & (held - 1ull)) {  // more than one lane holds the key (wave-uniform)
+      tq = wave_sum_u64(mine ? q : 0ull);
+      tr = bounced ? wave_sum_u64(mine && refl ? q : 0ull) : 0ull;
+    }
+    if (lane == lead) {
+      if (flux && tq) atomicAdd(&flux[k], tq);
+      if (hist) atomicAdd(&hist[k], (uint32_t)__popcll(held));
+      if (bounced && tr) atomicAdd(&rflux[k], tr);
+    }
+    todo &= ~held;
+  }
+  if (binned && ((todo >> lane) & 1ull)) {
+    if (flux && q) atomicAdd(&flux[key], q);
+    if (hist) atomicAdd(&hist[key], 1u);
+    if (refl && q) atomicAdd(&rflux[key], q);
+  }
+  if (stats) {
+    const bool in[2] = {seen, binned};
+    static_assert(BZR_FAR_SEEN == 0 && BZR_FAR_BINNED == 1, "the far-field rows' field order");
+    keyed_rows<2, 2u>(seen, ch, in, q, stats, power);
+  }
+}
+
 // UniformHemisphere(belts)'s patch table (reference/hostUtil.cpp:3-14, same float expressions) and the
 // belt boundaries cos(i * width) the device compares cos(incidence) against.
 bzr_status belt_tables(uint32_t belts, std::vector<float> &cos_lo, std::vector<uint32_t> &count,
@@ -4787,6 +4856,27 @@ extern "C" bzr_status bzr_emit(bzr_ctx *ctx, const bzr_emitter *em, uint64_t fir
 // bzr_illuminate_tir: spectral with `tir`, the chain that reflects (kModeTir) and what only that call returns.
 // bzr_illuminate_media: the same with tir->media, the chain that reflects, refracts between media and absorbs
 // (kModeAbsorb); k_land_tir lands its rays as they are (the weights carry everything).
+// bzr_illuminate_farfield: the same with tir->far, k_land_far after every batch's chain beside k_land_tir; without a
+// target k_land_tir lands on a rectangle of size 0 that no ray meets (its EXITED rows and the ledger are still wanted).
+struct IllumFar {
+  const bzr_farfield *frame;
+  uint64_t *flux;  // [nchan][cells of the frame], host or device memory like the near maps; flux or hist is given
+  uint32_t *hist;
+  uint64_t *rflux;           // the same for rays that reflected; may be null
+  uint64_t *stats, *power;   // [nchan][2], host memory; each may be null
+};
+extern "C" const char *bzr_internal_farfield_frame(const bzr_farfield *far, uint32_t nchan, float out[13]);  // capi_host.cpp
+// k_land_far's combine rounds.  0: plain per-lane atomics -- what the measurement chose (on a 5 degree
+// cone into 60 cells every number of rounds was slower than none); bzr_debug_farfield_rounds sets another for an A/B.
+constexpr uint32_t kFarRounds = 0;
+static bzr_status far_frame(const bzr_farfield *far, uint32_t nchan, FarFrame &f) {
+  float v[13];
+  if (const char *why = bzr_internal_farfield_frame(far, nchan, v)) return set_error(BZR_ERR_INVALID_ARGUMENT, why);
+  for (int k = 0; k < 3; ++k) f.n[k] = v[k], f.au[k] = v[3 + k], f.av[k] = v[6 + k];
+  f.r = v[9], f.s = v[10], f.cu = v[11], f.cv = v[12];
+  f.bins_u = far->bins_u, f.bins_v = far->bins_v;
+  return BZR_OK;
+}
 struct IllumTir {
   uint32_t max_bounces;
   uint64_t *rflux;          // the stray-light maps [nchan][cells], host or device memory like flux; each may be null
@@ -4796,6 +4886,7 @@ struct IllumTir {
   // tables [nlens][nchan] (host memory, each may be null: vacuum, all zero)
   bool media = false;
   const float *gap = nullptr, *glass_absorb = nullptr, *gap_absorb = nullptr;
+  const IllumFar *far = nullptr;  // bzr_illuminate_farfield
 };
 static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
                              const bzr_emitter *em, uint64_t total_rays, const bzr_target *tg, const bzr_radiometry *rad,
@@ -4816,16 +4907,29 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
       return s;
   }
   const uint32_t NC = spectral ? nchan : 1u;
+  const IllumFar *const far = tir ? tir->far : nullptr;
+  FarFrame ff{};
+  const bzr_target nowhere{{0.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f}, {0.0f, 0.0f, 1.0f}, 0.0f, 0.0f, 1u, 1u};
+  const bool landing = tg != nullptr;  // false: far field only (k_land_tir meets `nowhere`)
+  if (far) {
+    if (bzr_status s = far_frame(far->frame, nchan, ff)) return s;
+    if (!far->flux && !far->hist) return set_error(BZR_ERR_INVALID_ARGUMENT, "null far_flux_q32 and far_hist");
+    if (!landing) {
+      if (flux || hist || tir->rflux || tir->rhist)
+        return set_error(BZR_ERR_INVALID_ARGUMENT, "target maps given without a target");
+      tg = &nowhere;
+    }
+  }
   if (!lenses || !ri || !tg || (!with_power && !hist)) return set_error(BZR_ERR_INVALID_ARGUMENT, "null argument");
   if (with_power) {
-    if (!flux) return set_error(BZR_ERR_INVALID_ARGUMENT, "null flux_q32");
+    if (!flux && landing) return set_error(BZR_ERR_INVALID_ARGUMENT, "null flux_q32");
     if (total_rays >= (1ull << 32)) return set_error(BZR_ERR_INVALID_ARGUMENT, "total_rays must be below 2^32 (64-bit power sums)");
     if (rad->emission > BZR_EMISSION_LAMBERT) return set_error(BZR_ERR_INVALID_ARGUMENT, "unknown emission");
     if (rad->surface > BZR_SURFACE_FRESNEL) return set_error(BZR_ERR_INVALID_ARGUMENT, "unknown surface");
   }
   const bool fresnel = with_power && rad->surface == BZR_SURFACE_FRESNEL;
   if (bzr_status s = check_emitter(em)) return s;
-  if (!tg->bins_u || !tg->bins_v || !(tg->size_u > 0.0f) || !(tg->size_v > 0.0f))
+  if (landing && (!tg->bins_u || !tg->bins_v || !(tg->size_u > 0.0f) || !(tg->size_v > 0.0f)))
     return set_error(BZR_ERR_INVALID_ARGUMENT, "target bins and sizes must be positive");
   if (bzr_status s = check_flags(flags)) return s;
   LensSet set{};
@@ -4879,12 +4983,18 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   float *d_opl = nullptr;
   unsigned long long *d_rflux = tir ? reinterpret_cast<unsigned long long *>(tir->rflux) : nullptr;
   unsigned long long *d_lcount = nullptr, *d_lpower = nullptr;
+  // far: the two rows [NC][2] and, for a host caller, the far maps (zeroed, added back like rflux)
+  const size_t fmaps = far ? (size_t)ff.bins_u * ff.bins_v * NC : 0;
+  unsigned long long *d_fflux = far ? reinterpret_cast<unsigned long long *>(far->flux) : nullptr;
+  unsigned long long *d_frflux = far ? reinterpret_cast<unsigned long long *>(far->rflux) : nullptr;
+  uint32_t *d_fhist = far ? far->hist : nullptr;
+  unsigned long long *d_fstats = nullptr, *d_fpower = nullptr;
   if (bzr_status s = carve_buffer(ctx->scratch, ctx->scratch_bytes, [&](Staging &st) {
         belt_layout(st, em->belts, bt);
         st.take(d_rays, (size_t)B * 6), st.take(d_st, B), st.take(d_seg, B), st.take(d_stats, 4 * NC);
         if (host && hist) st.take(d_hist, maps);
         if (with_power) st.take(d_w, B), st.take(d_power, 4 * NC);
-        if (with_power && host) st.take(d_flux, maps);
+        if (with_power && host && flux) st.take(d_flux, maps);
         if (spectral) st.take(d_ch, B);
         if (tir) st.take(d_bnc, B);
         if (media) st.take(d_opl, B);
@@ -4892,6 +5002,10 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
         if (tir) st.take(d_lcount, ledger), st.take(d_lpower, ledger);
         if (tir && host && tir->rflux) st.take(d_rflux, maps);
         if (tir && host && tir->rhist) st.take(d_rhist, maps);
+        if (far) st.take(d_fstats, 2 * NC), st.take(d_fpower, 2 * NC);
+        if (far && host && far->flux) st.take(d_fflux, fmaps);
+        if (far && host && far->hist) st.take(d_fhist, fmaps);
+        if (far && host && far->rflux) st.take(d_frflux, fmaps);
       }))
     return s;
   if (bzr_status s = upload_belts(ctx, bt, belts)) return s;
@@ -4899,7 +5013,14 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   if (host && hist) BZR_HIP(hipMemsetAsync(d_hist, 0, maps * 4, ctx->stream));
   if (with_power) {
     BZR_HIP(hipMemsetAsync(d_power, 0, 32 * NC, ctx->stream));
-    if (host) BZR_HIP(hipMemsetAsync(d_flux, 0, maps * 8, ctx->stream));
+    if (host && flux) BZR_HIP(hipMemsetAsync(d_flux, 0, maps * 8, ctx->stream));
+  }
+  if (far) {
+    BZR_HIP(hipMemsetAsync(d_fstats, 0, 16 * NC, ctx->stream));
+    BZR_HIP(hipMemsetAsync(d_fpower, 0, 16 * NC, ctx->stream));
+    if (host && far->flux) BZR_HIP(hipMemsetAsync(d_fflux, 0, fmaps * 8, ctx->stream));
+    if (host && far->hist) BZR_HIP(hipMemsetAsync(d_fhist, 0, fmaps * 4, ctx->stream));
+    if (host && far->rflux) BZR_HIP(hipMemsetAsync(d_frflux, 0, fmaps * 8, ctx->stream));
   }
   if (tir) {
     BZR_HIP(hipMemsetAsync(d_lcount, 0, ledger * 8, ctx->stream));
@@ -4962,6 +5083,11 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
       hipLaunchKernelGGL(land, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg, make_float4(pn.x, pn.y, pn.z, pc),
                          cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats, d_w, d_flux, d_power, (const uint8_t *)d_ch,
                          spectral ? (uint32_t)cells : 0u);
+    if (far)
+      hipLaunchKernelGGL(k_land_far, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, ff, ff.bins_u * ff.bins_v,
+                         (const float *)d_rays, B, m, (const uint32_t *)d_st, (const float *)d_w, (const uint8_t *)d_ch,
+                         nchan, (const uint32_t *)d_bnc, d_fflux, d_fhist, d_frflux, d_fstats, d_fpower,
+                         ctx->far_rounds < 0 ? kFarRounds : (uint32_t)ctx->far_rounds);
     BZR_HIP(hipGetLastError());
   }
   unsigned long long hs[4 * kMaxChannels];
@@ -4969,10 +5095,20 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   std::vector<uint32_t> hh(host && hist ? maps : 0);
   if (host && hist) BZR_HIP(hipMemcpyAsync(hh.data(), d_hist, maps * 4, hipMemcpyDeviceToHost, ctx->stream));
   unsigned long long hp[4 * kMaxChannels] = {};
-  std::vector<unsigned long long> hf(host && with_power ? maps : 0);
+  std::vector<unsigned long long> hf(host && with_power && flux ? maps : 0);
   if (with_power) {
     BZR_HIP(hipMemcpyAsync(hp, d_power, 32 * NC, hipMemcpyDeviceToHost, ctx->stream));
-    if (host) BZR_HIP(hipMemcpyAsync(hf.data(), d_flux, maps * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (!hf.empty()) BZR_HIP(hipMemcpyAsync(hf.data(), d_flux, maps * 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  unsigned long long hfs[4 * kMaxChannels] = {};  // the far rows: [NC][2] stats, then [NC][2] power
+  std::vector<unsigned long long> hff(far && host && far->flux ? fmaps : 0), hfr(far && host && far->rflux ? fmaps : 0);
+  std::vector<uint32_t> hfh(far && host && far->hist ? fmaps : 0);
+  if (far) {
+    BZR_HIP(hipMemcpyAsync(hfs, d_fstats, 16 * NC, hipMemcpyDeviceToHost, ctx->stream));
+    BZR_HIP(hipMemcpyAsync(hfs + 2 * NC, d_fpower, 16 * NC, hipMemcpyDeviceToHost, ctx->stream));
+    if (!hff.empty()) BZR_HIP(hipMemcpyAsync(hff.data(), d_fflux, fmaps * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (!hfh.empty()) BZR_HIP(hipMemcpyAsync(hfh.data(), d_fhist, fmaps * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (!hfr.empty()) BZR_HIP(hipMemcpyAsync(hfr.data(), d_frflux, fmaps * 8, hipMemcpyDeviceToHost, ctx->stream));
   }
   std::vector<unsigned long long> hrf(tir && host && tir->rflux ? maps : 0), hl(tir ? 2 * ledger : 0);
   std::vector<uint32_t> hrh(tir && host && tir->rhist ? maps : 0);
@@ -4991,8 +5127,14 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
     for (size_t k = 0; k < ledger; ++k) tir->power[k] = hl[ledger + k];
   if (host && hist)
     for (size_t k = 0; k < maps; ++k) hist[k] += hh[k];
-  if (host && with_power)
-    for (size_t k = 0; k < maps; ++k) flux[k] += hf[k];
+  for (size_t k = 0; k < hf.size(); ++k) flux[k] += hf[k];
+  for (size_t k = 0; k < hff.size(); ++k) far->flux[k] += hff[k];
+  for (size_t k = 0; k < hfh.size(); ++k) far->hist[k] += hfh[k];
+  for (size_t k = 0; k < hfr.size(); ++k) far->rflux[k] += hfr[k];
+  if (far && far->stats)
+    for (uint32_t k = 0; k < 2 * NC; ++k) far->stats[k] = hfs[k];
+  if (far && far->power)
+    for (uint32_t k = 0; k < 2 * NC; ++k) far->power[k] = hfs[2 * NC + k];
   if (stats)
     for (uint32_t k = 0; k < 4 * NC; ++k) stats[k] = hs[k];
   if (power)
@@ -5050,4 +5192,107 @@ extern "C" bzr_status bzr_illuminate_media(bzr_ctx *ctx, const bzr_mesh *const *
   tir.gap_absorb = gap_absorb;
   return illuminate(ctx, lenses, ri_table, nlens, em, total_rays, tg, rad, flux_q32, hist, stats, power_q32, flags, true,
                     nchan, &tir);
+}
+
+extern "C" bzr_status bzr_illuminate_farfield(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                              const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                              uint32_t nlens, uint32_t nchan, const bzr_emitter *em, uint64_t total_rays,
+                                              const bzr_target *tg, const bzr_radiometry *rad, uint32_t max_bounces,
+                                              uint64_t *flux_q32, uint32_t *hist, uint64_t *reflected_flux_q32,
+                                              uint32_t *reflected_hist, uint64_t *stats, uint64_t *power_q32,
+                                              uint64_t *ledger_count, uint64_t *ledger_power_q32, uint32_t flags,
+                                              const bzr_farfield *far, uint64_t *far_flux_q32, uint32_t *far_hist,
+                                              uint64_t *far_reflected_flux_q32, uint64_t *far_stats,
+                                              uint64_t *far_power_q32) {
+  if (!rad) return set_error(BZR_ERR_INVALID_ARGUMENT, "null radiometry");
+  FarFrame checked{};  // (the frame's own checks need no context: ahead of illuminate()'s)
+  if (bzr_status s = far_frame(far, nchan, checked)) return s;
+  const IllumFar ifar{far, far_flux_q32, far_hist, far_reflected_flux_q32, far_stats, far_power_q32};
+  IllumTir tir{max_bounces, reflected_flux_q32, reflected_hist, ledger_count, ledger_power_q32};
+  tir.media = true;
+  tir.gap = gap_table;
+  tir.glass_absorb = glass_absorb;
+  tir.gap_absorb = gap_absorb;
+  tir.far = &ifar;
+  return illuminate(ctx, lenses, ri_table, nlens, em, total_rays, tg, rad, flux_q32, hist, stats, power_q32, flags, true,
+                    nchan, &tir);
+}
+
+// Host pointers: the rows and zeroed maps are staged in the context's carve, and the call waits (like bzr_emit).
+// Device pointers: k_land_far adds straight into the caller's maps; only the two host rows make the call wait.
+extern "C" bzr_status bzr_farfield_bin(bzr_ctx *ctx, const bzr_farfield *far, const float *rays_soa, const float *weight,
+                                       const uint32_t *status, const uint8_t *channel, uint32_t n, uint32_t nchan,
+                                       uint64_t *far_flux_q32, uint32_t *far_hist, uint64_t *far_stats,
+                                       uint64_t *far_power_q32, uint32_t flags) {
+  if (bzr_status s = check_flags(flags)) return s;
+  FarFrame ff{};
+  if (bzr_status s = far_frame(far, nchan, ff)) return s;
+  if (!far_flux_q32 && !far_hist) return set_error(BZR_ERR_INVALID_ARGUMENT, "null far_flux_q32 and far_hist");
+  if (n == 0) return BZR_OK;
+  if (!ctx) return set_error(BZR_ERR_INVALID_ARGUMENT, "null context");
+  if (!rays_soa) return set_error(BZR_ERR_INVALID_ARGUMENT, "null buffer");
+  DeviceGuard g(ctx->device);
+  const bool host = !(flags & BZR_DEVICE_PTRS), rows = far_stats || far_power_q32;
+  const size_t maps = (size_t)ff.bins_u * ff.bins_v * nchan;
+  const float *d_rays = rays_soa, *d_w = weight;
+  const uint32_t *d_st = status;
+  const uint8_t *d_ch = channel;
+  unsigned long long *d_flux = reinterpret_cast<unsigned long long *>(far_flux_q32), *d_stats = nullptr, *d_power = nullptr;
+  uint32_t *d_hist = far_hist;
+  if (host || rows)
+    if (bzr_status s = carve_buffer(ctx->scratch, ctx->scratch_bytes, [&](Staging &st) {
+          if (rows) st.take(d_stats, 2 * nchan), st.take(d_power, 2 * nchan);
+          if (!host) return;
+          st.take(d_rays, (size_t)n * 6);
+          if (weight) st.take(d_w, n);
+          if (status) st.take(d_st, n);
+          if (channel) st.take(d_ch, n);
+          if (far_flux_q32) st.take(d_flux, maps);
+          if (far_hist) st.take(d_hist, maps);
+        }))
+      return s;
+  if (rows) {
+    BZR_HIP(hipMemsetAsync(d_stats, 0, 16 * nchan, ctx->stream));
+    BZR_HIP(hipMemsetAsync(d_power, 0, 16 * nchan, ctx->stream));
+  }
+  if (host) {
+    BZR_HIP(hipMemcpyAsync(const_cast<float *>(d_rays), rays_soa, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
+    if (weight) BZR_HIP(hipMemcpyAsync(const_cast<float *>(d_w), weight, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (status)
+      BZR_HIP(hipMemcpyAsync(const_cast<uint32_t *>(d_st), status, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (channel) BZR_HIP(hipMemcpyAsync(const_cast<uint8_t *>(d_ch), channel, n, hipMemcpyHostToDevice, ctx->stream));
+    if (far_flux_q32) BZR_HIP(hipMemsetAsync(d_flux, 0, maps * 8, ctx->stream));
+    if (far_hist) BZR_HIP(hipMemsetAsync(d_hist, 0, maps * 4, ctx->stream));
+  }
+  const uint32_t grid = (uint32_t)(((uint64_t)n + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(k_land_far, dim3(grid), dim3(kBlock), 0, ctx->stream, ff, ff.bins_u * ff.bins_v, d_rays, n, n, d_st,
+                     d_w, d_ch, nchan, (const uint32_t *)nullptr, d_flux, d_hist, (unsigned long long *)nullptr, d_stats,
+                     d_power, ctx->far_rounds < 0 ? kFarRounds : (uint32_t)ctx->far_rounds);
+  BZR_HIP(hipGetLastError());
+  if (!host && !rows) return BZR_OK;
+  unsigned long long hs[4 * kMaxChannels] = {};
+  std::vector<unsigned long long> hf(host && far_flux_q32 ? maps : 0);
+  std::vector<uint32_t> hh(host && far_hist ? maps : 0);
+  if (rows) {
+    BZR_HIP(hipMemcpyAsync(hs, d_stats, 16 * nchan, hipMemcpyDeviceToHost, ctx->stream));
+    BZR_HIP(hipMemcpyAsync(hs + 2 * nchan, d_power, 16 * nchan, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (!hf.empty()) BZR_HIP(hipMemcpyAsync(hf.data(), d_flux, maps * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (!hh.empty()) BZR_HIP(hipMemcpyAsync(hh.data(), d_hist, maps * 4, hipMemcpyDeviceToHost, ctx->stream));
+  BZR_HIP(hipStreamSynchronize(ctx->stream));
+  for (size_t k = 0; k < hf.size(); ++k) far_flux_q32[k] += hf[k];
+  for (size_t k = 0; k < hh.size(); ++k) far_hist[k] += hh[k];
+  if (far_stats)
+    for (uint32_t k = 0; k < 2 * nchan; ++k) far_stats[k] = hs[k];
+  if (far_power_q32)
+    for (uint32_t k = 0; k < 2 * nchan; ++k) far_power_q32[k] = hs[2 * nchan + k];
+  return BZR_OK;
+}
+
+extern "C" int32_t bzr_debug_farfield_rounds(void *ctxp, int32_t rounds) {
+  bzr_ctx *ctx = static_cast<bzr_ctx *>(ctxp);
+  if (!ctx) return set_error(BZR_ERR_INVALID_ARGUMENT, "null context");
+  if (rounds > 64) return set_error(BZR_ERR_INVALID_ARGUMENT, "rounds must be at most 64");
+  ctx->far_rounds = rounds < 0 ? -1 : rounds;
+  return BZR_OK;
 }

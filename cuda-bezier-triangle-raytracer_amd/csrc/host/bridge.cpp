@@ -216,6 +216,39 @@ void traceChainAbsorb(std::vector<BezierLens const *> const &lenses, std::vector
   }
 }
 
+void farfieldBin(bzr_farfield const &far, Ray const *rays, float const *weights, RefractionResult const *status,
+                 uint8_t const *channels, std::size_t n, uint32_t nchan, uint64_t *farFlux, uint32_t *farHist,
+                 uint64_t *farStats, uint64_t *farPower, Context *ctx) {
+  if (nchan == 0 || nchan > BZR_MAX_CHANNELS) throw std::invalid_argument("nchan must be 1..BZR_MAX_CHANNELS");
+  // an empty batch needs no context: the frame and the maps are still checked
+  check(bzr_farfield_bin(nullptr, &far, nullptr, nullptr, nullptr, nullptr, 0, nchan, farFlux, farHist, nullptr, nullptr,
+                         BZR_HOST_PTRS));
+  std::vector<uint64_t> rows(4 * static_cast<std::size_t>(nchan), 0), part(rows.size());
+  for (std::size_t k = 0; n == 0 && k < 2 * static_cast<std::size_t>(nchan); ++k) {
+    if (farStats) farStats[k] = 0;
+    if (farPower) farPower[k] = 0;
+  }
+  if (n == 0) return;
+  Context &c = ctx ? *ctx : defaultContext();
+  std::lock_guard<std::mutex> hold(c.lock());
+  std::vector<float> soa;  // bzr_farfield_bin reads rows: the records' six words, transposed here
+  constexpr std::size_t kSlice = std::size_t(1) << 24;
+  for (std::size_t off = 0; off < n; off += kSlice) {
+    const std::size_t m = std::min(kSlice, n - off);
+    soa.resize(6 * m);
+    for (std::size_t i = 0; i < m; ++i)
+      for (std::size_t k = 0; k < 6; ++k) soa[k * m + i] = records(rays + off + i)[k];
+    check(bzr_farfield_bin(c.get(), &far, soa.data(), weights ? weights + off : nullptr, status ? words(status + off) : nullptr,
+                           channels ? channels + off : nullptr, static_cast<uint32_t>(m), nchan, farFlux, farHist,
+                           part.data(), part.data() + 2 * nchan, BZR_HOST_PTRS));
+    for (std::size_t k = 0; k < rows.size(); ++k) rows[k] += part[k];
+  }
+  for (std::size_t k = 0; k < 2 * static_cast<std::size_t>(nchan); ++k) {
+    if (farStats) farStats[k] = rows[k];
+    if (farPower) farPower[k] = rows[2 * nchan + k];
+  }
+}
+
 namespace {
 // The contexts' locks, taken in id order: two calls over shared contexts cannot deadlock (a repeated context is
 // locked once).

@@ -269,4 +269,99 @@ bzr_status bzr_absorption_from_transmittance(const double *internal_transmittanc
   return BZR_OK;
 }
 
+// ---- far field (include/bzr.h bzr_farfield) ----
+// The frame's checks and what every user derives from it, stated once: the pole n = axis_u x axis_v normalised as
+// illuminate() normalises the target's normal, S = R + R and the cell sizes.  out[13]: n, axis_u, axis_v, R, S, cu,
+// cv, as the device's FarFrame holds them (trace.hip calls this too).  Returns NULL, or why the frame is refused.
+const char *bzr_internal_farfield_frame(const bzr_farfield *far, uint32_t nchan, float out[13]) {
+  if (!far) return "null far-field frame";
+  if (!far->bins_u || !far->bins_v) return "far-field bins must be positive";
+  if (!std::isfinite(far->extent) || !(far->extent > 0.0f) || !(far->extent <= 1.41421354f))
+    return "far-field extent must be in (0, sqrt(2)]";
+  if (nchan == 0 || nchan > BZR_MAX_CHANNELS) return "nchan must be 1..64";
+  const uint64_t cells = (uint64_t)far->bins_u * far->bins_v;
+  if (cells >= (1ull << 32) || cells * nchan >= (1ull << 32)) return "far-field maps of 2^32 cells or more";
+  const float *au = far->axis_u, *av = far->axis_v;
+  float n[3] = {au[1] * av[2] - au[2] * av[1], au[2] * av[0] - au[0] * av[2], au[0] * av[1] - au[1] * av[0]};
+  const float z = n[0] * n[0] + (n[1] * n[1] + n[2] * n[2]);
+  if (z > 0.0f) {
+    const float s = std::sqrt(z);
+    for (float &c : n) c = c / s;
+  }
+  for (int k = 0; k < 3; ++k) out[k] = n[k], out[3 + k] = au[k], out[6 + k] = av[k];
+  const float S = far->extent + far->extent;
+  out[9] = far->extent;
+  out[10] = S;
+  out[11] = S / (float)far->bins_u;
+  out[12] = S / (float)far->bins_v;
+  return nullptr;
+}
+
+namespace {
+int64_t farfield_cell_host(const bzr_farfield &far, const float f[13], const float d[3]) {
+  const float mu = d[0] * f[0] + (d[1] * f[1] + d[2] * f[2]);
+  const float a = d[0] * f[3] + (d[1] * f[4] + d[2] * f[5]), b = d[0] * f[6] + (d[1] * f[7] + d[2] * f[8]);
+  const float g = 1.0f + mu;
+  const float h = 2.0f / g;
+  const float k = std::sqrt(h);
+  const float X = a * k, Y = b * k;
+  const float u = X + f[9], v = Y + f[9];
+  if (!(g > 0.0f && u >= 0.0f && u < f[10] && v >= 0.0f && v < f[10])) return -1;
+  uint32_t iu = (uint32_t)(u / f[11]), iv = (uint32_t)(v / f[12]);
+  if (iu >= far.bins_u) iu = far.bins_u - 1u;
+  if (iv >= far.bins_v) iv = far.bins_v - 1u;
+  return (int64_t)iv * far.bins_u + iu;
+}
+}  // namespace
+
+bzr_status bzr_farfield_cell(const bzr_farfield *far, const float d[3], int32_t *cell) {
+  float f[13];
+  if (const char *why = bzr_internal_farfield_frame(far, 1, f)) return bad(why);
+  if ((uint64_t)far->bins_u * far->bins_v >= (1ull << 31)) return bad("far-field map of 2^31 cells or more");
+  if (!d || !cell) return bad("null argument");
+  *cell = (int32_t)farfield_cell_host(*far, f, d);
+  return BZR_OK;
+}
+
+// include/bzr_debug.h: bzr_farfield_cell over n directions [n][3] at once
+int32_t bzr_debug_farfield_cells(const void *frame, const float *d_xyz, uint32_t n, int32_t *cell) {
+  const bzr_farfield *far = static_cast<const bzr_farfield *>(frame);
+  float f[13];
+  if (const char *why = bzr_internal_farfield_frame(far, 1, f)) return bad(why);
+  if ((uint64_t)far->bins_u * far->bins_v >= (1ull << 31)) return bad("far-field map of 2^31 cells or more");
+  if ((!d_xyz || !cell) && n) return bad("null argument");
+  for (uint32_t i = 0; i < n; ++i) cell[i] = (int32_t)farfield_cell_host(*far, f, d_xyz + (std::size_t)3 * i);
+  return BZR_OK;
+}
+
+bzr_status bzr_farfield_directions(const bzr_farfield *far, double *dir_xyz, double *polar_rad, double *azimuth_rad) {
+  float f[13];
+  if (const char *why = bzr_internal_farfield_frame(far, 1, f)) return bad(why);
+  const double R = far->extent;
+  for (uint32_t iv = 0; iv < far->bins_v; ++iv)
+    for (uint32_t iu = 0; iu < far->bins_u; ++iu) {
+      const std::size_t c = (std::size_t)iv * far->bins_u + iu;
+      const double X = -R + 2.0 * R * (iu + 0.5) / far->bins_u, Y = -R + 2.0 * R * (iv + 0.5) / far->bins_v;
+      const double rho2 = X * X + Y * Y, mu = 1.0 - rho2 / 2.0, w = std::sqrt(std::fmax(1.0 - rho2 / 4.0, 0.0));
+      const double a = X * w, b = Y * w;
+      if (dir_xyz)
+        for (int k = 0; k < 3; ++k) dir_xyz[3 * c + k] = a * f[3 + k] + b * f[6 + k] + mu * f[k];
+      if (polar_rad) polar_rad[c] = std::acos(std::fmin(std::fmax(mu, -1.0), 1.0));
+      if (azimuth_rad) azimuth_rad[c] = std::atan2(Y, X);
+    }
+  return BZR_OK;
+}
+
+bzr_status bzr_farfield_intensity(const bzr_farfield *far, const uint64_t *flux_q32, uint32_t nmaps, double scale,
+                                  double *out) {
+  float f[13];
+  if (const char *why = bzr_internal_farfield_frame(far, 1, f)) return bad(why);
+  if ((!flux_q32 || !out) && nmaps) return bad("null argument");
+  if (!std::isfinite(scale)) return bad("scale must be finite");
+  const double R = far->extent, omega = (2.0 * R / far->bins_u) * (2.0 * R / far->bins_v);
+  const std::size_t total = (std::size_t)far->bins_u * far->bins_v * nmaps;
+  for (std::size_t k = 0; k < total; ++k) out[k] = scale * (static_cast<double>(flux_q32[k]) / 4294967296.0) / omega;
+  return BZR_OK;
+}
+
 }  // extern "C"

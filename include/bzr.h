@@ -96,7 +96,8 @@ enum {
    * `Ray` of reference/3dGeomUtil.h:168, 24 bytes) instead of [6][n].  Host or device pointers alike; the library
    * transposes on the device (48 bytes per ray each way, HBM-bound), so a C++ caller hands its std::vector<Ray>
    * over with no host-side conversion.  Accepted by bzr_intersect (rays), bzr_refract, bzr_trace_chain,
-   * bzr_trace_chain_power, bzr_trace_tiled, bzr_tiled_set_rays (rays) and bzr_tiled_trace (out_rays); other calls reject it.  Other
+   * bzr_trace_chain_power, bzr_trace_tiled, bzr_tiled_set_rays (rays) and bzr_tiled_trace (out_rays); other calls reject it (the illumination calls and
+   * bzr_farfield_bin, which reads rows only, among them).  Other
    * arrays (hits, status, segments, expected) keep their layouts. */
   BZR_RAYS_AOS = 32u
 };
@@ -628,6 +629,80 @@ bzr_status bzr_illuminate_media(bzr_ctx *ctx, const bzr_mesh *const *lenses, con
                                 uint64_t *reflected_flux_q32, uint32_t *reflected_hist,
                                 uint64_t *stats, uint64_t *power_q32,
                                 uint64_t *ledger_count, uint64_t *ledger_power_q32, uint32_t flags);
+/* ---- far field: luminous intensity, power per steradian against direction ---- */
+/* A direction frame and its map.  axis_u and axis_v are unit and orthogonal, as bzr_target's; the pole is
+ * n = axis_u x axis_v, normalised on the host as the target's normal is.  Directions are mapped by the Lambert
+ * azimuthal equal-area projection about the pole, rho = 2 sin(theta / 2): equal areas in (X, Y) are equal solid
+ * angles.  The map is the square [-R, R)^2 with R = extent, 0 < R <= sqrt(2) as a float (bit pattern 0x3FB504F3 at
+ * the most), in bins_u x bins_v cells (row-major, u fastest).  Its corners reach rho = 2 at the most, so every cell
+ * is a whole cell of exactly (2R / bins_u)(2R / bins_v) steradians.  R = sqrt(2) holds the forward hemisphere in
+ * the inscribed disc and backward directions in the corners.
+ *
+ * The cell rule, defined by its operations so that the device, bzr_farfield_cell and a numpy restatement agree bit
+ * for bit: for a direction d (used as given, not normalised), in IEEE binary32 with one rounding per operation and
+ * no contraction -- under BZR_MODE_FAST too -- and dot products in the order x0 y0 + (x1 y1 + x2 y2):
+ *   mu = d . n    a = d . axis_u    b = d . axis_v
+ *   g = 1 + mu;   h = 2 / g;   k = sqrt(h)                 (division and root correctly rounded)
+ *   X = a k;   Y = b k;   u = X + R;   v = Y + R;   S = R + R
+ *   binned  iff  g > 0 && u >= 0 && u < S && v >= 0 && v < S      (a NaN anywhere fails; so does mu = -1)
+ *   cu = S / bins_u;   cv = S / bins_v                     (the bin counts converted to binary32)
+ *   iu = min((uint32) (u / cu), bins_u - 1);   iv likewise;   cell = iv * bins_u + iu
+ * A ray within rounding of a cell's or the map's edge may fall on either side of it. */
+typedef struct bzr_farfield {
+  float axis_u[3], axis_v[3];
+  float extent;
+  uint32_t bins_u, bins_v;
+} bzr_farfield;
+enum { BZR_FAR_SEEN = 0, BZR_FAR_BINNED = 1 };
+/* Bins a traced batch by direction.  rays_soa [6][n] as bzr_trace_chain_* writes out_rays (rows 3..5 are read).
+ * weight [n] (NULL: every ray 1.0f), status [n] (NULL: every ray is seen; otherwise only rays with status
+ * BZR_RR_OUTSIDE are), channel [n] (NULL: channel 0; a ray with channel >= nchan is skipped) live in host or device
+ * memory per `flags`, as the maps do.  far_flux_q32 and far_hist [nchan][bins_v][bins_u] accumulate (zero them
+ * first); at least one is given.  A binned ray of channel c adds q(w), bzr_illuminate_power's fixed point, to its
+ * cell of far_flux_q32[c] and one count to far_hist[c].  far_stats and far_power_q32 [nchan][2] (host memory
+ * always, each may be NULL, overwritten): per channel the count and the sum of q(w) of the rays seen (BZR_FAR_SEEN)
+ * and binned (BZR_FAR_BINNED).
+ * Returns BZR_ERR_INVALID_ARGUMENT before any output is touched for: a NULL far, zero bins, nchan x cells >= 2^32,
+ * an extent that is not finite or outside (0, sqrt(2)], nchan outside 1..BZR_MAX_CHANNELS, both maps NULL, unknown
+ * flags and BZR_RAYS_AOS.  n = 0 returns BZR_OK and touches nothing.  Both pipeline flags and BZR_MODE_FAST are
+ * accepted and change nothing.
+ * Host pointers: synchronous, staged through the context's scratch like bzr_emit.  BZR_DEVICE_PTRS: asynchronous on
+ * the context's stream, unless far_stats or far_power_q32 is given: the call then waits for them.
+ * Lanes of a wave that hold the same (channel, cell) are summed before the atomic; integer sums are order-free, so
+ * the maps' bits do not depend on it. */
+bzr_status bzr_farfield_bin(bzr_ctx *ctx, const bzr_farfield *far, const float *rays_soa, const float *weight,
+                            const uint32_t *status, const uint8_t *channel, uint32_t n, uint32_t nchan,
+                            uint64_t *far_flux_q32, uint32_t *far_hist,
+                            uint64_t *far_stats, uint64_t *far_power_q32, uint32_t flags);
+/* bzr_illuminate_media with a far-field frame: every traced ray that ends OUTSIDE is binned as bzr_farfield_bin bins
+ * it, with its final weight, into far_flux_q32 / far_hist [nchan][bins_v][bins_u] (at least one given; host or
+ * device memory per `flags` like flux_q32; accumulating).  A ray with at least one reflection is also added to
+ * far_reflected_flux_q32 (may be NULL): stray light and glare in angle.  far_stats and far_power_q32 [nchan][2]
+ * (host memory, each may be NULL, overwritten): per channel, [BZR_FAR_SEEN] equals stats / power_q32
+ * [c][BZR_ILLUM_EXITED].  target may be NULL: flux_q32, hist and the reflected maps must then be NULL, and the LANDED
+ * entries of stats, power_q32 and the ledger are 0.  With a target every bzr_illuminate_media output is that call's
+ * bit for bit.  The argument checks are bzr_illuminate_media's and bzr_farfield_bin's. */
+bzr_status bzr_illuminate_farfield(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                   const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                   uint32_t nlens, uint32_t nchan, const bzr_emitter *em, uint64_t total_rays,
+                                   const bzr_target *target, const bzr_radiometry *rad, uint32_t max_bounces,
+                                   uint64_t *flux_q32, uint32_t *hist,
+                                   uint64_t *reflected_flux_q32, uint32_t *reflected_hist,
+                                   uint64_t *stats, uint64_t *power_q32,
+                                   uint64_t *ledger_count, uint64_t *ledger_power_q32, uint32_t flags,
+                                   const bzr_farfield *far, uint64_t *far_flux_q32, uint32_t *far_hist,
+                                   uint64_t *far_reflected_flux_q32, uint64_t *far_stats, uint64_t *far_power_q32);
+/* Host helpers (no device).  bzr_farfield_cell: the cell rule above on the host, the device's twin: *cell is the
+ * cell of direction d, or -1 where d is not binned (maps of 2^31 cells or more are refused).
+ * bzr_farfield_directions: each cell centre in binary64, cell-major: dir_xyz [cells][3] the unit direction,
+ * polar_rad [cells] its angle from the pole, azimuth_rad [cells] = atan2(Y, X) (each may be NULL).  The inverse map:
+ * rho^2 = X^2 + Y^2, mu = 1 - rho^2 / 2, (a, b) = (X, Y) sqrt(1 - rho^2 / 4), d = a axis_u + b axis_v + mu n.
+ * bzr_farfield_intensity: out[m][cell] = scale x flux_q32[m][cell] / 2^32 / cell solid angle for nmaps maps: power
+ * per steradian; pass scale = 1 / emitted power for a normalised pattern. */
+bzr_status bzr_farfield_cell(const bzr_farfield *far, const float d[3], int32_t *cell);
+bzr_status bzr_farfield_directions(const bzr_farfield *far, double *dir_xyz, double *polar_rad, double *azimuth_rad);
+bzr_status bzr_farfield_intensity(const bzr_farfield *far, const uint64_t *flux_q32, uint32_t nmaps, double scale,
+                                  double *out);
 /* The bounding sphere bzr_illuminate culls with: center xyz, radius. */
 bzr_status bzr_mesh_bounding_sphere(const bzr_mesh *mesh, float out[4]);
 

@@ -494,6 +494,14 @@ void traceChainAbsorb(std::vector<BezierLens const *> const &lenses, std::vector
                       float const *opl, std::size_t n, uint32_t maxBounces, Ray *outRays, float *outWeights,
                       RefractionResult *outStatus, float *outOpl, float *outGlass = nullptr, uint32_t *outSegments = nullptr,
                       uint32_t *outBounces = nullptr, Context *ctx = nullptr);
+// Bins a traced batch by direction into a far-field map (bzr_farfield_bin): rays [n] as the traceChain* calls return
+// them (only the directions are read), weights, status and channels [n] each may be null (1.0f; every ray is seen,
+// otherwise only cOutside rays; channel 0).  farFlux / farHist [nchan][bins_v][bins_u] accumulate (one may be null);
+// farStats / farPower [nchan][2] (BZR_FAR_SEEN, BZR_FAR_BINNED; may be null) are overwritten.  Throws what the C call
+// refuses (std::runtime_error), before anything is touched.
+void farfieldBin(bzr_farfield const &far, Ray const *rays, float const *weights, RefractionResult const *status,
+                 uint8_t const *channels, std::size_t n, uint32_t nchan, uint64_t *farFlux, uint32_t *farHist,
+                 uint64_t *farStats = nullptr, uint64_t *farPower = nullptr, Context *ctx = nullptr);
 // The same chain over several devices from one process (bzr_trace_tiled): tiles of tileRays
 // consecutive rays dealt round-robin to `ctxs` (one per device, distinct), results in input order.
 void traceChainTiled(std::vector<Context *> const &ctxs, std::vector<BezierLens const *> const &lenses,

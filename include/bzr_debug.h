@@ -131,6 +131,14 @@ int32_t bzr_debug_fresnel(const float *eta, const float *cs, uint32_t n, float *
  * the text evaluates it (no device); otherwise ctx is a bzr_ctx* (bzr.h) and one small kernel on its device does,
  * synchronously.  The two agree bit for bit.  Returns 0 on success. */
 int32_t bzr_debug_attenuation(void *ctx, const float *x, uint32_t n, float *out);
+/* A/B hook of k_land_far's wave combine (bzr_farfield_bin, bzr_illuminate_farfield): the following calls on this
+ * context run at most `rounds` leader-election rounds per wave before the lanes left over issue their own atomics
+ * (0: plain per-lane atomics, 64: unbounded); a negative value restores the default.  The maps' bits do not depend
+ * on it.  ctx is a bzr_ctx* (bzr.h). */
+int32_t bzr_debug_farfield_rounds(void *ctx, int32_t rounds);
+/* bzr_farfield_cell (bzr.h) over n directions at once: far is a bzr_farfield*, d_xyz [n][3], cell [n] (-1: not
+ * binned).  No device.  Returns 0 on success. */
+int32_t bzr_debug_farfield_cells(const void *far, const float *d_xyz, uint32_t n, int32_t *cell);
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@
 on the cfg2 lens, emitter just behind it (inside the lens's bounding sphere, so nothing is culled and
 every ray is traced).  Prints one JSON line: emitted rays / s and the landed fraction.
 
-usage: bench_illum.py [total_rays] [--power] [--tir [max_bounces]] [--media]
+usage: bench_illum.py [total_rays] [--power] [--tir [max_bounces]] [--media] [--farfield]
 --power times bzr_illuminate_power (Lambert emitter, Fresnel surfaces: k_emit<true> -> chain with weights ->
 k_land<true>, 64-bit flux cells) beside bzr_illuminate on the same rays, alternating, and prints one more JSON line
 with both; the chain kernels' share comes from the context's event timing in a separate pass, the rest of a call is
@@ -16,7 +16,11 @@ plumbing (the per-batch row clear, k_land_tir's ledger) and of the bounce segmen
 --media prints one more JSON line: on the same wide emitter, bzr_illuminate_tir and bzr_illuminate_media (an encapsulant
 of index 1.41 / 1.333 / 1.2 / 1 in front of the lens, absorbing, and absorbing glass) at four reflections on the same
 emitted rays, alternating.  The media change which rays refract and reflect, so the ratio compares two workloads;
-whole-call times scatter by +- 15 % here."""
+whole-call times scatter by +- 15 % here.
+--farfield prints one more JSON line: on the same wide emitter and media, bzr_illuminate_media and
+bzr_illuminate_farfield (the same call plus a 256^2 far-field map at R = sqrt(2), axes the target's) on the same emitted rays, alternating, the far-field call without a target, and the far-field call with
+k_land_far's wave combine forced to 0, 4 and 64 rounds; the ratio is the cost of k_land_far per batch and of the far
+maps' staging."""
 import json
 import statistics
 import sys
@@ -32,8 +36,8 @@ from bzr_amd.configs import CONFIGS, build_lens  # noqa: E402
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--power", "--media")]
-    power, media = "--power" in sys.argv[1:], "--media" in sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a not in ("--power", "--media", "--farfield")]
+    power, media, farfield = "--power" in sys.argv[1:], "--media" in sys.argv[1:], "--farfield" in sys.argv[1:]
     tir = None
     if "--tir" in args:
         k = args.index("--tir")
@@ -57,6 +61,8 @@ def main():
         bench_tir(ctx, dm, tg, total, tir)
     if media:
         bench_media(ctx, dm, tg, total)
+    if farfield:
+        bench_farfield(ctx, dm, tg, total)
     if not power:
         return
 
@@ -180,6 +186,58 @@ def bench_media(ctx, dm, tg, total, max_bounces=4):
                       "landed_power_fraction": {k: round(sum(p["landed"] for p in v[1]) /
                                                          max(sum(p["emitted"] for p in v[1]), 1), 5)
                                                 for k, v in out.items()}}))
+
+
+def bench_farfield(ctx, dm, tg, total, max_bounces=4):
+    row1 = [1.3, 1.5, 1.8, 2.4]
+    gaps, glass, front = [[1.41, 1.333, 1.2, 1.0], [1.0] * 4], [[0.05, 0.7, 0.4, 200.0]], [[0.3, 0.02, 0.0, 0.1]]
+    em = bzr_amd.Emitter(origin=(8.0, -3.0, -1.5), edge_u=(0.0, 6.0, 0.0), edge_v=(0.0, 0.0, 3.0), parts_u=4, parts_v=4,
+                         points_per_part=1024, rays_per_point=1024, belts=16, seed=1)
+    far = bzr_amd.FarField(axis_u=(0.0, 1.0, 0.0), axis_v=(0.0, 0.0, 1.0), extent=bzr_amd.SQRT2, bins_u=256, bins_v=256)
+    calls = {"illuminate_media": lambda n: bzr_amd.illuminate_media(ctx, [dm], [row1], gaps, glass, front, em, n, tg,
+                                                                   max_bounces=max_bounces)[4:],
+             "illuminate_farfield": lambda n: bzr_amd.illuminate_farfield(ctx, [dm], [row1], gaps, glass, front, em, n, tg,
+                                                                         far, max_bounces=max_bounces)[4:],
+             "illuminate_farfield_no_target": lambda n: bzr_amd.illuminate_farfield(ctx, [dm], [row1], gaps, glass, front,
+                                                                                   em, n, None, far,
+                                                                                   max_bounces=max_bounces)[4:]}
+
+    def at_rounds(rounds):  # the far-field call with k_land_far's wave combine at `rounds` rounds (64: unbounded)
+        def call(n):
+            bzr_amd.debug_farfield_rounds(ctx, rounds)
+            try:
+                return calls["illuminate_farfield"](n)
+            finally:
+                bzr_amd.debug_farfield_rounds(ctx, -1)
+        return call
+
+    for rounds in (0, 4, 64):
+        calls[f"illuminate_farfield_rounds_{rounds}"] = at_rounds(rounds)
+    wall, out = {k: [] for k in calls}, {}
+    for call in calls.values():
+        call(1 << 20)  # warm-up
+    names = list(calls)
+    for r in range(6):  # alternating and rotated, as bench_tir
+        for name in names[r % len(names):] + names[:r % len(names)]:
+            t0 = time.perf_counter()
+            out[name] = calls[name](total)
+            wall[name].append(time.perf_counter() - t0)
+    med = {k: statistics.median(v) for k, v in wall.items()}
+    fo = out["illuminate_farfield"][3]
+    same = out["illuminate_media"][:2] == out["illuminate_farfield"][:2]
+    print(json.dumps({"workload": "illuminate_farfield beside illuminate_media, cfg2 lens, emitter at x=8 (no cull), "
+                                  "indices 1.3/1.5/1.8/2.4, 512^2 target, 256^2 far-field map",
+                      "rays": total, "max_bounces": max_bounces,
+                      "seconds": {k: round(v, 4) for k, v in med.items()},
+                      "seconds_min_max": {k: [round(min(v), 4), round(max(v), 4)] for k, v in wall.items()},
+                      "mrays_per_s": {k: round(total / v / 1e6, 1) for k, v in med.items()},
+                      "farfield_over_media": round(med["illuminate_farfield"] / med["illuminate_media"], 4),
+                      "no_target_over_media": round(med["illuminate_farfield_no_target"] / med["illuminate_media"], 4),
+                      "stats_and_power_same_as_media": bool(same),
+                      "seen": sum(s["seen"] for s in fo["stats"]), "binned": sum(s["binned"] for s in fo["stats"]),
+                      "exited": sum(s["exited"] for s in out["illuminate_farfield"][0]),
+                      "binned_power_fraction": round(sum(p["binned"] for p in fo["power"]) /
+                                                     max(sum(p["emitted"] for p in out["illuminate_farfield"][1]), 1), 5)}))
 
 
 if __name__ == "__main__":
