@@ -83,6 +83,9 @@ _SIGS = {
     "bzr_trace_chain_media": [_P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _U32],
     "bzr_trace_chain_absorb": [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P,
                                _U32],
+    "bzr_trace_chain_ghost": [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _U32, _U32, ctypes.c_uint64,
+                              ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _P, _U32],
+    "bzr_ghost_uniform": [ctypes.c_uint64, ctypes.c_uint64, _U32, _U32, _P],
     "bzr_absorption_from_transmittance": [_P, _U32, ctypes.c_double, _P],
     "bzr_dispersion_index": [_I32, _P, _U32, _P, _U32, _P],
     "bzr_trace_tiled": [_P, _U32, _P, _P, _U32, _P, _U32, _U32, _P, _P, _P, _U32],
@@ -108,6 +111,8 @@ _SIGS = {
     "bzr_farfield_bin": [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _U32],
     "bzr_illuminate_farfield": [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, ctypes.c_uint64, _P, _P, _U32, _P, _P, _P, _P, _P,
                                 _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P],
+    "bzr_illuminate_ghost": [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, ctypes.c_uint64, _P, _P, _U32, ctypes.c_uint64, _P,
+                             _P, _P, _P, _P, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P],
     "bzr_farfield_cell": [_P, _P, _P],
     "bzr_farfield_directions": [_P, _P, _P, _P],
     "bzr_farfield_intensity": [_P, _P, _U32, ctypes.c_double, _P],
@@ -151,7 +156,8 @@ _ADDED = ("bzr_trace_chain_power", "bzr_illuminate_power", "bzr_trace_chain_spec
           "bzr_dispersion_index", "bzr_trace_chain_tir", "bzr_illuminate_tir", "bzr_trace_chain_opl",
           "bzr_trace_chain_media", "bzr_trace_chain_absorb", "bzr_absorption_from_transmittance",
           "bzr_illuminate_media", "bzr_debug_attenuation", "bzr_farfield_bin", "bzr_illuminate_farfield",
-          "bzr_farfield_cell", "bzr_farfield_directions", "bzr_farfield_intensity", "bzr_debug_farfield_cells")
+          "bzr_farfield_cell", "bzr_farfield_directions", "bzr_farfield_intensity", "bzr_debug_farfield_cells",
+          "bzr_trace_chain_ghost", "bzr_ghost_uniform", "bzr_illuminate_ghost")
 _RET = {"bzr_last_error": ctypes.c_char_p, "bzr_abi_version": _I32}
 
 _lib = None
@@ -675,6 +681,54 @@ def trace_chain_absorb(ctx: Context, lenses, ri_table, gap_table, glass_absorb, 
     return out_rays, out_weight, out_status, out_segments, out_bounces, out_opl, out_glass
 
 
+def trace_chain_ghost(ctx: Context, lenses, ri_table, gap_table, glass_absorb, gap_absorb, rays, channel=None, weight=None,
+                      opl=None, max_bounces=4, ghost_seed=0, first_ray=0, out_rays=None, out_weight=None, out_status=None,
+                      out_segments=None, out_bounces=None, out_opl=None, out_glass=None, mode=MODE_PARITY):
+    """trace_chain_absorb with the Fresnel roulette at glass exits -> the same seven-tuple.  A ray that would refract
+    out of a lens with bounce budget left draws u = ghost_uniform(ghost_seed, first_ray + i, lens, reflections so far):
+    u >= T reflects it like a total reflection, u < T lets it out without the factor T.  The draws depend on the ray's
+    64-bit number alone, so a call split in two (first_ray moved along) gives the same bits; max_bounces = 0 is
+    trace_chain_absorb bit for bit (bzr.h bzr_trace_chain_ghost)."""
+    n = _n_of(rays, mode)
+    nl = len(lenses)
+    handles = (_P * nl)(*[m.handle for m in lenses])
+    table, nchan = _ri_table(ri_table, nl)
+    gap = _gap_table(gap_table, nl, nchan)
+    ga, pa = _absorb_table(glass_absorb, "glass_absorb", nl, nchan), _absorb_table(gap_absorb, "gap_absorb", nl, nchan)
+    out_rays = _empty_like(rays, 6, np.float32, mode) if out_rays is None else out_rays
+    out_weight = _empty_like(rays, 0, np.float32, mode) if out_weight is None else out_weight
+    out_status = _empty_like(rays, 0, np.uint32, mode) if out_status is None else out_status
+    out_segments = _empty_like(rays, 0, np.uint32, mode) if out_segments is None else out_segments
+    out_bounces = _empty_like(rays, 0, np.uint32, mode) if out_bounces is None else out_bounces
+    out_opl = _empty_like(rays, 0, np.float32, mode) if out_opl is None else out_opl
+    if out_glass is False:
+        out_glass = None
+    elif out_glass is None:
+        out_glass = _empty_like(rays, 0, np.float32, mode)
+    r, c, wi, pi = _Buf(rays, np.float32), _Buf(channel, np.uint8), _Buf(weight, np.float32), _Buf(opl, np.float32)
+    o, w = _Buf(out_rays, np.float32, True), _Buf(out_weight, np.float32, True)
+    s, g, b = _Buf(out_status, np.uint32, True), _Buf(out_segments, np.uint32, True), _Buf(out_bounces, np.uint32, True)
+    p, q = _Buf(out_opl, np.float32, True), _Buf(out_glass, np.float32, True)
+    res = _residency(r, c, o, w, s, g, b, wi, pi, p, q)
+    mask = (1 << 64) - 1
+    with _stream_for(ctx, res):
+        _check(lib().bzr_trace_chain_ghost(ctx.handle, ctypes.cast(handles, _P), table.ctypes.data if table.size else None,
+                                           _table_ptr(gap), _table_ptr(ga), _table_ptr(pa), nl, nchan, r.ptr, c.ptr,
+                                           wi.ptr, pi.ptr, n, int(max_bounces), int(ghost_seed) & mask,
+                                           int(first_ray) & mask, o.ptr, w.ptr, s.ptr, g.ptr, b.ptr, p.ptr, q.ptr,
+                                           res | mode))
+    return out_rays, out_weight, out_status, out_segments, out_bounces, out_opl, out_glass
+
+
+def ghost_uniform(seed: int, ray: int, lens: int, reflections: int) -> np.float32:
+    """The roulette's draw on the host, the device's twin: a 24-bit uniform in [0, 1) for (seed, the ray's 64-bit
+    number, lens 0..7, reflections in that lens so far 0..8) (bzr.h bzr_ghost_uniform)."""
+    u = ctypes.c_float()
+    mask = (1 << 64) - 1
+    _check(lib().bzr_ghost_uniform(int(seed) & mask, int(ray) & mask, int(lens), int(reflections), ctypes.byref(u)))
+    return np.float32(u.value)
+
+
 def absorption_from_transmittance(internal_transmittance, thickness: float) -> np.ndarray:
     """Absorption coefficients a = -ln(T) / thickness, float32, from a catalogue's internal transmittance T at a
     thickness, per unit of the length the thickness is given in.  Host only (bzr.h bzr_absorption_from_transmittance)."""
@@ -1006,9 +1060,10 @@ def illuminate_media(ctx: Context, lenses, ri_table, gap_table, glass_absorb, ga
 
 
 def _illuminate_reflecting(ctx, lenses, ri_table, media, em, total_rays, target, max_bounces, emission, surface, flux, hist,
-                           reflected_flux, reflected_hist, mode, far=None):
+                           reflected_flux, reflected_hist, mode, far=None, ghost_seed=None):
     """illuminate_tir (media None), illuminate_media (media = the gap table and the two absorption tables) or
-    illuminate_farfield (far = the frame and its three maps, each map or None; target may then be None)."""
+    illuminate_farfield (far = the frame and its three maps, each map or None; target may then be None);
+    illuminate_ghost: ghost_seed given, media given, far or None."""
     nl = len(lenses)
     handles = (_P * nl)(*[m.handle for m in lenses])
     table, nchan = _ri_table(ri_table, nl)
@@ -1054,7 +1109,12 @@ def _illuminate_reflecting(ctx, lenses, ri_table, media, em, total_rays, target,
             ctypes.byref(rad), int(max_bounces), f.ptr,
             h.ptr, rf.ptr, rh.ptr, stats, power, ledger["count"].ctypes.data, ledger["power"].ctypes.data, res | mode)
     with _stream_for(ctx, res):
-        if far is not None:
+        if ghost_seed is not None:
+            far_args = (ctypes.byref(frame), ff.ptr, fh.ptr, frf.ptr, fstats, fpower) if far is not None else (None,) * 6
+            _check(lib().bzr_illuminate_ghost(ctx.handle, handles, table.ctypes.data if table.size else None,
+                                              *[_table_ptr(a) for a in media], *tail[:7],
+                                              int(ghost_seed) & ((1 << 64) - 1), *tail[7:], *far_args))
+        elif far is not None:
             _check(lib().bzr_illuminate_farfield(ctx.handle, handles, table.ctypes.data if table.size else None,
                                                  *[_table_ptr(a) for a in media], *tail, ctypes.byref(frame), ff.ptr,
                                                  fh.ptr, frf.ptr, fstats, fpower))
@@ -1141,6 +1201,30 @@ def illuminate_farfield(ctx: Context, lenses, ri_table, gap_table, glass_absorb,
     return _illuminate_reflecting(ctx, lenses, ri_table, media, em, total_rays, target, max_bounces, emission, surface,
                                   flux, hist, reflected_flux, reflected_hist, mode,
                                   far=(far, far_flux, far_hist, far_reflected_flux))
+
+
+def illuminate_ghost(ctx: Context, lenses, ri_table, gap_table, glass_absorb, gap_absorb, em: Emitter, total_rays: int,
+                     target, far=None, max_bounces=4, ghost_seed=0, emission=EMISSION_LAMBERT, surface=SURFACE_FRESNEL,
+                     flux=None, hist=None, reflected_flux=None, reflected_hist=None, far_flux=None, far_hist=None,
+                     far_reflected_flux=None, mode=MODE_PARITY):
+    """illuminate_farfield over trace_chain_ghost's chain: emitter ray j draws with ray number j, whatever the batching.
+    Returns illuminate_farfield's eight-tuple, or with far None illuminate_media's seven-tuple; one of target and far is
+    given.  Ghost rays arrive in the reflected maps and in ledger rows >= 1.  With SURFACE_LOSSLESS or max_bounces 0
+    every output is illuminate_farfield's bit for bit (bzr.h bzr_illuminate_ghost)."""
+    nl = len(lenses)
+    _, nchan = _ri_table(ri_table, nl)
+    media = (_gap_table(gap_table, nl, nchan), _absorb_table(glass_absorb, "glass_absorb", nl, nchan),
+             _absorb_table(gap_absorb, "gap_absorb", nl, nchan))
+    if target is None and far is None:
+        raise BzrError("neither a target nor a far-field frame")
+    if target is None and any(a is not None for a in (flux, hist, reflected_flux, reflected_hist)):
+        raise BzrError("target maps given without a target")
+    if far is None and any(a is not None for a in (far_flux, far_hist, far_reflected_flux)):
+        raise BzrError("far maps given without a far-field frame")
+    return _illuminate_reflecting(ctx, lenses, ri_table, media, em, total_rays, target, max_bounces, emission, surface,
+                                  flux, hist, reflected_flux, reflected_hist, mode,
+                                  far=None if far is None else (far, far_flux, far_hist, far_reflected_flux),
+                                  ghost_seed=ghost_seed)
 
 
 def farfield_cell(far: FarField, directions) -> np.ndarray:
@@ -1331,6 +1415,6 @@ class TriMesh:
 __all__ = [
     "BzrError", "Context", "DeviceMesh", "TriMesh", "intersect", "patch_intersect", "refract", "trace_chain", "interpolate",
     "Emitter", "Target", "emit", "illuminate", "bounding_sphere",
-    "FarField", "farfield_bin", "illuminate_farfield", "farfield_cell", "farfield_directions", "farfield_intensity",
+    "FarField", "farfield_bin", "illuminate_farfield", "trace_chain_ghost", "ghost_uniform", "illuminate_ghost", "farfield_cell", "farfield_directions", "farfield_intensity",
     "device_count", "lib", "exported_symbols", "LIB_PATH",
 ]

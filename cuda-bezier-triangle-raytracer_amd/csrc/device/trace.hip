@@ -383,6 +383,43 @@ __device__ __forceinline__ uint32_t tir_eta_t(const Hit &h, float eta, f3 s, f3 
   }
   return refract_eta_t<kGain>(h, eta, s, d, expected, o_s, o_d, gain);
 }
+// The Fresnel roulette's uniform (kModeGhost; include/bzr.h bzr_trace_chain_ghost): a 24-bit uniform in [0, 1) for
+// ray number j = first_ray + i and draw e = 16 lens + reflections so far in that lens, off the emitter's uniform2
+// stream by the xor.  The host folds everything of the first hash's argument that the call fixes into one word,
+// base = (seed ^ 0x5851F42D4C957F2D) + golden (first_ray + 1) (ghost_base), so that mod 2^64 the argument
+// (seed ^ ...) + golden (j + 1) is base + golden i: one 64-bit kernel argument, one 64 x 32 product per lane.
+constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
+inline uint64_t ghost_base(uint64_t seed, uint64_t first_ray) {
+  return (seed ^ 0x5851F42D4C957F2Dull) + kGolden * (first_ray + 1ull);
+}
+__device__ __forceinline__ float ghost_uniform(uint64_t base, uint32_t i, uint32_t e) {
+  const uint64_t r = mix64(base + kGolden * (uint64_t)i);
+  const uint64_t h = mix64(r + kGolden * ((uint64_t)e + 1ull));
+  return (float)(uint32_t)(h >> 40) * 0x1p-24f;
+}
+// tir_eta_t with the roulette (kModeGhost).  A hit that tir_eta_t would test for total reflection -- expected OUTSIDE,
+// `may_reflect`, an intersection with cs >= 0 -- and that Snell's step would refract (s2 < 0.99) draws when `may_draw`
+// (u: the lane's uniform for this segment, made by the caller):
+// u >= T mirrors the ray exactly as a total reflection does (kReflected); u < T refracts it with gain 1, the roulette
+// having taken the 1 - T share.  Everything else is tir_eta_t.  (A sibling: the older instantiations keep their code.)
+template <bool kGain>
+__device__ __forceinline__ uint32_t ghost_eta_t(const Hit &h, float eta, f3 s, f3 d, uint32_t expected, bool may_reflect,
+                                                bool may_draw, float u, f3 &o_s, f3 &o_d, float &gain) {
+  const float s2 = eta * eta * (1.0f - h.cs * h.cs);
+  const bool leaving = expected == BZR_RR_OUTSIDE && may_reflect && h.what == kIntersect && h.cs >= 0.0f;
+  const bool drawn = leaving && may_draw && s2 < 0.99f;
+  bool mirror = leaving && s2 >= 1.0f;
+  if (drawn) mirror = u >= fresnel_t(eta, h.cs, s2);
+  if (mirror) {
+    const float k = 2.0f * h.cs;
+    o_d = normalized(sub(d, scale(h.normal, k)));
+    o_s = h.point;
+    return kReflected;
+  }
+  const uint32_t st = refract_eta_t<kGain>(h, eta, s, d, expected, o_s, o_d, gain);
+  if (drawn) gain = 1.0f;
+  return st;
+}
 // The segment's eta: one correctly rounded division, n0 / n1 going in, n1 / n2 coming out (bounce segments included).
 __device__ __forceinline__ float media_eta(float n0, float n1, float n2, bool outside) {
   return div_rn(outside ? n1 : n0, outside ? n2 : n1);
@@ -574,11 +611,18 @@ constexpr uint32_t kGapPart = (kMaxLenses + 1u) * BZR_MAX_CHANNELS, kAbsorbPart 
 // multiplies the weight by att(a len) (leg_attenuation), a = gap_absorb[l][channel[i]] in front of lens l and
 // glass_absorb[l][channel[i]] inside it, ahead of the Fresnel gain; a reflection now touches the weight.  A mode of its
 // own again: the other eight compile to the code they had.
+// kModeGhost: kModeAbsorb with the Fresnel roulette at glass exits (ghost_eta_t) -- a ray that would refract out of a
+// lens with bounce budget left reflects with probability 1 - T and otherwise leaves without the T factor; the ray's
+// 64-bit number is first_ray + its index in the call.  A mode of its own again: the other nine compile to the code they
+// had.  Its one job word, ghost_base, shares kModeHits' `hits` slot of TraceJob: with a field of its own behind gap_table
+// the non-counting k_trace<kModeGhost> came out with 36 and 68 B of scratch reserved (never accessed), kModeAbsorb's
+// artefact again, and every k_trace of the parent with another kernarg size (DESIGN (a)).
 enum OutMode {
   kModeHits = 0, kModeRefract = 1, kModeStage = 2, kModePower = 3, kModeSpectral = 4, kModeTir = 5, kModeOpl = 6,
-  kModeMedia = 7, kModeAbsorb = 8
+  kModeMedia = 7, kModeAbsorb = 8, kModeGhost = 9
 };
-constexpr bool has_absorb(int mode) { return mode == kModeAbsorb; }
+constexpr bool has_ghost(int mode) { return mode == kModeGhost; }
+constexpr bool has_absorb(int mode) { return mode == kModeAbsorb || has_ghost(mode); }
 constexpr bool has_media(int mode) { return mode == kModeMedia || has_absorb(mode); }
 constexpr bool has_opl(int mode) { return mode == kModeOpl || has_media(mode); }
 constexpr bool is_stage(int mode) {
@@ -621,6 +665,10 @@ struct Out {
   const float *gap_row, *gap_next;
   // kModeAbsorb: this lens's rows of the two absorption tables [nchan] (device memory): its glass, the medium in front
   const float *glass_absorb, *gap_absorb;
+  // kModeGhost: the roulette's base word for index 0 of these rows (ghost_base: ray gi draws with base + golden gi) and
+  // this stage's draw number e = 16 lens + reflections so far in it (an OUTSIDE stage that may reflect)
+  uint64_t ghost_base;
+  uint32_t ghost_e;
 };
 
 template <int kMode>
@@ -645,6 +693,12 @@ __device__ __forceinline__ void emit(const Out &o, uint32_t ld, uint32_t gi, f3 
       const bool outside = o.expected_all == BZR_RR_OUTSIDE;
       const float n0 = o.gap_row[col];
       if (!outside) nm = n0;
+      if constexpr (has_ghost(kMode)) {
+        const bool draws = outside && o.may_reflect && !o.lossless;  // (stage-uniform)
+        const float u = draws ? ghost_uniform(o.ghost_base, gi, o.ghost_e) : 0.0f;
+        st = ghost_eta_t<true>(h, media_eta(n0, ri, o.gap_next[col], outside), s, d, o.expected_all,
+                               in_table && o.may_reflect, draws, u, os, od, gain);
+      } else
       st = tir_eta_t<true>(h, media_eta(n0, ri, o.gap_next[col], outside), s, d, o.expected_all, in_table && o.may_reflect,
                            os, od, gain);
     } else if constexpr (has_tir(kMode))
@@ -1976,6 +2030,8 @@ template <>
 struct TraceKeep<kModeMedia> : TraceKeep<kModeOpl> {};  // kModeMedia keeps what kModeOpl keeps: no new word per lane
 template <>
 struct TraceKeep<kModeAbsorb> : TraceKeep<kModeMedia> {};  // and so does kModeAbsorb
+template <>
+struct TraceKeep<kModeGhost> : TraceKeep<kModeAbsorb> {};  // and kModeGhost: the draw is recomputed, nothing waits
 // The bundle walk's set of leaf slots already queued in this wave-segment (bundle_batch `seen`), one bit per
 // slot: the refract and chain kernels walk the trees with split leaf boxes (MeshView swide).  The intersect
 // kernel's 6.7 KB per wave leave no room for it (24 waves x 7.7 KB > 160 KB), and the power, spectral and TIR
@@ -2453,7 +2509,10 @@ __device__ __forceinline__ void trace_segment(const MeshView &m, f3 s, f3 d, boo
 // with each lens's index taken per ray from ri_table by the ray's channel).
 struct TraceJob {
   const float *rays;         // input [6][n]
-  float *hits;               // kModeHits [13][n]
+  union {                    // (one word, two modes that never meet: TraceJob keeps its size, see kModeGhost above)
+    float *hits;             // kModeHits [13][n]
+    uint64_t ghost_base;     // kModeGhost: the roulette's base word for ray 0 of the job (ghost_base())
+  };
   float *out_rays;           // kModeRefract / kModeStage [6][n] (may alias rays in kModeStage)
   uint32_t *status;          // kModeRefract / kModeStage [n]
   uint32_t *segments;        // kModeStage, optional [n]
@@ -2620,6 +2679,18 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
         if (l == 0u && b == 0u && i < n && job.weight_in) L.weight[lane] = job.weight_in[i];
         if constexpr (has_opl(kMode))
           if (l == 0u && b == 0u && i < n && job.opl_in) L.opl[lane] = job.opl_in[i];
+        // kModeGhost: the lane's uniform for this segment, both hashes made here from the job's base word, behind the
+        // segment's passes and ahead of the winner's words (e is wave-uniform; nothing of the roulette lives across a walk)
+        bool draws = false;
+        float u = 0.0f;
+        if constexpr (has_ghost(kMode)) {
+          draws = b != 0u && b <= job.max_bounces && !job.lossless;
+          // (the ray's index is put together again from the wave's tile: its product with the golden ratio, two
+          // registers, would otherwise be hoisted out of both loops and live across every walk)
+          if (draws)
+            u = ghost_uniform(job.ghost_base, (uint32_t)__builtin_amdgcn_readfirstlane(tile * kTraceBlock) + threadIdx.x,
+                              16u * l + b - 1u);
+        }
         Hit h = no_hit();
         uint32_t patch = 0xFFFFFFFFu;
         if (best != ~0ull) h = winner(L, lane, patch);
@@ -2635,6 +2706,11 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
           const uint32_t c = l * job.nchan + (in_table ? ch : 0u);
           const float n0 = job.gap_table[c];
           if (b == 0u) nm = n0;
+          if constexpr (has_ghost(kMode))
+            r = ghost_eta_t<true>(h, media_eta(n0, ri, job.gap_table[c + job.nchan], b != 0u), s, d,
+                                  b == 0u ? uint32_t(BZR_RR_INSIDE) : uint32_t(BZR_RR_OUTSIDE),
+                                  in_table && b <= job.max_bounces, draws, u, os, od, gain);
+          else
           r = tir_eta_t<true>(h, media_eta(n0, ri, job.gap_table[c + job.nchan], b != 0u), s, d,
                               b == 0u ? uint32_t(BZR_RR_INSIDE) : uint32_t(BZR_RR_OUTSIDE),
                               in_table && b <= job.max_bounces, os, od, gain);
@@ -2820,7 +2896,8 @@ __global__ __launch_bounds__(kBlock) void k_refract_scan(MeshView m, const float
 // is optional.  kScan 4: kModeOpl's form -- kScan 3 with the optical path and the glass path (opl_leg); opl_in may be
 // null (0) and may alias out_opl, out_glass is optional.  kScan 5: kModeMedia's form -- kScan 4 with gap_table [count +
 // 1][nchan] (tir_eta_t, opl_leg_media).  kScan 6: kModeAbsorb's form -- kScan 5 with the two absorption tables
-// [count][nchan] (leg_attenuation).  (An int, not an enum: instantiations 0 to 3 keep their names.)
+// [count][nchan] (leg_attenuation).  kScan 7: kModeGhost's form -- kScan 6 with the roulette (ghost_eta_t) for ray number
+// first_ray + i (ghost_at: ghost_base for ray 0).  (An int, not an enum: instantiations 0 to 3 keep their names.)
 template <int kScan>
 __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const float *__restrict__ rays, uint32_t n,
                                                        float *__restrict__ out_rays, uint32_t *__restrict__ out_status,
@@ -2831,9 +2908,9 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
                                                        const float *opl_in, float *out_opl, float *out_glass,
                                                        const float *__restrict__ gap_table,
                                                        const float *__restrict__ glass_absorb,
-                                                       const float *__restrict__ gap_absorb) {
+                                                       const float *__restrict__ gap_absorb, uint64_t ghost_at) {
   constexpr bool kPower = kScan != 0, kSpectral = kScan >= 2, kTir = kScan >= 3, kOpl = kScan >= 4, kMedia = kScan >= 5;
-  constexpr bool kAbsorb = kScan == 6;
+  constexpr bool kAbsorb = kScan >= 6, kGhost = kScan == 7;
   uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   f3 s, d;
@@ -2865,6 +2942,11 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
       if constexpr (kMedia) {
         const float n0 = gap_table[l * nchan + ch];
         if (j == 0u) nm = n0;
+        if constexpr (kGhost)
+          st = ghost_eta_t<true>(h, media_eta(n0, ri, gap_table[(l + 1u) * nchan + ch], j != 0u), s, d,
+                                 j == 0 ? BZR_RR_INSIDE : BZR_RR_OUTSIDE, in_table && j <= max_bounces, j != 0u,
+                                 j != 0u ? ghost_uniform(ghost_at, i, 16u * l + j - 1u) : 0.0f, os, od, gain);
+        else
         st = tir_eta_t<true>(h, media_eta(n0, ri, gap_table[(l + 1u) * nchan + ch], j != 0u), s, d,
                              j == 0 ? BZR_RR_INSIDE : BZR_RR_OUTSIDE, in_table && j <= max_bounces, os, od, gain);
       } else if constexpr (kTir)
@@ -3436,6 +3518,10 @@ bzr_status run_chain(bzr_ctx *ctx, const LensSet &set, const TraceJob &job, uint
           o.glass_absorb = job.gap_table + kGapPart + (size_t)l * job.nchan;
           o.gap_absorb = o.glass_absorb + kAbsorbPart;
         }
+        if constexpr (has_ghost(kMode)) {
+          o.ghost_base = job.ghost_base;
+          o.ghost_e = 16u * l + j - 1u;  // (read by an OUTSIDE stage that may reflect: j >= 1)
+        }
         if (bzr_status s = run_segment<kMode>(use_fast(flags), ctx, set.lens[l], o.first ? job.rays : job.out_rays, job.ld,
                                               off, m, o.first ? nullptr : (o.bounce_stage ? pend : job.status), o, w))
           return s;
@@ -3985,6 +4071,7 @@ extern "C" bzr_status bzr_refract(bzr_ctx *ctx, const bzr_mesh *mesh, float ri, 
 // bzr_trace_chain_media (kModeMedia: kModeOpl + `gap`, the media table [nlens + 1][nchan] in host memory, null: vacuum).
 // bzr_trace_chain_absorb (kModeAbsorb: kModeMedia + `glass_abs` and `gap_abs`, the absorption tables [nlens][nchan] in
 // host memory, null: all zero).
+// bzr_trace_chain_ghost (kModeGhost: kModeAbsorb + `ghost_seed` and `first_ray`, the roulette's seed and ray 0's number).
 template <int kMode>
 static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
                               const float *rays, const float *weight_in, uint32_t n, float *out_rays, float *out_weight,
@@ -3992,7 +4079,7 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
                               const uint8_t *channel = nullptr, uint32_t nchan = 0, uint32_t max_bounces = 0,
                               uint32_t *out_bounces = nullptr, const float *opl_in = nullptr, float *out_opl = nullptr,
                               float *out_glass = nullptr, const float *gap = nullptr, const float *glass_abs = nullptr,
-                              const float *gap_abs = nullptr) {
+                              const float *gap_abs = nullptr, uint64_t ghost_seed = 0, uint64_t first_ray = 0) {
   constexpr bool kPower = has_power(kMode), kSpectral = has_channels(kMode), kTir = has_tir(kMode);
   constexpr bool kOpl = has_opl(kMode), kMedia = has_media(kMode), kAbsorb = has_absorb(kMode);
   if (bzr_status s = check_flags(flags, true)) return s;
@@ -4067,11 +4154,11 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
   }
   if (use_scan(flags)) {
     launch(ctx, BZR_KERNEL_CHAIN_SCAN,
-           k_chain_scan<kAbsorb ? 6 : kMedia ? 5 : kOpl ? 4 : (kTir ? 3 : (kSpectral ? 2 : (kPower ? 1 : 0)))>,
+           k_chain_scan<has_ghost(kMode) ? 7 : kAbsorb ? 6 : kMedia ? 5 : kOpl ? 4 : (kTir ? 3 : (kSpectral ? 2 : (kPower ? 1 : 0)))>,
            dim3(grid_for(n)), set, d_rays, n, d_out, d_st, d_seg, d_win, d_w, d_ch, (const float *)ctx->ri_table, nchan, d_bnc,
            max_bounces, d_oin, d_opl, d_glass, kMedia ? (const float *)ctx->ri_table + kRiTableFloats : nullptr,
            kAbsorb ? (const float *)ctx->ri_table + kGlassAbsorbAt : nullptr,
-           kAbsorb ? (const float *)ctx->ri_table + kGapAbsorbAt : nullptr);
+           kAbsorb ? (const float *)ctx->ri_table + kGapAbsorbAt : nullptr, ghost_base(ghost_seed, first_ray));
     BZR_HIP(hipGetLastError());
   } else {
     TraceJob job{};
@@ -4091,6 +4178,7 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     job.opl_in = d_oin;
     job.glass = d_glass;
     job.gap_table = kMedia ? ctx->ri_table + kRiTableFloats : nullptr;
+    job.ghost_base = ghost_base(ghost_seed, first_ray);
     Work w;
     const uint32_t ch = staged ? chunk_for(ctx, n) : 0u;
     if (staged)
@@ -4187,6 +4275,26 @@ extern "C" bzr_status bzr_trace_chain_absorb(bzr_ctx *ctx, const bzr_mesh *const
   return trace_chain<kModeAbsorb>(ctx, lenses, ri_table, nlens, rays, weight_in, n, out_rays, out_weight, out_status,
                                   out_segments, flags, channel, nchan, max_bounces, out_bounces, opl_in, out_opl, out_glass,
                                   gap_table, glass_absorb, gap_absorb);
+}
+
+extern "C" bzr_status bzr_trace_chain_ghost(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                            const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                            uint32_t nlens, uint32_t nchan, const float *rays, const uint8_t *channel,
+                                            const float *weight_in, const float *opl_in, uint32_t n,
+                                            uint32_t max_bounces, uint64_t ghost_seed, uint64_t first_ray,
+                                            float *out_rays, float *out_weight, uint32_t *out_status,
+                                            uint32_t *out_segments, uint32_t *out_bounces, float *out_opl,
+                                            float *out_glass, uint32_t flags) {
+  // (bzr_trace_chain_absorb's checks, in its order)
+  if (!out_opl) return set_error(BZR_ERR_INVALID_ARGUMENT, "null out_opl");
+  if (max_bounces > BZR_MAX_BOUNCES) return set_error(BZR_ERR_INVALID_ARGUMENT, "max_bounces must be 0..8");
+  if (nlens >= 1 && nlens <= kMaxLenses && nchan >= 1 && nchan <= kMaxChannels) {
+    if (bzr_status s = check_absorb_table(glass_absorb, nlens, nchan, "glass_absorb entries must be finite and >= 0")) return s;
+    if (bzr_status s = check_absorb_table(gap_absorb, nlens, nchan, "gap_absorb entries must be finite and >= 0")) return s;
+  }
+  return trace_chain<kModeGhost>(ctx, lenses, ri_table, nlens, rays, weight_in, n, out_rays, out_weight, out_status,
+                                 out_segments, flags, channel, nchan, max_bounces, out_bounces, opl_in, out_opl, out_glass,
+                                 gap_table, glass_absorb, gap_absorb, ghost_seed, first_ray);
 }
 
 // ------------------------------------------------------------ test hook: normalized()
@@ -4887,6 +4995,9 @@ struct IllumTir {
   bool media = false;
   const float *gap = nullptr, *glass_absorb = nullptr, *gap_absorb = nullptr;
   const IllumFar *far = nullptr;  // bzr_illuminate_farfield
+  // bzr_illuminate_ghost: the chain is kModeGhost's; ray j of the emitter draws for ray number j
+  bool ghost = false;
+  uint64_t ghost_seed = 0;
 };
 static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
                              const bzr_emitter *em, uint64_t total_rays, const bzr_target *tg, const bzr_radiometry *rad,
@@ -5043,7 +5154,8 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   const uint32_t lambert = with_power && rad->emission == BZR_EMISSION_LAMBERT ? 1u : 0u;
   // the mode, chosen once: the chain's (a lossless surface leaves the weights as emitted: the plain chain; the
   // spectral chain refracts per channel with a lossless surface too: its run-time flag) and the two kernels'
-  auto *const chain = media      ? &run_chain<kModeAbsorb>
+  auto *const chain = (tir && tir->ghost) ? &run_chain<kModeGhost>
+                      : media    ? &run_chain<kModeAbsorb>
                       : tir      ? &run_chain<kModeTir>
                       : spectral ? &run_chain<kModeSpectral>
                       : fresnel  ? &run_chain<kModePower>
@@ -5072,6 +5184,9 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
     if (media) {
       job.opl = d_opl;
       job.gap_table = ctx->ri_table + kRiTableFloats;
+    }
+    if (tir && tir->ghost) {
+      job.ghost_base = ghost_base(tir->ghost_seed, first);
     }
     if (bzr_status s = chain(ctx, set, job, flags, staged, d_pend, B, w)) return s;
     if (tir)
@@ -5214,6 +5329,38 @@ extern "C" bzr_status bzr_illuminate_farfield(bzr_ctx *ctx, const bzr_mesh *cons
   tir.glass_absorb = glass_absorb;
   tir.gap_absorb = gap_absorb;
   tir.far = &ifar;
+  return illuminate(ctx, lenses, ri_table, nlens, em, total_rays, tg, rad, flux_q32, hist, stats, power_q32, flags, true,
+                    nchan, &tir);
+}
+
+// bzr_illuminate_farfield with the roulette chain; `far` may be null (bzr_illuminate_media's outputs alone).
+extern "C" bzr_status bzr_illuminate_ghost(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                           const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                           uint32_t nlens, uint32_t nchan, const bzr_emitter *em, uint64_t total_rays,
+                                           const bzr_target *tg, const bzr_radiometry *rad, uint32_t max_bounces,
+                                           uint64_t ghost_seed, uint64_t *flux_q32, uint32_t *hist,
+                                           uint64_t *reflected_flux_q32, uint32_t *reflected_hist, uint64_t *stats,
+                                           uint64_t *power_q32, uint64_t *ledger_count, uint64_t *ledger_power_q32,
+                                           uint32_t flags, const bzr_farfield *far, uint64_t *far_flux_q32,
+                                           uint32_t *far_hist, uint64_t *far_reflected_flux_q32, uint64_t *far_stats,
+                                           uint64_t *far_power_q32) {
+  if (!rad) return set_error(BZR_ERR_INVALID_ARGUMENT, "null radiometry");
+  if (!far && (far_flux_q32 || far_hist || far_reflected_flux_q32 || far_stats || far_power_q32))
+    return set_error(BZR_ERR_INVALID_ARGUMENT, "far outputs given without a far-field frame");
+  if (!far && !tg) return set_error(BZR_ERR_INVALID_ARGUMENT, "neither a target nor a far-field frame");
+  if (far) {
+    FarFrame checked{};
+    if (bzr_status s = far_frame(far, nchan, checked)) return s;
+  }
+  const IllumFar ifar{far, far_flux_q32, far_hist, far_reflected_flux_q32, far_stats, far_power_q32};
+  IllumTir tir{max_bounces, reflected_flux_q32, reflected_hist, ledger_count, ledger_power_q32};
+  tir.media = true;
+  tir.gap = gap_table;
+  tir.glass_absorb = glass_absorb;
+  tir.gap_absorb = gap_absorb;
+  tir.far = far ? &ifar : nullptr;
+  tir.ghost = true;
+  tir.ghost_seed = ghost_seed;
   return illuminate(ctx, lenses, ri_table, nlens, em, total_rays, tg, rad, flux_q32, hist, stats, power_q32, flags, true,
                     nchan, &tir);
 }

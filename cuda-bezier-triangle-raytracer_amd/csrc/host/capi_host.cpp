@@ -269,6 +269,22 @@ bzr_status bzr_absorption_from_transmittance(const double *internal_transmittanc
   return BZR_OK;
 }
 
+// ---- the Fresnel roulette's uniform (include/bzr.h bzr_trace_chain_ghost): the host twin of trace.hip ghost_uniform ----
+static uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+bzr_status bzr_ghost_uniform(uint64_t seed, uint64_t ray, uint32_t lens, uint32_t reflections, float *u) {
+  if (!u) return bad("null u");
+  if (lens > 7u || reflections > BZR_MAX_BOUNCES) return bad("lens must be 0..7 and reflections 0..8");
+  const uint64_t e = 16u * lens + reflections;
+  const uint64_t r = mix64((seed ^ 0x5851F42D4C957F2Dull) + 0x9E3779B97F4A7C15ull * (ray + 1ull));
+  const uint64_t h = mix64(r + 0x9E3779B97F4A7C15ull * (e + 1ull));
+  *u = static_cast<float>(static_cast<uint32_t>(h >> 40)) * 0x1p-24f;
+  return BZR_OK;
+}
+
 // ---- far field (include/bzr.h bzr_farfield) ----
 // The frame's checks and what every user derives from it, stated once: the pole n = axis_u x axis_v normalised as
 // illuminate() normalises the target's normal, S = R + R and the cell sizes.  out[13]: n, axis_u, axis_v, R, S, cu,

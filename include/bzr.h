@@ -384,6 +384,44 @@ bzr_status bzr_trace_chain_absorb(bzr_ctx *ctx, const bzr_mesh *const *lenses, c
                                   const float *weight_in, const float *opl_in, uint32_t n, uint32_t max_bounces,
                                   float *out_rays_soa, float *out_weight, uint32_t *out_status, uint32_t *out_segments,
                                   uint32_t *out_bounces, float *out_opl, float *out_glass, uint32_t flags);
+/* ---- Fresnel ghost reflections: the roulette at glass exits ----
+ * bzr_trace_chain_absorb plus two arguments behind max_bounces: ghost_seed, and first_ray -- ray i of the call has the
+ * 64-bit ray number j = first_ray + i (mod 2^64).  Everything is bzr_trace_chain_absorb's except the following.
+ * The draw happens in a segment expected OUTSIDE, for a ray whose channel is in the table, whose winning hit is an
+ * intersection with cs >= 0 and s2 = eta^2 (1 - cs^2) < 0.99 -- exactly the rays Snell's step refracts out of the
+ * glass -- and that has made k < max_bounces reflections in this lens l so far:
+ *   T = fresnel_t(eta, cs, s2), the value the absorbing chain multiplies in (exact binary32 in both modes);
+ *   u = G(ghost_seed, j, e) with e = 16 l + k (l <= 7, k <= 7);
+ *   u >= T: the ray reflects -- the mirror step of a total reflection bit for bit (k2 = 2 cs, r = d - n k2 per
+ *           component, normalised, origin at the hit's point); out_bounces goes up, the ray meets the same lens again
+ *           expected OUTSIDE, and its weight gets the leg's attenuation A alone, like a total reflection;
+ *   u <  T: the ray refracts as before, but its weight gets A alone: T is not multiplied in, the roulette already took
+ *           the 1 - T share.
+ * With k == max_bounces (the budget spent) there is no draw: the ray refracts with w = (w A) T as in
+ * bzr_trace_chain_absorb, so no ray leaves a lens pending, and max_bounces = 0 is bzr_trace_chain_absorb bit for bit on
+ * every pipeline and under BZR_MODE_FAST.  s2 >= 1 (total reflection), 0.99 <= s2 < 1, a NaN and a hit on the wrong
+ * side are unchanged.  A segment expected INSIDE is unchanged: w = (w A) T, a front surface never reflects.  The
+ * optical path and glass legs are unchanged; a reflected leg is a glass leg, as for a total reflection.
+ * The uniform, in 64-bit unsigned arithmetic mod 2^64, mix64 being the splitmix64 finaliser
+ * (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31):
+ *   r = mix64((ghost_seed ^ 0x5851F42D4C957F2D) + 0x9E3779B97F4A7C15 * (j + 1))
+ *   h = mix64(r + 0x9E3779B97F4A7C15 * (e + 1))
+ *   u = (h >> 40) / 2^24        (a 24-bit uniform in [0, 1), exact in binary32)
+ * The xor keeps it off the emitter's stream.  A ray's draws depend on nothing but (ghost_seed, j, l, k): the results do
+ * not depend on the pipeline, the chunking, the batching or on which other rays are in the call -- a call over all rays
+ * at first_ray = F equals the calls over [0, m) at F and [m, n) at F + m bit for bit.  The estimator is unbiased: the
+ * expected weight of the rays that leave with no reflection is bzr_trace_chain_absorb's, and the reflected share now
+ * travels on as rays instead of vanishing.  The argument checks are bzr_trace_chain_absorb's. */
+bzr_status bzr_trace_chain_ghost(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                 const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                 uint32_t nlens, uint32_t nchan, const float *rays_soa, const uint8_t *channel,
+                                 const float *weight_in, const float *opl_in, uint32_t n, uint32_t max_bounces,
+                                 uint64_t ghost_seed, uint64_t first_ray,
+                                 float *out_rays_soa, float *out_weight, uint32_t *out_status, uint32_t *out_segments,
+                                 uint32_t *out_bounces, float *out_opl, float *out_glass, uint32_t flags);
+/* The draw's host twin (no context, no device): *u = G(seed, ray, 16 lens + reflections).  lens above 7 or reflections
+ * above 8, or a NULL u, return BZR_ERR_INVALID_ARGUMENT with nothing written. */
+bzr_status bzr_ghost_uniform(uint64_t seed, uint64_t ray, uint32_t lens, uint32_t reflections, float *u);
 /* Absorption coefficients from a glass catalogue's internal transmittance, on the host (no context, no device):
  * out_a[i] = -ln(internal_transmittance[i]) / thickness, evaluated in binary64 and rounded once to float, per unit of
  * the length `thickness` is given in.  A transmittance outside (0, 1], a thickness that is not finite and positive or
@@ -692,6 +730,26 @@ bzr_status bzr_illuminate_farfield(bzr_ctx *ctx, const bzr_mesh *const *lenses, 
                                    uint64_t *ledger_count, uint64_t *ledger_power_q32, uint32_t flags,
                                    const bzr_farfield *far, uint64_t *far_flux_q32, uint32_t *far_hist,
                                    uint64_t *far_reflected_flux_q32, uint64_t *far_stats, uint64_t *far_power_q32);
+/* bzr_illuminate_farfield over the chain of bzr_trace_chain_ghost: ghost_seed follows max_bounces, and ray j of the
+ * emitter (its 64-bit ray number, whatever the batching) draws G(ghost_seed, j, e).  far may be NULL: the five far
+ * outputs must then be NULL and the call is bzr_illuminate_media with the roulette; at least one of target and far is
+ * given.  Ghost rays arrive where reflected rays do: in the reflected maps, far_reflected_flux_q32 and ledger rows >= 1.
+ * With rad->surface == BZR_SURFACE_LOSSLESS (no draw is taken) or max_bounces = 0 every output is
+ * bzr_illuminate_farfield's bit for bit.
+ * The ledger's count identities hold.  Its power line: at a drawn exit nothing is lost -- the ray carries its whole
+ * weight out or back in -- so under BZR_SURFACE_FRESNEL what leaves the account, beside absorption, is the 1 - T share
+ * at every entry into a lens and at the exits of rays whose budget was spent; the expectation of every row-0 sum is
+ * bzr_illuminate_farfield's. */
+bzr_status bzr_illuminate_ghost(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                uint32_t nlens, uint32_t nchan, const bzr_emitter *em, uint64_t total_rays,
+                                const bzr_target *target, const bzr_radiometry *rad, uint32_t max_bounces,
+                                uint64_t ghost_seed, uint64_t *flux_q32, uint32_t *hist,
+                                uint64_t *reflected_flux_q32, uint32_t *reflected_hist,
+                                uint64_t *stats, uint64_t *power_q32,
+                                uint64_t *ledger_count, uint64_t *ledger_power_q32, uint32_t flags,
+                                const bzr_farfield *far, uint64_t *far_flux_q32, uint32_t *far_hist,
+                                uint64_t *far_reflected_flux_q32, uint64_t *far_stats, uint64_t *far_power_q32);
 /* Host helpers (no device).  bzr_farfield_cell: the cell rule above on the host, the device's twin: *cell is the
  * cell of direction d, or -1 where d is not binned (maps of 2^31 cells or more are refused).
  * bzr_farfield_directions: each cell centre in binary64, cell-major: dir_xyz [cells][3] the unit direction,

@@ -494,6 +494,15 @@ void traceChainAbsorb(std::vector<BezierLens const *> const &lenses, std::vector
                       float const *opl, std::size_t n, uint32_t maxBounces, Ray *outRays, float *outWeights,
                       RefractionResult *outStatus, float *outOpl, float *outGlass = nullptr, uint32_t *outSegments = nullptr,
                       uint32_t *outBounces = nullptr, Context *ctx = nullptr);
+// traceChainAbsorb with the Fresnel roulette at glass exits (bzr_trace_chain_ghost): ray i draws with the 64-bit ray
+// number firstRay + i and ghostSeed, so a batch split in two calls (firstRay moved along) gives the same bits;
+// maxBounces = 0 is traceChainAbsorb bit for bit.  Throws what traceChainAbsorb throws.
+void traceChainGhost(std::vector<BezierLens const *> const &lenses, std::vector<float> const &riTable,
+                     std::vector<float> const &gapTable, std::vector<float> const &glassAbsorb,
+                     std::vector<float> const &gapAbsorb, Ray const *rays, uint8_t const *channels, float const *weights,
+                     float const *opl, std::size_t n, uint32_t maxBounces, uint64_t ghostSeed, uint64_t firstRay,
+                     Ray *outRays, float *outWeights, RefractionResult *outStatus, float *outOpl, float *outGlass = nullptr,
+                     uint32_t *outSegments = nullptr, uint32_t *outBounces = nullptr, Context *ctx = nullptr);
 // Bins a traced batch by direction into a far-field map (bzr_farfield_bin): rays [n] as the traceChain* calls return
 // them (only the directions are read), weights, status and channels [n] each may be null (1.0f; every ray is seen,
 // otherwise only cOutside rays; channel 0).  farFlux / farHist [nchan][bins_v][bins_u] accumulate (one may be null);

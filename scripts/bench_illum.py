@@ -3,7 +3,7 @@
 on the cfg2 lens, emitter just behind it (inside the lens's bounding sphere, so nothing is culled and
 every ray is traced).  Prints one JSON line: emitted rays / s and the landed fraction.
 
-usage: bench_illum.py [total_rays] [--power] [--tir [max_bounces]] [--media] [--farfield]
+usage: bench_illum.py [total_rays] [--power] [--tir [max_bounces]] [--media] [--farfield] [--ghost]
 --power times bzr_illuminate_power (Lambert emitter, Fresnel surfaces: k_emit<true> -> chain with weights ->
 k_land<true>, 64-bit flux cells) beside bzr_illuminate on the same rays, alternating, and prints one more JSON line
 with both; the chain kernels' share comes from the context's event timing in a separate pass, the rest of a call is
@@ -20,7 +20,11 @@ whole-call times scatter by +- 15 % here.
 --farfield prints one more JSON line: on the same wide emitter and media, bzr_illuminate_media and
 bzr_illuminate_farfield (the same call plus a 256^2 far-field map at R = sqrt(2), axes the target's) on the same emitted rays, alternating, the far-field call without a target, and the far-field call with
 k_land_far's wave combine forced to 0, 4 and 64 rounds; the ratio is the cost of k_land_far per batch and of the far
-maps' staging."""
+maps' staging.
+--ghost prints one more JSON line: on the same wide emitter, media and far-field frame, bzr_illuminate_farfield (the
+yardstick), bzr_illuminate_ghost at budget 0 (its stats and power checked equal to the yardstick's at budget 0) and
+bzr_illuminate_ghost at four reflections on the same emitted rays, alternating and rotated; the ratio is the cost of the
+roulette's draws and of the bounce segments of the rays it reflects, and the ledger shows where they went."""
 import json
 import statistics
 import sys
@@ -36,7 +40,7 @@ from bzr_amd.configs import CONFIGS, build_lens  # noqa: E402
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--power", "--media", "--farfield")]
+    args = [a for a in sys.argv[1:] if a not in ("--power", "--media", "--farfield", "--ghost")]
     power, media, farfield = "--power" in sys.argv[1:], "--media" in sys.argv[1:], "--farfield" in sys.argv[1:]
     tir = None
     if "--tir" in args:
@@ -63,6 +67,8 @@ def main():
         bench_media(ctx, dm, tg, total)
     if farfield:
         bench_farfield(ctx, dm, tg, total)
+    if "--ghost" in sys.argv[1:]:
+        bench_ghost(ctx, dm, tg, total)
     if not power:
         return
 
@@ -238,6 +244,59 @@ def bench_farfield(ctx, dm, tg, total, max_bounces=4):
                       "exited": sum(s["exited"] for s in out["illuminate_farfield"][0]),
                       "binned_power_fraction": round(sum(p["binned"] for p in fo["power"]) /
                                                      max(sum(p["emitted"] for p in out["illuminate_farfield"][1]), 1), 5)}))
+
+
+def bench_ghost(ctx, dm, tg, total, max_bounces=4, seed=2024):
+    row1 = [1.3, 1.5, 1.8, 2.4]
+    gaps, glass, front = [[1.41, 1.333, 1.2, 1.0], [1.0] * 4], [[0.05, 0.7, 0.4, 200.0]], [[0.3, 0.02, 0.0, 0.1]]
+    em = bzr_amd.Emitter(origin=(8.0, -3.0, -1.5), edge_u=(0.0, 6.0, 0.0), edge_v=(0.0, 0.0, 3.0), parts_u=4, parts_v=4,
+                         points_per_part=1024, rays_per_point=1024, belts=16, seed=1)
+    far = bzr_amd.FarField(axis_u=(0.0, 1.0, 0.0), axis_v=(0.0, 0.0, 1.0), extent=bzr_amd.SQRT2, bins_u=256, bins_v=256)
+
+    def farfield(n, budget=max_bounces):
+        return bzr_amd.illuminate_farfield(ctx, [dm], [row1], gaps, glass, front, em, n, tg, far, max_bounces=budget)[4:]
+
+    def ghost(n, budget=max_bounces):
+        return bzr_amd.illuminate_ghost(ctx, [dm], [row1], gaps, glass, front, em, n, tg, far, max_bounces=budget,
+                                        ghost_seed=seed)[4:]
+
+    calls = {"illuminate_farfield": farfield, "illuminate_ghost_0": lambda n: ghost(n, 0), "illuminate_ghost": ghost}
+    for call in calls.values():
+        call(1 << 20)  # warm-up
+    same = farfield(1 << 20, 0)[:2] == ghost(1 << 20, 0)[:2]
+    wall, out = {k: [] for k in calls}, {}
+    names = list(calls)
+    for r in range(6):  # alternating and rotated, as bench_tir
+        for name in names[r % 3:] + names[:r % 3]:
+            t0 = time.perf_counter()
+            out[name] = calls[name](total)
+            wall[name].append(time.perf_counter() - t0)
+    chain = {}
+    for name in names:
+        ctx.timing(True)
+        ctx.timing_report()
+        calls[name](total)
+        chain[name] = sum(v[0] for v in ctx.timing_report().values()) / 1e3
+        ctx.timing(False)
+    med = {k: statistics.median(v) for k, v in wall.items()}
+    count = {k: out[k][2]["count"].sum(axis=0) for k in ("illuminate_farfield", "illuminate_ghost")}
+    print(json.dumps({"workload": "illuminate_ghost beside illuminate_farfield, cfg2 lens, emitter at x=8 (no cull), "
+                                  "indices 1.3/1.5/1.8/2.4, 512^2 target, 256^2 far-field map",
+                      "rays": total, "max_bounces": max_bounces, "ghost_seed": seed,
+                      "seconds": {k: round(v, 4) for k, v in med.items()},
+                      "seconds_min_max": {k: [round(min(v), 4), round(max(v), 4)] for k, v in wall.items()},
+                      "mrays_per_s": {k: round(total / v / 1e6, 1) for k, v in med.items()},
+                      "chain_kernels_seconds": {k: round(v, 4) for k, v in chain.items()},
+                      "ghost_0_over_farfield": round(med["illuminate_ghost_0"] / med["illuminate_farfield"], 4),
+                      "ghost_over_farfield": round(med["illuminate_ghost"] / med["illuminate_farfield"], 4),
+                      "ghost_over_farfield_rounds": [round(x / y, 4) for x, y in
+                                                     zip(wall["illuminate_ghost"], wall["illuminate_farfield"])],
+                      "budget_0_stats_and_power_same_as_farfield": bool(same),
+                      "reflecting_fraction": {k: round(int(v[1:, :2].sum()) / total, 5) for k, v in count.items()},
+                      "landed_reflected": {k: int(v[1:, 2].sum()) for k, v in count.items()},
+                      "landed_power_fraction": {k: round(sum(p["landed"] for p in out[k][1]) /
+                                                         max(sum(p["emitted"] for p in out[k][1]), 1), 5) for k in count},
+                      "ledger_rows_lost_exited_landed": {k: v.tolist() for k, v in count.items()}}))
 
 
 if __name__ == "__main__":
