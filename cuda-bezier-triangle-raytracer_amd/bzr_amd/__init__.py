@@ -40,6 +40,7 @@ RAYS_AOS = 32  # rays / out_rays as [n, 6] records (the reference's Ray layout),
 WHAT_FOLLOW0, WHAT_FOLLOW1, WHAT_FOLLOW2, WHAT_NONE, WHAT_INTERSECT = 0, 1, 2, 3, 4
 LIMIT_THIS, LIMIT_NONE = 0, 1
 RR_NONE, RR_INSIDE, RR_OUTSIDE = 0, 1, 2
+RR_BACK = 4  # BZR_RR_BACK: trace_chain_bidir alone, the ray left the chain in front of its first lens
 ENVELOPE_ELLIPSOID, ENVELOPE_TESTLENS = 0, 1
 PATCH_WORDS = 66  # sizeof(bzr_patch) / 4
 KERNELS = ("k_traverse", "bucket", "k_newton", "k_follow", "k_finish", "k_overflow", "k_intersect_scan",
@@ -86,6 +87,11 @@ _SIGS = {
     "bzr_trace_chain_ghost": [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _U32, _U32, ctypes.c_uint64,
                               ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _P, _U32],
     "bzr_ghost_uniform": [ctypes.c_uint64, ctypes.c_uint64, _U32, _U32, _P],
+    "bzr_trace_chain_bidir": [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _U32, _U32, ctypes.c_uint64,
+                              ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _U32],
+    "bzr_bidir_uniform": [ctypes.c_uint64, ctypes.c_uint64, _U32, _P],
+    "bzr_illuminate_bidir": [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, ctypes.c_uint64, _P, _P, _U32, ctypes.c_uint64, _P, _P,
+                             _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P],
     "bzr_absorption_from_transmittance": [_P, _U32, ctypes.c_double, _P],
     "bzr_dispersion_index": [_I32, _P, _U32, _P, _U32, _P],
     "bzr_trace_tiled": [_P, _U32, _P, _P, _U32, _P, _U32, _U32, _P, _P, _P, _U32],
@@ -157,7 +163,8 @@ _ADDED = ("bzr_trace_chain_power", "bzr_illuminate_power", "bzr_trace_chain_spec
           "bzr_trace_chain_media", "bzr_trace_chain_absorb", "bzr_absorption_from_transmittance",
           "bzr_illuminate_media", "bzr_debug_attenuation", "bzr_farfield_bin", "bzr_illuminate_farfield",
           "bzr_farfield_cell", "bzr_farfield_directions", "bzr_farfield_intensity", "bzr_debug_farfield_cells",
-          "bzr_trace_chain_ghost", "bzr_ghost_uniform", "bzr_illuminate_ghost")
+          "bzr_trace_chain_ghost", "bzr_ghost_uniform", "bzr_illuminate_ghost", "bzr_trace_chain_bidir",
+          "bzr_bidir_uniform", "bzr_illuminate_bidir")
 _RET = {"bzr_last_error": ctypes.c_char_p, "bzr_abi_version": _I32}
 
 _lib = None
@@ -720,6 +727,58 @@ def trace_chain_ghost(ctx: Context, lenses, ri_table, gap_table, glass_absorb, g
     return out_rays, out_weight, out_status, out_segments, out_bounces, out_opl, out_glass
 
 
+def trace_chain_bidir(ctx: Context, lenses, ri_table, gap_table, glass_absorb, gap_absorb, rays, channel=None, weight=None,
+                      opl=None, max_bounces=4, ghost_seed=0, first_ray=0, axis=(1.0, 0.0, 0.0), out_rays=None,
+                      out_weight=None, out_status=None, out_segments=None, out_bounces=None, out_opl=None, out_glass=None,
+                      mode=MODE_PARITY):
+    """The bidirectional chain -> trace_chain_ghost's seven-tuple.  The roulette runs at every surface, front surfaces
+    included; a ray goes on to the neighbour lens that the surface it left faces along `axis` (the chain's forward
+    direction), and ends RR_OUTSIDE behind the last lens, RR_BACK in front of the first, or RR_NONE.  max_bounces is the
+    ray's budget for its whole path.  Fused, or ACCEL_NONE for the scan; PIPELINE_STAGED is refused (bzr.h
+    bzr_trace_chain_bidir)."""
+    n = _n_of(rays, mode)
+    nl = len(lenses)
+    handles = (_P * nl)(*[m.handle for m in lenses])
+    table, nchan = _ri_table(ri_table, nl)
+    gap = _gap_table(gap_table, nl, nchan)
+    ga, pa = _absorb_table(glass_absorb, "glass_absorb", nl, nchan), _absorb_table(gap_absorb, "gap_absorb", nl, nchan)
+    ax = np.ascontiguousarray(axis, np.float32)
+    if ax.shape != (3,):
+        raise BzrError("axis must have three components")
+    out_rays = _empty_like(rays, 6, np.float32, mode) if out_rays is None else out_rays
+    out_weight = _empty_like(rays, 0, np.float32, mode) if out_weight is None else out_weight
+    out_status = _empty_like(rays, 0, np.uint32, mode) if out_status is None else out_status
+    out_segments = _empty_like(rays, 0, np.uint32, mode) if out_segments is None else out_segments
+    out_bounces = _empty_like(rays, 0, np.uint32, mode) if out_bounces is None else out_bounces
+    out_opl = _empty_like(rays, 0, np.float32, mode) if out_opl is None else out_opl
+    if out_glass is False:
+        out_glass = None
+    elif out_glass is None:
+        out_glass = _empty_like(rays, 0, np.float32, mode)
+    r, c, wi, pi = _Buf(rays, np.float32), _Buf(channel, np.uint8), _Buf(weight, np.float32), _Buf(opl, np.float32)
+    o, w = _Buf(out_rays, np.float32, True), _Buf(out_weight, np.float32, True)
+    s, g, b = _Buf(out_status, np.uint32, True), _Buf(out_segments, np.uint32, True), _Buf(out_bounces, np.uint32, True)
+    p, q = _Buf(out_opl, np.float32, True), _Buf(out_glass, np.float32, True)
+    res = _residency(r, c, o, w, s, g, b, wi, pi, p, q)
+    mask = (1 << 64) - 1
+    with _stream_for(ctx, res):
+        _check(lib().bzr_trace_chain_bidir(ctx.handle, ctypes.cast(handles, _P), table.ctypes.data if table.size else None,
+                                           _table_ptr(gap), _table_ptr(ga), _table_ptr(pa), nl, nchan, r.ptr, c.ptr,
+                                           wi.ptr, pi.ptr, n, int(max_bounces), int(ghost_seed) & mask,
+                                           int(first_ray) & mask, ax.ctypes.data, o.ptr, w.ptr, s.ptr, g.ptr, b.ptr, p.ptr,
+                                           q.ptr, res | mode))
+    return out_rays, out_weight, out_status, out_segments, out_bounces, out_opl, out_glass
+
+
+def bidir_uniform(seed: int, ray: int, segment: int) -> np.float32:
+    """trace_chain_bidir's draw on the host: the 24-bit uniform of (seed, the ray's 64-bit number, the segment's ordinal
+    counted from 0) (bzr.h bzr_bidir_uniform)."""
+    u = ctypes.c_float()
+    mask = (1 << 64) - 1
+    _check(lib().bzr_bidir_uniform(int(seed) & mask, int(ray) & mask, int(segment), ctypes.byref(u)))
+    return np.float32(u.value)
+
+
 def ghost_uniform(seed: int, ray: int, lens: int, reflections: int) -> np.float32:
     """The roulette's draw on the host, the device's twin: a 24-bit uniform in [0, 1) for (seed, the ray's 64-bit
     number, lens 0..7, reflections in that lens so far 0..8) (bzr.h bzr_ghost_uniform)."""
@@ -1060,10 +1119,11 @@ def illuminate_media(ctx: Context, lenses, ri_table, gap_table, glass_absorb, ga
 
 
 def _illuminate_reflecting(ctx, lenses, ri_table, media, em, total_rays, target, max_bounces, emission, surface, flux, hist,
-                           reflected_flux, reflected_hist, mode, far=None, ghost_seed=None):
+                           reflected_flux, reflected_hist, mode, far=None, ghost_seed=None, axis=None):
     """illuminate_tir (media None), illuminate_media (media = the gap table and the two absorption tables) or
     illuminate_farfield (far = the frame and its three maps, each map or None; target may then be None);
-    illuminate_ghost: ghost_seed given, media given, far or None."""
+    illuminate_ghost: ghost_seed given, media given, far or None; illuminate_bidir: and axis given -- the ledger dict
+    then holds the BACK rays' rows too, "back_count" and "back_power" [nchan][LEDGER_ROWS]."""
     nl = len(lenses)
     handles = (_P * nl)(*[m.handle for m in lenses])
     table, nchan = _ri_table(ri_table, nl)
@@ -1108,8 +1168,20 @@ def _illuminate_reflecting(ctx, lenses, ri_table, media, em, total_rays, target,
     tail = (nl, nchan, ctypes.byref(em), int(total_rays), ctypes.byref(target) if target is not None else None,
             ctypes.byref(rad), int(max_bounces), f.ptr,
             h.ptr, rf.ptr, rh.ptr, stats, power, ledger["count"].ctypes.data, ledger["power"].ctypes.data, res | mode)
+    back = {k: np.zeros((rows, LEDGER_ROWS), np.uint64) for k in ("back_count", "back_power")}
     with _stream_for(ctx, res):
-        if ghost_seed is not None:
+        if axis is not None:
+            ax = np.ascontiguousarray(axis, np.float32)
+            if ax.shape != (3,):
+                raise BzrError("axis must have three components")
+            far_args = (ctypes.byref(frame), ff.ptr, fh.ptr, frf.ptr, fstats, fpower) if far is not None else (None,) * 6
+            _check(lib().bzr_illuminate_bidir(ctx.handle, handles, table.ctypes.data if table.size else None,
+                                              *[_table_ptr(a) for a in media], *tail[:7],
+                                              int(ghost_seed) & ((1 << 64) - 1), ax.ctypes.data, *tail[7:-1],
+                                              back["back_count"].ctypes.data, back["back_power"].ctypes.data, tail[-1],
+                                              *far_args))
+            ledger.update(back)
+        elif ghost_seed is not None:
             far_args = (ctypes.byref(frame), ff.ptr, fh.ptr, frf.ptr, fstats, fpower) if far is not None else (None,) * 6
             _check(lib().bzr_illuminate_ghost(ctx.handle, handles, table.ctypes.data if table.size else None,
                                               *[_table_ptr(a) for a in media], *tail[:7],
@@ -1225,6 +1297,30 @@ def illuminate_ghost(ctx: Context, lenses, ri_table, gap_table, glass_absorb, ga
                                   flux, hist, reflected_flux, reflected_hist, mode,
                                   far=None if far is None else (far, far_flux, far_hist, far_reflected_flux),
                                   ghost_seed=ghost_seed)
+
+
+def illuminate_bidir(ctx: Context, lenses, ri_table, gap_table, glass_absorb, gap_absorb, em: Emitter, total_rays: int,
+                     target, far=None, max_bounces=4, ghost_seed=0, axis=(1.0, 0.0, 0.0), emission=EMISSION_LAMBERT,
+                     surface=SURFACE_FRESNEL, flux=None, hist=None, reflected_flux=None, reflected_hist=None,
+                     far_flux=None, far_hist=None, far_reflected_flux=None, mode=MODE_PARITY):
+    """illuminate_ghost over trace_chain_bidir's chain, `axis` its forward direction.  Returns illuminate_ghost's tuple;
+    its ledger dict also holds "back_count" and "back_power" [nchan][LEDGER_ROWS]: the rays that left in front of the
+    first lens (RR_BACK), by min(bounces, MAX_BOUNCES), and their summed q(w).  Those rays are in no ledger field and
+    in no map; per channel LOST + EXITED + BACK over the rows is EMITTED - CULLED (bzr.h bzr_illuminate_bidir)."""
+    nl = len(lenses)
+    _, nchan = _ri_table(ri_table, nl)
+    media = (_gap_table(gap_table, nl, nchan), _absorb_table(glass_absorb, "glass_absorb", nl, nchan),
+             _absorb_table(gap_absorb, "gap_absorb", nl, nchan))
+    if target is None and far is None:
+        raise BzrError("neither a target nor a far-field frame")
+    if target is None and any(a is not None for a in (flux, hist, reflected_flux, reflected_hist)):
+        raise BzrError("target maps given without a target")
+    if far is None and any(a is not None for a in (far_flux, far_hist, far_reflected_flux)):
+        raise BzrError("far maps given without a far-field frame")
+    return _illuminate_reflecting(ctx, lenses, ri_table, media, em, total_rays, target, max_bounces, emission, surface,
+                                  flux, hist, reflected_flux, reflected_hist, mode,
+                                  far=None if far is None else (far, far_flux, far_hist, far_reflected_flux),
+                                  ghost_seed=ghost_seed, axis=axis)
 
 
 def farfield_cell(far: FarField, directions) -> np.ndarray:
@@ -1415,6 +1511,7 @@ class TriMesh:
 __all__ = [
     "BzrError", "Context", "DeviceMesh", "TriMesh", "intersect", "patch_intersect", "refract", "trace_chain", "interpolate",
     "Emitter", "Target", "emit", "illuminate", "bounding_sphere",
-    "FarField", "farfield_bin", "illuminate_farfield", "trace_chain_ghost", "ghost_uniform", "illuminate_ghost", "farfield_cell", "farfield_directions", "farfield_intensity",
+    "FarField", "farfield_bin", "illuminate_farfield", "trace_chain_ghost", "ghost_uniform", "illuminate_ghost",
+    "trace_chain_bidir", "bidir_uniform", "illuminate_bidir", "RR_BACK", "farfield_cell", "farfield_directions", "farfield_intensity",
     "device_count", "lib", "exported_symbols", "LIB_PATH",
 ]

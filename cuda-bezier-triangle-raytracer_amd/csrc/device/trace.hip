@@ -420,6 +420,54 @@ __device__ __forceinline__ uint32_t ghost_eta_t(const Hit &h, float eta, f3 s, f
   if (drawn) gain = 1.0f;
   return st;
 }
+// The bidirectional walk's step (kModeBidir; include/bzr.h bzr_trace_chain_bidir): ghost_eta_t on either side of the
+// glass.  `expected` names the side the segment must meet -- INSIDE (cs < 0) for an open segment, OUTSIDE (cs >= 0)
+// for a glass segment -- and on that side, with `may_reflect` (the channel is in the table, the ray's budget is not
+// spent), s2 >= 1 mirrors the ray and s2 < 0.99 draws when `may_draw`: u >= T mirrors, u < T refracts with gain 1.
+// The mirror step is tir_eta_t's for both signs of cs.  Everything else is refract_eta_t.  (A sibling again.)
+template <bool kGain>
+__device__ __forceinline__ uint32_t bidir_eta_t(const Hit &h, float eta, f3 s, f3 d, uint32_t expected, bool may_reflect,
+                                                bool may_draw, float u, f3 &o_s, f3 &o_d, float &gain) {
+  const float s2 = eta * eta * (1.0f - h.cs * h.cs);
+  const bool side = expected == BZR_RR_INSIDE ? h.cs < 0.0f : h.cs >= 0.0f;
+  const bool facing = may_reflect && h.what == kIntersect && side;
+  const bool drawn = facing && may_draw && s2 < 0.99f;
+  bool mirror = facing && s2 >= 1.0f;
+  if (drawn) mirror = u >= fresnel_t(eta, h.cs, s2);
+  if (mirror) {
+    const float k = 2.0f * h.cs;
+    o_d = normalized(sub(d, scale(h.normal, k)));
+    o_s = h.point;
+    return kReflected;
+  }
+  const uint32_t st = refract_eta_t<kGain>(h, eta, s, d, expected, o_s, o_d, gain);
+  if (drawn) gain = 1.0f;
+  return st;
+}
+// The walk's side rule: does the surface a glass segment met face forward along the chain's axis `a`?  One dot product
+// in binary32, the last two products summed first (no contraction: the build's -ffp-contract=off).
+__device__ __forceinline__ bool bidir_back(f3 n, f3 a) { return n.x * a.x + (n.y * a.y + n.z * a.z) >= 0.0f; }
+// The walk's per-lane word (k_trace<kModeBidir>'s LDS row `state`, k_chain_scan<8>'s register): bits 0-3 the key
+// 2 lens + phase (phase 1: inside that lens's glass; 0: in the open, heading for it), bit 4 fwd, bit 5 travelling,
+// bits 8-10 the final status once it no longer travels.
+constexpr uint32_t kBidirFwd = 1u << 4, kBidirTravels = 1u << 5;
+__device__ __forceinline__ uint32_t bidir_ended(uint32_t status) { return status << 8; }
+// The word of a ray that has just come into gap g heading `fwd`: it ends OUTSIDE behind the last lens, BACK in front of
+// the first, and otherwise heads for lens g (fwd) or g - 1.
+__device__ __forceinline__ uint32_t bidir_open(uint32_t g, bool fwd, uint32_t nlens) {
+  if (fwd && g == nlens) return bidir_ended(BZR_RR_OUTSIDE);
+  if (!fwd && g == 0u) return bidir_ended(BZR_RR_BACK);
+  return 2u * (fwd ? g : g - 1u) | (fwd ? kBidirFwd : 0u) | kBidirTravels;
+}
+// One event's step from the word `w0` (key 2 l + gl): `r` the step's result (NONE, kReflected, or the side refracted
+// to), gi the gap the segment's leg lies in (open) or leads to (glass), `back` the side rule's answer.
+__device__ __forceinline__ uint32_t bidir_next(uint32_t w0, uint32_t r, bool gl, uint32_t l, uint32_t gi, bool back,
+                                               uint32_t nlens) {
+  if (r == BZR_RR_NONE) return bidir_ended(BZR_RR_NONE);
+  if (r == kReflected) return gl ? w0 : bidir_open(gi, (w0 & kBidirFwd) == 0u, nlens);  // in glass: the same lens again
+  if (!gl) return (2u * l + 1u) | kBidirTravels;                                        // refracted in
+  return bidir_open(gi, back, nlens);                                                   // refracted out into gap gi
+}
 // The segment's eta: one correctly rounded division, n0 / n1 going in, n1 / n2 coming out (bounce segments included).
 __device__ __forceinline__ float media_eta(float n0, float n1, float n2, bool outside) {
   return div_rn(outside ? n1 : n0, outside ? n2 : n1);
@@ -617,12 +665,19 @@ constexpr uint32_t kGapPart = (kMaxLenses + 1u) * BZR_MAX_CHANNELS, kAbsorbPart 
 // had.  Its one job word, ghost_base, shares kModeHits' `hits` slot of TraceJob: with a field of its own behind gap_table
 // the non-counting k_trace<kModeGhost> came out with 36 and 68 B of scratch reserved (never accessed), kModeAbsorb's
 // artefact again, and every k_trace of the parent with another kernarg size (DESIGN (a)).
+// kModeBidir: the bidirectional walk (include/bzr.h bzr_trace_chain_bidir) -- kModeGhost's words per ray, but the roulette
+// runs at every surface (bidir_eta_t) and a ray goes to whichever neighbour lens the surface it left faces, so the lens is
+// per lane: the wave picks one (lens, phase) key per round (k_trace below).  Fused and scan only; no staged form.  Its
+// three job words, the chain's axis, share kModeRefract's `expected` and `expected_all` slots of TraceJob, as ghost_base
+// shares `hits`: TraceJob keeps its size and the older kernels their code.  A mode of its own: the other ten compile to
+// the code they had.
 enum OutMode {
   kModeHits = 0, kModeRefract = 1, kModeStage = 2, kModePower = 3, kModeSpectral = 4, kModeTir = 5, kModeOpl = 6,
-  kModeMedia = 7, kModeAbsorb = 8, kModeGhost = 9
+  kModeMedia = 7, kModeAbsorb = 8, kModeGhost = 9, kModeBidir = 10
 };
 constexpr bool has_ghost(int mode) { return mode == kModeGhost; }
-constexpr bool has_absorb(int mode) { return mode == kModeAbsorb || has_ghost(mode); }
+constexpr bool has_bidir(int mode) { return mode == kModeBidir; }
+constexpr bool has_absorb(int mode) { return mode == kModeAbsorb || has_ghost(mode) || has_bidir(mode); }
 constexpr bool has_media(int mode) { return mode == kModeMedia || has_absorb(mode); }
 constexpr bool has_opl(int mode) { return mode == kModeOpl || has_media(mode); }
 constexpr bool is_stage(int mode) {
@@ -2032,6 +2087,12 @@ template <>
 struct TraceKeep<kModeAbsorb> : TraceKeep<kModeMedia> {};  // and so does kModeAbsorb
 template <>
 struct TraceKeep<kModeGhost> : TraceKeep<kModeAbsorb> {};  // and kModeGhost: the draw is recomputed, nothing waits
+// kModeBidir: and the lane's place in the walk (bidir_open's word: key, fwd, travelling, final status), 256 B more per
+// wave: 6 232 B, 24 waves per CU still fit in 160 KiB (149 568 B).  The draw is recomputed here too.
+template <>
+struct TraceKeep<kModeBidir> : TraceKeep<kModeAbsorb> {
+  uint32_t state[64];
+};
 // The bundle walk's set of leaf slots already queued in this wave-segment (bundle_batch `seen`), one bit per
 // slot: the refract and chain kernels walk the trees with split leaf boxes (MeshView swide).  The intersect
 // kernel's 6.7 KB per wave leave no room for it (24 waves x 7.7 KB > 160 KB), and the power, spectral and TIR
@@ -2516,9 +2577,15 @@ struct TraceJob {
   float *out_rays;           // kModeRefract / kModeStage [6][n] (may alias rays in kModeStage)
   uint32_t *status;          // kModeRefract / kModeStage [n]
   uint32_t *segments;        // kModeStage, optional [n]
-  const uint32_t *expected;  // kModeRefract: per ray, or null -> expected_all
+  union {                    // (one word, two modes that never meet, as above)
+    const uint32_t *expected;  // kModeRefract: per ray, or null -> expected_all
+    float axis_xy[2];          // kModeBidir: the chain's forward axis, x and y
+  };
   const uint32_t *alive_in;  // kModeStage: rays with alive_in[i] == NONE are skipped and left untouched
-  uint32_t expected_all;
+  union {
+    uint32_t expected_all;
+    float axis_z;              // kModeBidir: and z
+  };
   uint32_t n;
   uint32_t ld;               // row stride of rays / out_rays / hits (>= n)
   unsigned long long *wave_clock;  // optional test hook: [2 * waves] start, duration (s_memtime ticks)
@@ -2545,6 +2612,12 @@ struct TraceJob {
 // (7 waves per SIMD) by itself; the intersect kernel (kModeHits: a 12-word winner) would take 82 (5 waves)
 // since the always list's bundle code, and the bound holds it at 80 (6 waves, as before) without scratch.
 constexpr int kTraceWpe = 6;
+// BZR_BIDIR_PICK: which (lens, phase) key a k_trace<kModeBidir> wave runs next -- 0: the lowest key held by a travelling
+// lane, 1 (default): the key most travelling lanes hold (cfg4 4096^2 at budget 2: 17.86 against 18.05 ms).  The results
+// do not depend on it (DESIGN (a), Appendix A).
+#ifndef BZR_BIDIR_PICK
+#define BZR_BIDIR_PICK 1
+#endif
 #define BZR_TRACE_ATTR __attribute__((amdgpu_waves_per_eu(kTraceWpe)))
 // Threads per k_trace block: its waves share nothing but the CU, so one-wave blocks let
 // a finished wave be replaced at once (waves run 1-4 segments; 64 vs 256: cfg4 -3 %, cfg5 -7 %).
@@ -2646,7 +2719,106 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
   float wgt = 1.0f;  // kModePower: the lane's power (loaded behind the first segment's walk, below)
   const uint32_t nseg = is_stage(kMode) ? 2u * lenses.count : 1u;
   uint32_t st = BZR_RR_NONE, seg = 0;
-  if constexpr (has_tir(kMode)) {
+  if constexpr (has_bidir(kMode)) {
+    // The walk is per lane, the segment per wave.  Each lane's place (bidir_open's word) waits in LDS beside the
+    // counters, the weight and the two paths.  Each round the wave votes for one key 2 lens + phase among the lanes
+    // still travelling (BZR_BIDIR_PICK), runs that lens's trace_segment over the lanes holding it and steps them; it
+    // ends when no lane travels.  A ray's step reads nothing but its own words and (ghost_base, its index), so the
+    // order of the rounds changes the time alone.  Every round steps at least one lane and a lane makes at most
+    // (max_bounces + 1)(2 count + 1) segments: the loop ends.
+    static_assert(sizeof(TraceLds<kMode>) * 24u <= 160u * 1024u, "24 waves of k_trace<kModeBidir> per CU");
+    L.count[lane] = 0u;
+    L.weight[lane] = 1.0f;
+    L.opl[lane] = 0.0f;
+    L.glass[lane] = 0.0f;
+    L.state[lane] = alive ? bidir_open(0u, true, lenses.count) : bidir_ended(BZR_RR_NONE);
+    for (uint32_t round = 0;; ++round) {
+      const uint32_t w0 = L.state[lane];
+      const bool travels = (w0 & kBidirTravels) != 0u;
+      uint32_t key = 16u;
+#if BZR_BIDIR_PICK == 0
+      for (uint32_t k = 0; k < 2u * lenses.count; ++k)  // the lowest key first
+        if (__ballot(travels && (w0 & 15u) == k)) {
+          key = k;
+          break;
+        }
+#else
+      uint32_t most = 0u;  // the key most lanes hold first (ties: the lowest)
+      for (uint32_t k = 0; k < 2u * lenses.count; ++k) {
+        const uint32_t held = popc64(__ballot(travels && (w0 & 15u) == k));
+        if (held > most) {
+          most = held;
+          key = k;
+        }
+      }
+#endif
+      if (key == 16u) break;
+      key = (uint32_t)__builtin_amdgcn_readfirstlane(key);
+      const uint32_t l = key >> 1;
+      const bool gl = (key & 1u) != 0u;  // a glass segment (expected OUTSIDE), or an open one (expected INSIDE)
+      const bool act = travels && (w0 & 15u) == key;
+      const MeshView &m = lenses.lens[l];
+      unsigned long long best;
+      const uint32_t r0 = ctr.rounds, p0 = ctr.pairs + ctr.follows;
+      trace_segment<kMode, kFast, kCount>(m, s, d, act, best, L, lane, ctr);
+      if (kCount) {
+        ctr.segments += popc64(__ballot(act));
+        if (gl) {
+          ctr.rounds_odd += ctr.rounds - r0;
+          ctr.runs_odd += ctr.pairs + ctr.follows - p0;
+        }
+      }
+      // (the caller's weight and path behind the first walk, as below; every traced lane is in the first round)
+      if (round == 0u && i < n && job.weight_in) L.weight[lane] = job.weight_in[i];
+      if (round == 0u && i < n && job.opl_in) L.opl[lane] = job.opl_in[i];
+      // everything of the step is read or made here, behind the segment's passes: the lane's word and counters from
+      // LDS, its channel and table entries from memory, the draw from the job's base word and the rebuilt ray index
+      const uint32_t cnt = L.count[lane];  // segments so far (low half), reflections so far (high half)
+      float u = 0.0f;
+      if (!job.lossless)
+        u = ghost_uniform(job.ghost_base, (uint32_t)__builtin_amdgcn_readfirstlane(tile * kTraceBlock) + threadIdx.x,
+                          256u + (cnt & 0xFFFFu));
+      Hit h = no_hit();
+      uint32_t patch = 0xFFFFFFFFu;
+      if (best != ~0ull) h = winner(L, lane, patch);
+      const uint32_t ch = (i < n && job.channel) ? job.channel[i] : 0u;
+      const bool in_table = ch < job.nchan;
+      const uint32_t c = in_table ? ch : 0u;
+      const float ri = job.ri_table[l * job.nchan + c];
+      const bool back = bidir_back(h.normal, mk(job.axis_xy[0], job.axis_xy[1], job.axis_z));
+      // the gap the leg lies in (open: the ray's own) or leads to (glass: behind the surface it met)
+      const uint32_t gi = gl ? (back ? l + 1u : l) : ((L.state[lane] & kBidirFwd) ? l : l + 1u);
+      const float ng = job.gap_table[gi * job.nchan + c];
+      const float eta = div_rn(gl ? ri : ng, gl ? ng : ri);
+      f3 os, od;
+      float gain = 1.0f;
+      uint32_t r = bidir_eta_t<true>(h, eta, s, d, gl ? uint32_t(BZR_RR_OUTSIDE) : uint32_t(BZR_RR_INSIDE),
+                                     in_table && (cnt >> 16) < job.max_bounces, !job.lossless, u, os, od, gain);
+      if (!in_table) r = BZR_RR_NONE;
+      if (job.lossless) gain = 1.0f;
+      if (act) {
+        if (r != BZR_RR_NONE) {
+          const float len = opl_leg_absorb(s, os, gl ? ri : ng, gl, L.opl[lane], L.glass[lane]);
+          const float a = job.gap_table[kGapPart + (gl ? l * job.nchan + c : kAbsorbPart + gi * job.nchan + c)];
+          const float leg_att = leg_attenuation(a, len);
+          s = os;
+          d = od;
+          L.weight[lane] = r == kReflected ? L.weight[lane] * leg_att : (L.weight[lane] * leg_att) * gain;
+        }
+        L.count[lane] = cnt + (r == kReflected ? 0x10001u : 1u);
+        L.state[lane] = bidir_next(w0, r, gl, l, gi, back, lenses.count);
+      }
+    }
+    st = (L.state[lane] >> 8) & 7u;
+    seg = L.count[lane];
+    wgt = L.weight[lane];
+    if (traced && job.bounces) job.bounces[i] = seg >> 16;
+    seg &= 0xFFFFu;
+    if (traced) {
+      job.opl[i] = L.opl[lane];
+      if (job.glass) job.glass[i] = L.glass[lane];
+    }
+  } else if constexpr (has_tir(kMode)) {
     // The lens stays wave-uniform: per lens one INSIDE segment (b == 0), then up to 1 + max_bounces OUTSIDE segments
     // over the lanes still inside it (`pend`); lanes that left the lens wait, and a wave vote ends the lens's
     // segments when none is pending.  The last OUTSIDE segment may not reflect, so no lane leaves the loop pending.
@@ -2908,9 +3080,10 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
                                                        const float *opl_in, float *out_opl, float *out_glass,
                                                        const float *__restrict__ gap_table,
                                                        const float *__restrict__ glass_absorb,
-                                                       const float *__restrict__ gap_absorb, uint64_t ghost_at) {
+                                                       const float *__restrict__ gap_absorb, uint64_t ghost_at,
+                                                       float axis_x, float axis_y, float axis_z) {
   constexpr bool kPower = kScan != 0, kSpectral = kScan >= 2, kTir = kScan >= 3, kOpl = kScan >= 4, kMedia = kScan >= 5;
-  constexpr bool kAbsorb = kScan >= 6, kGhost = kScan == 7;
+  constexpr bool kAbsorb = kScan >= 6, kGhost = kScan == 7, kBidir = kScan == 8;
   uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   f3 s, d;
@@ -2928,6 +3101,38 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
   float opl = 0.0f, glass = 0.0f;
   if constexpr (kOpl) opl = opl_in ? opl_in[i] : 0.0f;
   bool alive = true;
+  if constexpr (kBidir) {
+    // the walk per lane, event by event (bidir_open's word in a register); max_bounces is the budget of the whole path
+    uint32_t w = bidir_open(0u, true, lenses.count);
+    while (w & kBidirTravels) {
+      const uint32_t l = (w & 15u) >> 1;
+      const bool gl = (w & 1u) != 0u;
+      uint32_t patch;
+      Hit h = mesh_intersect_scan(lenses.lens[l], s, d, patch);
+      const float ri = ri_table[l * nchan + ch];
+      const bool back = bidir_back(h.normal, mk(axis_x, axis_y, axis_z));
+      const uint32_t gi = gl ? (back ? l + 1u : l) : ((w & kBidirFwd) ? l : l + 1u);
+      const float ng = gap_table[gi * nchan + ch];
+      f3 os, od;
+      float gain = 1.0f;
+      uint32_t r = bidir_eta_t<true>(h, div_rn(gl ? ri : ng, gl ? ng : ri), s, d, gl ? BZR_RR_OUTSIDE : BZR_RR_INSIDE,
+                                     in_table && bounces < max_bounces, true, ghost_uniform(ghost_at, i, 256u + seg), os,
+                                     od, gain);
+      if (!in_table) r = BZR_RR_NONE;
+      ++seg;
+      if (r != BZR_RR_NONE) {
+        const float len = opl_leg_absorb(s, os, gl ? ri : ng, gl, opl, glass);
+        const float att_leg = leg_attenuation(gl ? glass_absorb[l * nchan + ch] : gap_absorb[gi * nchan + ch], len);
+        s = os;
+        d = od;
+        wgt = r == kReflected ? wgt * att_leg : (wgt * att_leg) * gain;
+        if (r == kReflected) ++bounces;
+      }
+      w = bidir_next(w, r, gl, l, gi, back, lenses.count);
+    }
+    st = (w >> 8) & 7u;
+    alive = false;
+  }
   for (uint32_t l = 0; l < lenses.count && alive; ++l) {
     // kTir: j counts the lens's segments -- INSIDE, then OUTSIDE while the ray reflects (the last may not)
     for (uint32_t j = 0; j < (kTir ? max_bounces + 2u : 2u) && alive; ++j) {
@@ -4079,7 +4284,8 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
                               const uint8_t *channel = nullptr, uint32_t nchan = 0, uint32_t max_bounces = 0,
                               uint32_t *out_bounces = nullptr, const float *opl_in = nullptr, float *out_opl = nullptr,
                               float *out_glass = nullptr, const float *gap = nullptr, const float *glass_abs = nullptr,
-                              const float *gap_abs = nullptr, uint64_t ghost_seed = 0, uint64_t first_ray = 0) {
+                              const float *gap_abs = nullptr, uint64_t ghost_seed = 0, uint64_t first_ray = 0,
+                              const float *axis = nullptr) {
   constexpr bool kPower = has_power(kMode), kSpectral = has_channels(kMode), kTir = has_tir(kMode);
   constexpr bool kOpl = has_opl(kMode), kMedia = has_media(kMode), kAbsorb = has_absorb(kMode);
   if (bzr_status s = check_flags(flags, true)) return s;
@@ -4120,7 +4326,8 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     if (bzr_status s = upload_absorb_table(ctx, glass_abs, nlens, nchan, kGlassAbsorbAt, ctx->glass_absorb_host)) return s;
     if (bzr_status s = upload_absorb_table(ctx, gap_abs, nlens, nchan, kGapAbsorbAt, ctx->gap_absorb_host)) return s;
   }
-  const bool staged = !use_scan(flags) && use_staged(flags, n, max_patches(set));
+  // (kModeBidir has no staged form: its entry point has refused the explicit flag, the automatic choice is fused)
+  const bool staged = !has_bidir(kMode) && !use_scan(flags) && use_staged(flags, n, max_patches(set));
   float *r = nullptr, *tmp = nullptr;  // tmp, host + AoS: the records on the device, in and out
   uint8_t *c = nullptr;
   // kModeTir: the staged chain's pending row (one word per ray) and a host caller's bounce row, behind the rest
@@ -4154,11 +4361,12 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
   }
   if (use_scan(flags)) {
     launch(ctx, BZR_KERNEL_CHAIN_SCAN,
-           k_chain_scan<has_ghost(kMode) ? 7 : kAbsorb ? 6 : kMedia ? 5 : kOpl ? 4 : (kTir ? 3 : (kSpectral ? 2 : (kPower ? 1 : 0)))>,
+           k_chain_scan<has_bidir(kMode) ? 8 : has_ghost(kMode) ? 7 : kAbsorb ? 6 : kMedia ? 5 : kOpl ? 4 : (kTir ? 3 : (kSpectral ? 2 : (kPower ? 1 : 0)))>,
            dim3(grid_for(n)), set, d_rays, n, d_out, d_st, d_seg, d_win, d_w, d_ch, (const float *)ctx->ri_table, nchan, d_bnc,
            max_bounces, d_oin, d_opl, d_glass, kMedia ? (const float *)ctx->ri_table + kRiTableFloats : nullptr,
            kAbsorb ? (const float *)ctx->ri_table + kGlassAbsorbAt : nullptr,
-           kAbsorb ? (const float *)ctx->ri_table + kGapAbsorbAt : nullptr, ghost_base(ghost_seed, first_ray));
+           kAbsorb ? (const float *)ctx->ri_table + kGapAbsorbAt : nullptr, ghost_base(ghost_seed, first_ray),
+           axis ? axis[0] : 0.0f, axis ? axis[1] : 0.0f, axis ? axis[2] : 0.0f);
     BZR_HIP(hipGetLastError());
   } else {
     TraceJob job{};
@@ -4179,11 +4387,18 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     job.glass = d_glass;
     job.gap_table = kMedia ? ctx->ri_table + kRiTableFloats : nullptr;
     job.ghost_base = ghost_base(ghost_seed, first_ray);
+    if constexpr (has_bidir(kMode)) {
+      job.axis_xy[0] = axis[0];
+      job.axis_xy[1] = axis[1];
+      job.axis_z = axis[2];
+      if (bzr_status s = run_fused<kMode>(ctx, set, job, flags)) return s;
+    } else {
     Work w;
     const uint32_t ch = staged ? chunk_for(ctx, n) : 0u;
     if (staged)
       if (bzr_status s = ensure_work(ctx, ch, max_patches(set), w)) return s;
     if (bzr_status s = run_chain<kMode>(ctx, set, job, flags, staged, d_pend, ch, w)) return s;
+    }
   }
   if (bzr_status s = rays_out(ctx, d_out, out_rays, n, host, aos, tmp)) return s;
   if (host) {
@@ -4295,6 +4510,42 @@ extern "C" bzr_status bzr_trace_chain_ghost(bzr_ctx *ctx, const bzr_mesh *const 
   return trace_chain<kModeGhost>(ctx, lenses, ri_table, nlens, rays, weight_in, n, out_rays, out_weight, out_status,
                                  out_segments, flags, channel, nchan, max_bounces, out_bounces, opl_in, out_opl, out_glass,
                                  gap_table, glass_absorb, gap_absorb, ghost_seed, first_ray);
+}
+
+// The chain's forward axis: finite and not zero (only the sign of one dot product with it is used).
+static bzr_status check_axis(const float *axis) {
+  if (!axis) return set_error(BZR_ERR_INVALID_ARGUMENT, "null axis");
+  if (!std::isfinite(axis[0]) || !std::isfinite(axis[1]) || !std::isfinite(axis[2]) ||
+      (axis[0] == 0.0f && axis[1] == 0.0f && axis[2] == 0.0f))
+    return set_error(BZR_ERR_INVALID_ARGUMENT, "axis must be finite and not zero");
+  return BZR_OK;
+}
+static bzr_status check_bidir_flags(uint32_t flags) {
+  if (flags & BZR_PIPELINE_STAGED)
+    return set_error(BZR_ERR_INVALID_ARGUMENT, "the bidirectional chain has no staged pipeline: fused, or BZR_ACCEL_NONE");
+  return BZR_OK;
+}
+
+extern "C" bzr_status bzr_trace_chain_bidir(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                            const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                            uint32_t nlens, uint32_t nchan, const float *rays, const uint8_t *channel,
+                                            const float *weight_in, const float *opl_in, uint32_t n,
+                                            uint32_t max_bounces, uint64_t ghost_seed, uint64_t first_ray,
+                                            const float axis[3], float *out_rays, float *out_weight,
+                                            uint32_t *out_status, uint32_t *out_segments, uint32_t *out_bounces,
+                                            float *out_opl, float *out_glass, uint32_t flags) {
+  // (bzr_trace_chain_ghost's checks, in its order, then the walk's own)
+  if (!out_opl) return set_error(BZR_ERR_INVALID_ARGUMENT, "null out_opl");
+  if (max_bounces > BZR_MAX_BOUNCES) return set_error(BZR_ERR_INVALID_ARGUMENT, "max_bounces must be 0..8");
+  if (nlens >= 1 && nlens <= kMaxLenses && nchan >= 1 && nchan <= kMaxChannels) {
+    if (bzr_status s = check_absorb_table(glass_absorb, nlens, nchan, "glass_absorb entries must be finite and >= 0")) return s;
+    if (bzr_status s = check_absorb_table(gap_absorb, nlens, nchan, "gap_absorb entries must be finite and >= 0")) return s;
+  }
+  if (bzr_status s = check_axis(axis)) return s;
+  if (bzr_status s = check_bidir_flags(flags)) return s;
+  return trace_chain<kModeBidir>(ctx, lenses, ri_table, nlens, rays, weight_in, n, out_rays, out_weight, out_status,
+                                 out_segments, flags, channel, nchan, max_bounces, out_bounces, opl_in, out_opl, out_glass,
+                                 gap_table, glass_absorb, gap_absorb, ghost_seed, first_ray, axis);
 }
 
 // ------------------------------------------------------------ test hook: normalized()
@@ -4801,6 +5052,30 @@ __global__ __launch_bounds__(kBlock) void k_land_tir(bzr_target tg, float4 plane
   keyed_rows<BZR_LEDGER_FIELDS, BZR_LEDGER_FIELDS>(traced, ch * BZR_LEDGER_ROWS + row, in, q, t.count, t.power);
 }
 
+// bzr_illuminate_bidir's BACK rays: every traced ray of channel c whose status is BZR_RR_BACK adds one count and q(w) to
+// row c * BZR_LEDGER_ROWS + min(bounces, BZR_MAX_BOUNCES) of the two back rows (keyed_rows, one counter per key).
+// k_land_tir and k_land_far see such a ray as neither lost nor exited: it is in no ledger field, lands and bins nowhere.
+__global__ __launch_bounds__(kBlock) void k_back_rows(uint32_t n, const uint32_t *__restrict__ status,
+                                                      const uint32_t *__restrict__ segments,
+                                                      const uint32_t *__restrict__ bounces,
+                                                      const float *__restrict__ weight,
+                                                      const uint8_t *__restrict__ channel,
+                                                      unsigned long long *__restrict__ count,
+                                                      unsigned long long *__restrict__ power) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  bool back = false;
+  unsigned long long q = 0ull;
+  uint32_t key = 0u;
+  if (i < n && segments[i] != 0u && status[i] == BZR_RR_BACK) {
+    back = true;
+    q = power_q32(weight[i]);
+    const uint32_t b = bounces[i];
+    key = channel[i] * BZR_LEDGER_ROWS + (b < BZR_MAX_BOUNCES ? b : uint32_t(BZR_MAX_BOUNCES));
+  }
+  const bool in[1] = {true};
+  keyed_rows<1, 1>(back, key, in, q, count, power);
+}
+
 // The far-field landing kernel (bzr_farfield_bin, bzr_illuminate_farfield): one thread per ray, binned by direction
 // (emitter.hpp farfield_cell).  A ray is seen when `status` is null or its status is OUTSIDE, and its channel (0
 // without `channel`) is below nchan; a seen ray that is binned adds q(w) (w = 1 without `weight`) to flux[key] and one
@@ -4998,6 +5273,11 @@ struct IllumTir {
   // bzr_illuminate_ghost: the chain is kModeGhost's; ray j of the emitter draws for ray number j
   bool ghost = false;
   uint64_t ghost_seed = 0;
+  // bzr_illuminate_bidir: the chain is kModeBidir's (fused only) with ghost_seed and this axis; the BACK rays' two rows
+  // [nchan][BZR_LEDGER_ROWS], host memory, each may be null
+  bool bidir = false;
+  float axis[3] = {0.0f, 0.0f, 0.0f};
+  uint64_t *back_count = nullptr, *back_power = nullptr;
 };
 static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
                              const bzr_emitter *em, uint64_t total_rays, const bzr_target *tg, const bzr_radiometry *rad,
@@ -5089,7 +5369,10 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
   // the stray-light maps of a host caller.  media: the chain's optical path row between the two, under the same
   // memset -- scratch that nothing returns (no glass row: the chain's is optional)
   const size_t ledger = (size_t)BZR_LEDGER_ROWS * BZR_LEDGER_FIELDS * NC;
-  const bool staged = use_staged(flags, B, nb);
+  const bool bidir = tir && tir->bidir;
+  const bool staged = !bidir && use_staged(flags, B, nb);  // (the bidirectional chain is fused only)
+  const size_t back_rows = (size_t)BZR_LEDGER_ROWS * NC;
+  unsigned long long *d_bcount = nullptr, *d_bpower = nullptr;
   uint32_t *d_bnc = nullptr, *d_pend = nullptr, *d_rhist = tir ? tir->rhist : nullptr;
   float *d_opl = nullptr;
   unsigned long long *d_rflux = tir ? reinterpret_cast<unsigned long long *>(tir->rflux) : nullptr;
@@ -5111,6 +5394,7 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
         if (media) st.take(d_opl, B);
         if (tir && staged) st.take(d_pend, B);
         if (tir) st.take(d_lcount, ledger), st.take(d_lpower, ledger);
+        if (bidir) st.take(d_bcount, back_rows), st.take(d_bpower, back_rows);
         if (tir && host && tir->rflux) st.take(d_rflux, maps);
         if (tir && host && tir->rhist) st.take(d_rhist, maps);
         if (far) st.take(d_fstats, 2 * NC), st.take(d_fpower, 2 * NC);
@@ -5138,6 +5422,10 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
     BZR_HIP(hipMemsetAsync(d_lpower, 0, ledger * 8, ctx->stream));
     if (host && tir->rflux) BZR_HIP(hipMemsetAsync(d_rflux, 0, maps * 8, ctx->stream));
     if (host && tir->rhist) BZR_HIP(hipMemsetAsync(d_rhist, 0, maps * 4, ctx->stream));
+  }
+  if (bidir) {
+    BZR_HIP(hipMemsetAsync(d_bcount, 0, back_rows * 8, ctx->stream));
+    BZR_HIP(hipMemsetAsync(d_bpower, 0, back_rows * 8, ctx->stream));
   }
   // The in-place job has alive_in set, so the chain has no first stage: nothing in it writes a culled ray's bounce
   // word (either pipeline) or pending word (staged), and a staged bounce stage traces every ray whose pending word is
@@ -5188,7 +5476,16 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
     if (tir && tir->ghost) {
       job.ghost_base = ghost_base(tir->ghost_seed, first);
     }
-    if (bzr_status s = chain(ctx, set, job, flags, staged, d_pend, B, w)) return s;
+    if (bidir) {
+      job.ghost_base = ghost_base(tir->ghost_seed, first);
+      job.axis_xy[0] = tir->axis[0];
+      job.axis_xy[1] = tir->axis[1];
+      job.axis_z = tir->axis[2];
+      if (bzr_status s = run_fused<kModeBidir>(ctx, set, job, flags)) return s;
+      hipLaunchKernelGGL(k_back_rows, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, m, (const uint32_t *)d_st,
+                         (const uint32_t *)d_seg, (const uint32_t *)d_bnc, (const float *)d_w, (const uint8_t *)d_ch,
+                         d_bcount, d_bpower);
+    } else if (bzr_status s = chain(ctx, set, job, flags, staged, d_pend, B, w)) return s;
     if (tir)
       hipLaunchKernelGGL(k_land_tir, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, *tg,
                          make_float4(pn.x, pn.y, pn.z, pc), cell_u, cell_v, d_rays, B, m, d_st, d_hist, d_stats, d_w, d_flux,
@@ -5233,7 +5530,16 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
     if (!hrf.empty()) BZR_HIP(hipMemcpyAsync(hrf.data(), d_rflux, maps * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (!hrh.empty()) BZR_HIP(hipMemcpyAsync(hrh.data(), d_rhist, maps * 4, hipMemcpyDeviceToHost, ctx->stream));
   }
+  std::vector<unsigned long long> hb(bidir ? 2 * back_rows : 0);
+  if (bidir) {
+    BZR_HIP(hipMemcpyAsync(hb.data(), d_bcount, back_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+    BZR_HIP(hipMemcpyAsync(hb.data() + back_rows, d_bpower, back_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
   BZR_HIP(hipStreamSynchronize(ctx->stream));
+  if (bidir && tir->back_count)
+    for (size_t k = 0; k < back_rows; ++k) tir->back_count[k] = hb[k];
+  if (bidir && tir->back_power)
+    for (size_t k = 0; k < back_rows; ++k) tir->back_power[k] = hb[back_rows + k];
   for (size_t k = 0; k < hrf.size(); ++k) tir->rflux[k] += hrf[k];
   for (size_t k = 0; k < hrh.size(); ++k) tir->rhist[k] += hrh[k];
   if (tir && tir->count)
@@ -5361,6 +5667,44 @@ extern "C" bzr_status bzr_illuminate_ghost(bzr_ctx *ctx, const bzr_mesh *const *
   tir.far = far ? &ifar : nullptr;
   tir.ghost = true;
   tir.ghost_seed = ghost_seed;
+  return illuminate(ctx, lenses, ri_table, nlens, em, total_rays, tg, rad, flux_q32, hist, stats, power_q32, flags, true,
+                    nchan, &tir);
+}
+
+// bzr_illuminate_ghost over the bidirectional chain, with the BACK rays' two rows.
+extern "C" bzr_status bzr_illuminate_bidir(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                           const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                           uint32_t nlens, uint32_t nchan, const bzr_emitter *em, uint64_t total_rays,
+                                           const bzr_target *tg, const bzr_radiometry *rad, uint32_t max_bounces,
+                                           uint64_t ghost_seed, const float axis[3], uint64_t *flux_q32, uint32_t *hist,
+                                           uint64_t *reflected_flux_q32, uint32_t *reflected_hist, uint64_t *stats,
+                                           uint64_t *power_q32, uint64_t *ledger_count, uint64_t *ledger_power_q32,
+                                           uint64_t *back_count, uint64_t *back_power_q32, uint32_t flags,
+                                           const bzr_farfield *far, uint64_t *far_flux_q32, uint32_t *far_hist,
+                                           uint64_t *far_reflected_flux_q32, uint64_t *far_stats,
+                                           uint64_t *far_power_q32) {
+  if (!rad) return set_error(BZR_ERR_INVALID_ARGUMENT, "null radiometry");
+  if (!far && (far_flux_q32 || far_hist || far_reflected_flux_q32 || far_stats || far_power_q32))
+    return set_error(BZR_ERR_INVALID_ARGUMENT, "far outputs given without a far-field frame");
+  if (!far && !tg) return set_error(BZR_ERR_INVALID_ARGUMENT, "neither a target nor a far-field frame");
+  if (bzr_status s = check_axis(axis)) return s;
+  if (bzr_status s = check_bidir_flags(flags)) return s;
+  if (far) {
+    FarFrame checked{};
+    if (bzr_status s = far_frame(far, nchan, checked)) return s;
+  }
+  const IllumFar ifar{far, far_flux_q32, far_hist, far_reflected_flux_q32, far_stats, far_power_q32};
+  IllumTir tir{max_bounces, reflected_flux_q32, reflected_hist, ledger_count, ledger_power_q32};
+  tir.media = true;
+  tir.gap = gap_table;
+  tir.glass_absorb = glass_absorb;
+  tir.gap_absorb = gap_absorb;
+  tir.far = far ? &ifar : nullptr;
+  tir.ghost_seed = ghost_seed;
+  tir.bidir = true;
+  tir.axis[0] = axis[0], tir.axis[1] = axis[1], tir.axis[2] = axis[2];
+  tir.back_count = back_count;
+  tir.back_power = back_power_q32;
   return illuminate(ctx, lenses, ri_table, nlens, em, total_rays, tg, rad, flux_q32, hist, stats, power_q32, flags, true,
                     nchan, &tir);
 }

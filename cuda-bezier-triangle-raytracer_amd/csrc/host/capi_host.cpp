@@ -285,6 +285,17 @@ bzr_status bzr_ghost_uniform(uint64_t seed, uint64_t ray, uint32_t lens, uint32_
   return BZR_OK;
 }
 
+// The bidirectional walk's draw (include/bzr.h bzr_trace_chain_bidir): the same function at e = 256 + segment.
+bzr_status bzr_bidir_uniform(uint64_t seed, uint64_t ray, uint32_t segment, float *u) {
+  if (!u) return bad("null u");
+  if (segment > (BZR_MAX_BOUNCES + 1u) * (2u * 8u + 1u)) return bad("segment must be 0..153");
+  const uint64_t e = 256u + segment;
+  const uint64_t r = mix64((seed ^ 0x5851F42D4C957F2Dull) + 0x9E3779B97F4A7C15ull * (ray + 1ull));
+  const uint64_t h = mix64(r + 0x9E3779B97F4A7C15ull * (e + 1ull));
+  *u = static_cast<float>(static_cast<uint32_t>(h >> 40)) * 0x1p-24f;
+  return BZR_OK;
+}
+
 // ---- far field (include/bzr.h bzr_farfield) ----
 // The frame's checks and what every user derives from it, stated once: the pole n = axis_u x axis_v normalised as
 // illuminate() normalises the target's normal, S = R + R and the cell sizes.  out[13]: n, axis_u, axis_v, R, S, cu,

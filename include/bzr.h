@@ -105,6 +105,8 @@ enum {
 enum { BZR_WHAT_FOLLOW0 = 0, BZR_WHAT_FOLLOW1 = 1, BZR_WHAT_FOLLOW2 = 2, BZR_WHAT_NONE = 3, BZR_WHAT_INTERSECT = 4 };
 enum { BZR_LIMIT_THIS = 0, BZR_LIMIT_NONE = 1 };                       /* BezierTriangle::LimitPlaneIntersection */
 enum { BZR_RR_NONE = 0, BZR_RR_INSIDE = 1, BZR_RR_OUTSIDE = 2 };       /* RefractionResult */
+/* bzr_trace_chain_bidir alone: the ray left the chain in front of its first lens.  (3 is kept free.) */
+enum { BZR_RR_BACK = 4 };
 enum { BZR_HIT_FIELDS = 13, BZR_RAY_FIELDS = 6 };
 
 /* One cubic Bezier patch, byte-identical to the reference's BezierTriangle
@@ -422,6 +424,68 @@ bzr_status bzr_trace_chain_ghost(bzr_ctx *ctx, const bzr_mesh *const *lenses, co
 /* The draw's host twin (no context, no device): *u = G(seed, ray, 16 lens + reflections).  lens above 7 or reflections
  * above 8, or a NULL u, return BZR_ERR_INVALID_ARGUMENT with nothing written. */
 bzr_status bzr_ghost_uniform(uint64_t seed, uint64_t ray, uint32_t lens, uint32_t reflections, float *u);
+/* ---- the bidirectional chain: front-surface reflections and ghosts between lenses ----
+ * bzr_trace_chain_ghost's arguments with `axis` behind first_ray: the chain's forward direction.  Only the sign of one
+ * dot product with it is used.  A zero or non-finite axis returns BZR_ERR_INVALID_ARGUMENT before any output is touched.
+ * Every other chain call sends a ray that leaves lens l to lens l + 1.  Here a ray goes to the neighbour that the
+ * surface it left faces, the roulette runs at every surface, and max_bounces (<= BZR_MAX_BOUNCES) is the ray's budget of
+ * reflections for its whole path, not per lens.
+ * Per-ray state: g in [0, nlens], the gap the ray is in (gap g is gap_table[g], in front of lens g); fwd: a ray in the
+ * open heads for lens g when fwd, else for lens g - 1; k, the reflections so far on the whole path; q, the segments so
+ * far.  Start: g = 0, fwd, k = q = 0.  c is the ray's channel; a channel outside the table ends the ray NONE in its
+ * first segment, as before.  The walk is a loop over events:
+ *   fwd && g == nlens: the ray ends, status BZR_RR_OUTSIDE.   !fwd && g == 0: it ends, status BZR_RR_BACK (4).
+ *   Open segment.  Lens l = fwd ? g : g - 1, expected INSIDE; eta = gap_table[g][c] / ri_table[l][c], one correctly
+ *     rounded division; q += 1.  The step applies where the winning hit is an intersection with cs < 0;
+ *     s2 = eta^2 (1 - cs^2).
+ *       s2 >= 1 with k < max_bounces: the mirror step of bzr_trace_chain_tir bit for bit (k2 = 2 cs, r = d - n k2 per
+ *         component, normalised, origin at the hit's point); k += 1, fwd = !fwd, the weight gets the leg's A alone.
+ *         With the budget spent the ray ends NONE.
+ *       0.99 <= s2 < 1, a NaN, a miss, a hit with cs >= 0: NONE, as in every chain.
+ *       s2 < 0.99 with k < max_bounces: T = fresnel_t(eta, cs, s2), u = G(ghost_seed, j, 256 + q - 1), G being
+ *         bzr_trace_chain_ghost's function (the offset 256 keeps these draws off that call's e <= 135).
+ *         u >= T: mirrored as above, k += 1, fwd = !fwd, w = w A.   u < T: refracted into lens l, w = w A (no T).
+ *       s2 < 0.99 with the budget spent: refracted in with w = (w A) T, bzr_trace_chain_absorb's step.
+ *     The leg lies in gap g: m = gap_table[g][c] len goes into out_opl, and A comes from gap_absorb[g][c].  Every such
+ *     leg has g <= nlens - 1, so gap_absorb needs no row of its own for the space behind the last lens: a ray is in gap
+ *     nlens only after it left lens nlens - 1 through a surface that faces forward, which sets fwd, and such a ray ends
+ *     OUTSIDE before its next segment; a reflection in the open flips fwd but keeps g, and happens only in a gap with
+ *     an open segment.
+ *   Glass segment.  The ray is inside lens l, expected OUTSIDE; q += 1.  The step applies on an intersection with
+ *     cs >= 0.  The side rule: back = n0 a0 + (n1 a1 + n2 a2) >= 0 with n the hit's normal and a the axis, in binary32
+ *     without contraction (exact under BZR_MODE_FAST too); g' = back ? l + 1 : l.  eta = ri_table[l][c] /
+ *     gap_table[g'][c]: the medium behind the surface the ray actually meets decides eta, s2, total reflection and T.
+ *       s2 >= 1 with k < max_bounces: total reflection; the ray stays in lens l, k += 1, w = w A.
+ *       s2 < 0.99 with k < max_bounces: the roulette of bzr_trace_chain_ghost with the draw G(ghost_seed, j, 256 + q - 1):
+ *         u >= T reflects (k += 1, w = w A, the same lens again), u < T refracts out with w = w A.
+ *       s2 < 0.99 with the budget spent: refracted out with w = (w A) T.   Everything else: NONE.
+ *     After refracting out g = g', fwd = back.  The leg is a glass leg: len into out_glass, ri_table[l][c] len into
+ *     out_opl, A from glass_absorb[l][c].
+ * Outputs: out_status is NONE, OUTSIDE or BACK; out_rays_soa the ray after its last successful refraction or reflection
+ * (the input ray if there was none); out_segments = q, out_bounces = k, out_opl and out_glass as the legs define them.
+ * Termination: between two reflections a ray crosses each surface of the chain at most once in one direction, at most
+ * 2 nlens segments, and one more ends in the reflection or the end; with at most max_bounces reflections
+ * q <= (max_bounces + 1)(2 nlens + 1), 153 at the most.
+ * Consequences.  A ray that ends with k < max_bounces under zero absorption tables has out_weight == weight_in bit for
+ * bit: no step multiplied T in and every A was exactly 1.  A ray's results depend on nothing but its own inputs and
+ * (ghost_seed, j): not on the pipeline, on the split of a call (first_ray moved along) or on which rays share its wave.
+ * max_bounces = 0 is bzr_trace_chain_absorb bit for bit on every ray for which every surface it met from inside glass
+ * faced forward (back true each time: the side rule then names the gap the forward chain assumes).
+ * Limits.  The walk is ordered by neighbours: a ray that misses its neighbour lens is NONE even where a lens further
+ * on would have met it; it is not a nearest-of-all-lenses search.  There is no staged pipeline: an explicit
+ * BZR_PIPELINE_STAGED returns BZR_ERR_INVALID_ARGUMENT, the automatic choice is fused, BZR_ACCEL_NONE is the brute-force
+ * scan.  The other argument checks are bzr_trace_chain_ghost's. */
+bzr_status bzr_trace_chain_bidir(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                 const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                 uint32_t nlens, uint32_t nchan, const float *rays_soa, const uint8_t *channel,
+                                 const float *weight_in, const float *opl_in, uint32_t n, uint32_t max_bounces,
+                                 uint64_t ghost_seed, uint64_t first_ray, const float axis[3],
+                                 float *out_rays_soa, float *out_weight, uint32_t *out_status, uint32_t *out_segments,
+                                 uint32_t *out_bounces, float *out_opl, float *out_glass, uint32_t flags);
+/* The walk's draw on the host (no context, no device): *u = G(seed, ray, 256 + segment), segment = q - 1 counting from
+ * 0.  A segment above the bound (BZR_MAX_BOUNCES + 1)(2 * 8 + 1) = 153, or a NULL u, return BZR_ERR_INVALID_ARGUMENT
+ * with nothing written. */
+bzr_status bzr_bidir_uniform(uint64_t seed, uint64_t ray, uint32_t segment, float *u);
 /* Absorption coefficients from a glass catalogue's internal transmittance, on the host (no context, no device):
  * out_a[i] = -ln(internal_transmittance[i]) / thickness, evaluated in binary64 and rounded once to float, per unit of
  * the length `thickness` is given in.  A transmittance outside (0, 1], a thickness that is not finite and positive or
@@ -748,6 +812,26 @@ bzr_status bzr_illuminate_ghost(bzr_ctx *ctx, const bzr_mesh *const *lenses, con
                                 uint64_t *reflected_flux_q32, uint32_t *reflected_hist,
                                 uint64_t *stats, uint64_t *power_q32,
                                 uint64_t *ledger_count, uint64_t *ledger_power_q32, uint32_t flags,
+                                const bzr_farfield *far, uint64_t *far_flux_q32, uint32_t *far_hist,
+                                uint64_t *far_reflected_flux_q32, uint64_t *far_stats, uint64_t *far_power_q32);
+/* bzr_illuminate_ghost over the chain of bzr_trace_chain_bidir: `axis` follows ghost_seed (checked as there), and two
+ * host outputs follow the ledger: back_count and back_power_q32, each [nchan][BZR_LEDGER_ROWS], each may be NULL, both
+ * overwritten.  A ray that ends BZR_RR_BACK is counted in row min(bounces, BZR_MAX_BOUNCES) of its channel, with q(w)
+ * summed beside it; it is in no ledger field, does not land, is not binned in the far field and is not in
+ * stats[EXITED].  OUTSIDE rays land and are binned as in bzr_illuminate_ghost.  Per channel
+ *   sum over rows (LOST + EXITED) + sum over rows BACK = EMITTED - CULLED.
+ * With rad->surface == BZR_SURFACE_LOSSLESS no draw is taken, and the call is bzr_illuminate_farfield bit for bit
+ * wherever the side rule sends no ray backward (the back rows are then zero).  The chain is fused: an explicit
+ * BZR_PIPELINE_STAGED returns BZR_ERR_INVALID_ARGUMENT. */
+bzr_status bzr_illuminate_bidir(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                uint32_t nlens, uint32_t nchan, const bzr_emitter *em, uint64_t total_rays,
+                                const bzr_target *target, const bzr_radiometry *rad, uint32_t max_bounces,
+                                uint64_t ghost_seed, const float axis[3], uint64_t *flux_q32, uint32_t *hist,
+                                uint64_t *reflected_flux_q32, uint32_t *reflected_hist,
+                                uint64_t *stats, uint64_t *power_q32,
+                                uint64_t *ledger_count, uint64_t *ledger_power_q32,
+                                uint64_t *back_count, uint64_t *back_power_q32, uint32_t flags,
                                 const bzr_farfield *far, uint64_t *far_flux_q32, uint32_t *far_hist,
                                 uint64_t *far_reflected_flux_q32, uint64_t *far_stats, uint64_t *far_power_q32);
 /* Host helpers (no device).  bzr_farfield_cell: the cell rule above on the host, the device's twin: *cell is the

@@ -503,6 +503,17 @@ void traceChainGhost(std::vector<BezierLens const *> const &lenses, std::vector<
                      float const *opl, std::size_t n, uint32_t maxBounces, uint64_t ghostSeed, uint64_t firstRay,
                      Ray *outRays, float *outWeights, RefractionResult *outStatus, float *outOpl, float *outGlass = nullptr,
                      uint32_t *outSegments = nullptr, uint32_t *outBounces = nullptr, Context *ctx = nullptr);
+// The bidirectional chain (bzr_trace_chain_bidir): traceChainGhost's arguments with the chain's forward axis behind
+// firstRay.  The roulette runs at every surface and a ray goes on to the neighbour lens the surface it left faces; it
+// ends cOutside, cNone, or with the status word BZR_RR_BACK (4) in front of the first lens.  maxBounces is the budget of
+// the whole path.  Throws what traceChainGhost throws, and for a zero or non-finite axis.
+void traceChainBidir(std::vector<BezierLens const *> const &lenses, std::vector<float> const &riTable,
+                     std::vector<float> const &gapTable, std::vector<float> const &glassAbsorb,
+                     std::vector<float> const &gapAbsorb, Ray const *rays, uint8_t const *channels, float const *weights,
+                     float const *opl, std::size_t n, uint32_t maxBounces, uint64_t ghostSeed, uint64_t firstRay,
+                     float const (&axis)[3], Ray *outRays, float *outWeights, RefractionResult *outStatus, float *outOpl,
+                     float *outGlass = nullptr, uint32_t *outSegments = nullptr, uint32_t *outBounces = nullptr,
+                     Context *ctx = nullptr);
 // Bins a traced batch by direction into a far-field map (bzr_farfield_bin): rays [n] as the traceChain* calls return
 // them (only the directions are read), weights, status and channels [n] each may be null (1.0f; every ray is seen,
 // otherwise only cOutside rays; channel 0).  farFlux / farHist [nchan][bins_v][bins_u] accumulate (one may be null);

@@ -3,7 +3,7 @@
 on the cfg2 lens, emitter just behind it (inside the lens's bounding sphere, so nothing is culled and
 every ray is traced).  Prints one JSON line: emitted rays / s and the landed fraction.
 
-usage: bench_illum.py [total_rays] [--power] [--tir [max_bounces]] [--media] [--farfield] [--ghost]
+usage: bench_illum.py [total_rays] [--power] [--tir [max_bounces]] [--media] [--farfield] [--ghost] [--bidir]
 --power times bzr_illuminate_power (Lambert emitter, Fresnel surfaces: k_emit<true> -> chain with weights ->
 k_land<true>, 64-bit flux cells) beside bzr_illuminate on the same rays, alternating, and prints one more JSON line
 with both; the chain kernels' share comes from the context's event timing in a separate pass, the rest of a call is
@@ -40,7 +40,7 @@ from bzr_amd.configs import CONFIGS, build_lens  # noqa: E402
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--power", "--media", "--farfield", "--ghost")]
+    args = [a for a in sys.argv[1:] if a not in ("--power", "--media", "--farfield", "--ghost", "--bidir")]
     power, media, farfield = "--power" in sys.argv[1:], "--media" in sys.argv[1:], "--farfield" in sys.argv[1:]
     tir = None
     if "--tir" in args:
@@ -69,6 +69,8 @@ def main():
         bench_farfield(ctx, dm, tg, total)
     if "--ghost" in sys.argv[1:]:
         bench_ghost(ctx, dm, tg, total)
+    if "--bidir" in sys.argv[1:]:
+        bench_bidir(ctx, dm, tg, total)
     if not power:
         return
 
@@ -297,6 +299,52 @@ def bench_ghost(ctx, dm, tg, total, max_bounces=4, seed=2024):
                       "landed_power_fraction": {k: round(sum(p["landed"] for p in out[k][1]) /
                                                          max(sum(p["emitted"] for p in out[k][1]), 1), 5) for k in count},
                       "ledger_rows_lost_exited_landed": {k: v.tolist() for k, v in count.items()}}))
+
+
+def bench_bidir(ctx, dm, tg, total, max_bounces=4, seed=2024):
+    """--bidir: on bench_ghost's emitter, media and far-field frame, bzr_illuminate_ghost (the yardstick) and
+    bzr_illuminate_bidir at four reflections on the same emitted rays, alternating and rotated; one more JSON line."""
+    row1 = [1.3, 1.5, 1.8, 2.4]
+    gaps, glass, front = [[1.41, 1.333, 1.2, 1.0], [1.0] * 4], [[0.05, 0.7, 0.4, 200.0]], [[0.3, 0.02, 0.0, 0.1]]
+    em = bzr_amd.Emitter(origin=(8.0, -3.0, -1.5), edge_u=(0.0, 6.0, 0.0), edge_v=(0.0, 0.0, 3.0), parts_u=4, parts_v=4,
+                         points_per_part=1024, rays_per_point=1024, belts=16, seed=1)
+    far = bzr_amd.FarField(axis_u=(0.0, 1.0, 0.0), axis_v=(0.0, 0.0, 1.0), extent=bzr_amd.SQRT2, bins_u=256, bins_v=256)
+
+    def ghost(n):
+        return bzr_amd.illuminate_ghost(ctx, [dm], [row1], gaps, glass, front, em, n, tg, far, max_bounces=max_bounces,
+                                        ghost_seed=seed, mode=bzr_amd.PIPELINE_FUSED)[4:]
+
+    def bidir(n):
+        return bzr_amd.illuminate_bidir(ctx, [dm], [row1], gaps, glass, front, em, n, tg, far, max_bounces=max_bounces,
+                                        ghost_seed=seed, axis=(1.0, 0.0, 0.0))[4:]
+
+    calls = {"illuminate_ghost": ghost, "illuminate_bidir": bidir}
+    for call in calls.values():
+        call(1 << 20)  # warm-up
+    wall, out = {k: [] for k in calls}, {}
+    names = list(calls)
+    for r in range(6):  # alternating and rotated
+        for name in names[r % 2:] + names[:r % 2]:
+            t0 = time.perf_counter()
+            out[name] = calls[name](total)
+            wall[name].append(time.perf_counter() - t0)
+    med = {k: statistics.median(v) for k, v in wall.items()}
+    led = out["illuminate_bidir"][2]
+    emitted = sum(p["emitted"] for p in out["illuminate_bidir"][1])
+    traced = sum(s["emitted"] - s["culled"] for s in out["illuminate_bidir"][0])
+    print(json.dumps({"workload": "illuminate_bidir beside illuminate_ghost (fused), cfg2 lens, emitter at x=8 (no cull), "
+                                  "indices 1.3/1.5/1.8/2.4, 512^2 target, 256^2 far-field map",
+                      "rays": total, "max_bounces": max_bounces, "ghost_seed": seed,
+                      "seconds": {k: round(v, 4) for k, v in med.items()},
+                      "seconds_min_max": {k: [round(min(v), 4), round(max(v), 4)] for k, v in wall.items()},
+                      "bidir_over_ghost": round(med["illuminate_bidir"] / med["illuminate_ghost"], 4),
+                      "bidir_over_ghost_rounds": [round(x / y, 4) for x, y in
+                                                  zip(wall["illuminate_bidir"], wall["illuminate_ghost"])],
+                      "count_identity_holds": int(led["count"][:, :, :2].sum()) + int(led["back_count"].sum()) == traced,
+                      "back_rays_by_row": led["back_count"].sum(axis=0).tolist(),
+                      "back_power_fraction": round(int(led["back_power"].sum()) / max(emitted, 1), 5),
+                      "landed_power_fraction": {k: round(sum(p["landed"] for p in out[k][1]) /
+                                                         max(sum(p["emitted"] for p in out[k][1]), 1), 5) for k in calls}}))
 
 
 if __name__ == "__main__":
