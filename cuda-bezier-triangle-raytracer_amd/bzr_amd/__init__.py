@@ -92,6 +92,12 @@ _SIGS = {
     "bzr_bidir_uniform": [ctypes.c_uint64, ctypes.c_uint64, _U32, _P],
     "bzr_illuminate_bidir": [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, ctypes.c_uint64, _P, _P, _U32, ctypes.c_uint64, _P, _P,
                              _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P],
+    "bzr_trace_chain_coated": [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _U32, _U32, ctypes.c_uint64,
+                               ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32],
+    "bzr_illuminate_coated": [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, ctypes.c_uint64, _P, _P, _U32, ctypes.c_uint64, _P, _P,
+                              _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P],
+    "bzr_coat_transmittance": [_P, ctypes.c_float, _P],
+    "bzr_coating_reflectance": [ctypes.c_double, ctypes.c_double, _P, _P, _U32, ctypes.c_double, _P],
     "bzr_absorption_from_transmittance": [_P, _U32, ctypes.c_double, _P],
     "bzr_dispersion_index": [_I32, _P, _U32, _P, _U32, _P],
     "bzr_trace_tiled": [_P, _U32, _P, _P, _U32, _P, _U32, _U32, _P, _P, _P, _U32],
@@ -155,6 +161,7 @@ _SIGS = {
     "bzr_debug_chunk_cap": [_P, _U32, ctypes.POINTER(_U32)],
     "bzr_debug_fresnel": [_P, _P, _U32, _P],
     "bzr_debug_attenuation": [_P, _P, _U32, _P],
+    "bzr_debug_coat_transmittance": [_P, _P, _U32, _P],
     "bzr_debug_farfield_rounds": [_P, _I32],
 }
 # entry points added without an ABI bump: an explicitly chosen earlier build (BZR_LIBRARY) may lack them
@@ -164,7 +171,8 @@ _ADDED = ("bzr_trace_chain_power", "bzr_illuminate_power", "bzr_trace_chain_spec
           "bzr_illuminate_media", "bzr_debug_attenuation", "bzr_farfield_bin", "bzr_illuminate_farfield",
           "bzr_farfield_cell", "bzr_farfield_directions", "bzr_farfield_intensity", "bzr_debug_farfield_cells",
           "bzr_trace_chain_ghost", "bzr_ghost_uniform", "bzr_illuminate_ghost", "bzr_trace_chain_bidir",
-          "bzr_bidir_uniform", "bzr_illuminate_bidir")
+          "bzr_bidir_uniform", "bzr_illuminate_bidir", "bzr_trace_chain_coated", "bzr_illuminate_coated",
+          "bzr_coat_transmittance", "bzr_coating_reflectance")
 _RET = {"bzr_last_error": ctypes.c_char_p, "bzr_abi_version": _I32}
 
 _lib = None
@@ -770,6 +778,131 @@ def trace_chain_bidir(ctx: Context, lenses, ri_table, gap_table, glass_absorb, g
     return out_rays, out_weight, out_status, out_segments, out_bounces, out_opl, out_glass
 
 
+COAT_SAMPLES = 129  # BZR_COAT_SAMPLES: a row's reflectances at the gap-side cosines i / 128
+
+
+class _CoatingC(ctypes.Structure):
+    """bzr_coating"""
+    _fields_ = [("table", _P), ("mask", _U32)]
+
+
+class Coating:
+    """bzr_coating: tabulated reflectances of coated surfaces.  Coating(table, mask) takes the table
+    [2 nlens, nchan, COAT_SAMPLES] float32 (surface 2 l + side: side 0 the front of lens l, 1 its back) and the mask,
+    bit 2 l + side per coated surface; Coating({(lens, side): rows [nchan, COAT_SAMPLES], ...}, nlens=) builds both
+    from the coated surfaces alone (bzr.h bzr_coating)."""
+
+    def __init__(self, table, mask=None, nlens=None):
+        if isinstance(table, dict):
+            if nlens is None:
+                raise BzrError("Coating from a dict needs nlens")
+            rows = {k: np.ascontiguousarray(v, np.float32) for k, v in table.items()}
+            shapes = {r.shape for r in rows.values()}
+            if len(shapes) > 1 or any(len(sh) != 2 or sh[1] != COAT_SAMPLES for sh in shapes):
+                raise BzrError(f"every surface's rows must be [nchan, {COAT_SAMPLES}] of one nchan")
+            nchan = shapes.pop()[0] if shapes else 1
+            self.table = np.zeros((2 * int(nlens), nchan, COAT_SAMPLES), np.float32)
+            self.mask = 0
+            for (lens, side), r in rows.items():
+                if not (0 <= int(lens) < int(nlens)) or int(side) not in (0, 1):
+                    raise BzrError(f"no surface ({lens}, {side}) in a chain of {nlens} lenses")
+                self.table[2 * int(lens) + int(side)] = r
+                self.mask |= 1 << (2 * int(lens) + int(side))
+        else:
+            self.table = None if table is None else np.ascontiguousarray(table, np.float32)
+            self.mask = int(mask or 0)
+
+    def _c(self, nl, nchan):
+        if self.table is not None and self.table.shape != (2 * nl, nchan, COAT_SAMPLES):
+            raise BzrError(f"coating table must be [2 nlens = {2 * nl}, nchan = {nchan}, {COAT_SAMPLES}], "
+                           f"got {self.table.shape}")
+        return _CoatingC(self.table.ctypes.data if self.table is not None else None, self.mask & 0xFFFFFFFF)
+
+
+def _coating(coat, nl, nchan):
+    """A Coating (or None) as a pointer argument; the structure must outlive the call, so it is returned too."""
+    if coat is None:
+        return None, None
+    c = coat._c(nl, nchan)
+    return ctypes.byref(c), c
+
+
+def trace_chain_coated(ctx: Context, lenses, ri_table, gap_table, glass_absorb, gap_absorb, rays, channel=None, weight=None,
+                       opl=None, max_bounces=4, ghost_seed=0, first_ray=0, axis=(1.0, 0.0, 0.0), coat=None,
+                       out_rays=None, out_weight=None, out_status=None, out_segments=None, out_bounces=None, out_opl=None,
+                       out_glass=None, mode=MODE_PARITY):
+    """trace_chain_bidir over coated surfaces -> the same seven-tuple.  coat: a Coating, or None (no surface coated:
+    trace_chain_bidir bit for bit).  On a coated surface the roulette's threshold and the budget-spent factor T come
+    from the surface's row at the gap-side cosine instead of the Fresnel formula (bzr.h bzr_coating)."""
+    n = _n_of(rays, mode)
+    nl = len(lenses)
+    handles = (_P * nl)(*[m.handle for m in lenses])
+    table, nchan = _ri_table(ri_table, nl)
+    gap = _gap_table(gap_table, nl, nchan)
+    ga, pa = _absorb_table(glass_absorb, "glass_absorb", nl, nchan), _absorb_table(gap_absorb, "gap_absorb", nl, nchan)
+    ax = np.ascontiguousarray(axis, np.float32)
+    if ax.shape != (3,):
+        raise BzrError("axis must have three components")
+    cref, ckeep = _coating(coat, nl, nchan)
+    out_rays = _empty_like(rays, 6, np.float32, mode) if out_rays is None else out_rays
+    out_weight = _empty_like(rays, 0, np.float32, mode) if out_weight is None else out_weight
+    out_status = _empty_like(rays, 0, np.uint32, mode) if out_status is None else out_status
+    out_segments = _empty_like(rays, 0, np.uint32, mode) if out_segments is None else out_segments
+    out_bounces = _empty_like(rays, 0, np.uint32, mode) if out_bounces is None else out_bounces
+    out_opl = _empty_like(rays, 0, np.float32, mode) if out_opl is None else out_opl
+    if out_glass is False:
+        out_glass = None
+    elif out_glass is None:
+        out_glass = _empty_like(rays, 0, np.float32, mode)
+    r, c, wi, pi = _Buf(rays, np.float32), _Buf(channel, np.uint8), _Buf(weight, np.float32), _Buf(opl, np.float32)
+    o, w = _Buf(out_rays, np.float32, True), _Buf(out_weight, np.float32, True)
+    s, g, b = _Buf(out_status, np.uint32, True), _Buf(out_segments, np.uint32, True), _Buf(out_bounces, np.uint32, True)
+    p, q = _Buf(out_opl, np.float32, True), _Buf(out_glass, np.float32, True)
+    res = _residency(r, c, o, w, s, g, b, wi, pi, p, q)
+    mask = (1 << 64) - 1
+    with _stream_for(ctx, res):
+        _check(lib().bzr_trace_chain_coated(ctx.handle, ctypes.cast(handles, _P), table.ctypes.data if table.size else None,
+                                            _table_ptr(gap), _table_ptr(ga), _table_ptr(pa), nl, nchan, r.ptr, c.ptr,
+                                            wi.ptr, pi.ptr, n, int(max_bounces), int(ghost_seed) & mask,
+                                            int(first_ray) & mask, ax.ctypes.data, cref, o.ptr, w.ptr, s.ptr, g.ptr, b.ptr,
+                                            p.ptr, q.ptr, res | mode))
+    del ckeep
+    return out_rays, out_weight, out_status, out_segments, out_bounces, out_opl, out_glass
+
+
+def coat_transmittance(row, mu) -> np.ndarray:
+    """The coated surface's lookup on the host, the device's twin bit for bit: T = coat_t(row, mu) for every mu (a
+    scalar, or an array in one call), row [COAT_SAMPLES] float32 (bzr.h bzr_coat_transmittance, bzr_debug.h
+    bzr_debug_coat_transmittance)."""
+    r = np.ascontiguousarray(row, np.float32)
+    if r.shape != (COAT_SAMPLES,):
+        raise BzrError(f"row must hold {COAT_SAMPLES} reflectances")
+    m = np.asarray(mu, np.float32)
+    if m.ndim == 0:
+        t = ctypes.c_float()
+        _check(lib().bzr_coat_transmittance(r.ctypes.data, ctypes.c_float(float(m)), ctypes.byref(t)))
+        return np.float32(t.value)
+    flat = np.ascontiguousarray(m).reshape(-1)
+    out = np.empty(flat.size, np.float32)
+    _check(lib().bzr_debug_coat_transmittance(r.ctypes.data, flat.ctypes.data, flat.size, out.ctypes.data))
+    return out.reshape(m.shape)
+
+
+def coating_reflectance(n_gap: float, n_glass: float, layer_index=(), layer_thickness_um=(), wavelength_um=0.55):
+    """One row of a Coating on the host: the unpolarised reflectance of a lossless dielectric stack between a gap of
+    index n_gap and glass of index n_glass at the gap-side cosines i / 128, float32 [COAT_SAMPLES].  Layers from the
+    gap side to the glass; none is the bare Fresnel surface (bzr.h bzr_coating_reflectance)."""
+    li = np.ascontiguousarray(layer_index, np.float64).ravel()
+    lt = np.ascontiguousarray(layer_thickness_um, np.float64).ravel()
+    if li.size != lt.size:
+        raise BzrError("one thickness per layer")
+    out = np.empty(COAT_SAMPLES, np.float32)
+    _check(lib().bzr_coating_reflectance(float(n_gap), float(n_glass), li.ctypes.data if li.size else None,
+                                         lt.ctypes.data if lt.size else None, li.size, float(wavelength_um),
+                                         out.ctypes.data))
+    return out
+
+
 def bidir_uniform(seed: int, ray: int, segment: int) -> np.float32:
     """trace_chain_bidir's draw on the host: the 24-bit uniform of (seed, the ray's 64-bit number, the segment's ordinal
     counted from 0) (bzr.h bzr_bidir_uniform)."""
@@ -1119,11 +1252,12 @@ def illuminate_media(ctx: Context, lenses, ri_table, gap_table, glass_absorb, ga
 
 
 def _illuminate_reflecting(ctx, lenses, ri_table, media, em, total_rays, target, max_bounces, emission, surface, flux, hist,
-                           reflected_flux, reflected_hist, mode, far=None, ghost_seed=None, axis=None):
+                           reflected_flux, reflected_hist, mode, far=None, ghost_seed=None, axis=None, coat=None):
     """illuminate_tir (media None), illuminate_media (media = the gap table and the two absorption tables) or
     illuminate_farfield (far = the frame and its three maps, each map or None; target may then be None);
     illuminate_ghost: ghost_seed given, media given, far or None; illuminate_bidir: and axis given -- the ledger dict
-    then holds the BACK rays' rows too, "back_count" and "back_power" [nchan][LEDGER_ROWS]."""
+    then holds the BACK rays' rows too, "back_count" and "back_power" [nchan][LEDGER_ROWS]; illuminate_coated: and coat
+    given (a Coating)."""
     nl = len(lenses)
     handles = (_P * nl)(*[m.handle for m in lenses])
     table, nchan = _ri_table(ri_table, nl)
@@ -1175,11 +1309,20 @@ def _illuminate_reflecting(ctx, lenses, ri_table, media, em, total_rays, target,
             if ax.shape != (3,):
                 raise BzrError("axis must have three components")
             far_args = (ctypes.byref(frame), ff.ptr, fh.ptr, frf.ptr, fstats, fpower) if far is not None else (None,) * 6
-            _check(lib().bzr_illuminate_bidir(ctx.handle, handles, table.ctypes.data if table.size else None,
-                                              *[_table_ptr(a) for a in media], *tail[:7],
-                                              int(ghost_seed) & ((1 << 64) - 1), ax.ctypes.data, *tail[7:-1],
-                                              back["back_count"].ctypes.data, back["back_power"].ctypes.data, tail[-1],
-                                              *far_args))
+            if coat is not None:
+                cref, ckeep = _coating(coat, nl, nchan)
+                _check(lib().bzr_illuminate_coated(ctx.handle, handles, table.ctypes.data if table.size else None,
+                                                   *[_table_ptr(a) for a in media], *tail[:7],
+                                                   int(ghost_seed) & ((1 << 64) - 1), ax.ctypes.data, cref, *tail[7:-1],
+                                                   back["back_count"].ctypes.data, back["back_power"].ctypes.data,
+                                                   tail[-1], *far_args))
+                del ckeep
+            else:
+                _check(lib().bzr_illuminate_bidir(ctx.handle, handles, table.ctypes.data if table.size else None,
+                                                  *[_table_ptr(a) for a in media], *tail[:7],
+                                                  int(ghost_seed) & ((1 << 64) - 1), ax.ctypes.data, *tail[7:-1],
+                                                  back["back_count"].ctypes.data, back["back_power"].ctypes.data,
+                                                  tail[-1], *far_args))
             ledger.update(back)
         elif ghost_seed is not None:
             far_args = (ctypes.byref(frame), ff.ptr, fh.ptr, frf.ptr, fstats, fpower) if far is not None else (None,) * 6
@@ -1321,6 +1464,29 @@ def illuminate_bidir(ctx: Context, lenses, ri_table, gap_table, glass_absorb, ga
                                   flux, hist, reflected_flux, reflected_hist, mode,
                                   far=None if far is None else (far, far_flux, far_hist, far_reflected_flux),
                                   ghost_seed=ghost_seed, axis=axis)
+
+
+def illuminate_coated(ctx: Context, lenses, ri_table, gap_table, glass_absorb, gap_absorb, em: Emitter, total_rays: int,
+                      target, far=None, max_bounces=4, ghost_seed=0, axis=(1.0, 0.0, 0.0), coat=None,
+                      emission=EMISSION_LAMBERT, surface=SURFACE_FRESNEL, flux=None, hist=None, reflected_flux=None,
+                      reflected_hist=None, far_flux=None, far_hist=None, far_reflected_flux=None, mode=MODE_PARITY):
+    """illuminate_bidir over trace_chain_coated's chain, `coat` a Coating (None: no surface coated) -> illuminate_bidir's
+    tuple.  With surface=SURFACE_LOSSLESS the coating is ignored; with no surface coated the call is illuminate_bidir
+    bit for bit (bzr.h bzr_illuminate_coated)."""
+    nl = len(lenses)
+    _, nchan = _ri_table(ri_table, nl)
+    media = (_gap_table(gap_table, nl, nchan), _absorb_table(glass_absorb, "glass_absorb", nl, nchan),
+             _absorb_table(gap_absorb, "gap_absorb", nl, nchan))
+    if target is None and far is None:
+        raise BzrError("neither a target nor a far-field frame")
+    if target is None and any(a is not None for a in (flux, hist, reflected_flux, reflected_hist)):
+        raise BzrError("target maps given without a target")
+    if far is None and any(a is not None for a in (far_flux, far_hist, far_reflected_flux)):
+        raise BzrError("far maps given without a far-field frame")
+    return _illuminate_reflecting(ctx, lenses, ri_table, media, em, total_rays, target, max_bounces, emission, surface,
+                                  flux, hist, reflected_flux, reflected_hist, mode,
+                                  far=None if far is None else (far, far_flux, far_hist, far_reflected_flux),
+                                  ghost_seed=ghost_seed, axis=axis, coat=coat if coat is not None else Coating(None, 0))
 
 
 def farfield_cell(far: FarField, directions) -> np.ndarray:
@@ -1512,6 +1678,7 @@ __all__ = [
     "BzrError", "Context", "DeviceMesh", "TriMesh", "intersect", "patch_intersect", "refract", "trace_chain", "interpolate",
     "Emitter", "Target", "emit", "illuminate", "bounding_sphere",
     "FarField", "farfield_bin", "illuminate_farfield", "trace_chain_ghost", "ghost_uniform", "illuminate_ghost",
-    "trace_chain_bidir", "bidir_uniform", "illuminate_bidir", "RR_BACK", "farfield_cell", "farfield_directions", "farfield_intensity",
+    "trace_chain_bidir", "bidir_uniform", "illuminate_bidir", "RR_BACK",
+    "Coating", "COAT_SAMPLES", "trace_chain_coated", "illuminate_coated", "coat_transmittance", "coating_reflectance", "farfield_cell", "farfield_directions", "farfield_intensity",
     "device_count", "lib", "exported_symbols", "LIB_PATH",
 ]

@@ -58,6 +58,11 @@ struct bzr_ctx {
   // kModeAbsorb's two absorption tables [nlens][nchan] lie behind the gap table, each part with its own host copy
   // (trace.hip upload_absorb_table).
   std::vector<float> glass_absorb_host, gap_absorb_host;
+  // kModeCoat's rows [2 nlens][nchan][BZR_COAT_SAMPLES] lie behind those; the host copy holds the masked rows alone,
+  // packed in surface order, and coat_key the mask and the shape they were sent with: mask << 32 | nlens << 16 | nchan,
+  // 0 while the device holds none (trace.hip upload_coat_table).
+  std::vector<float> coat_host;
+  uint64_t coat_key = 0;
   int32_t far_rounds = -1;  // test hook (bzr_debug_farfield_rounds): k_land_far's combine rounds, < 0: the default
 };
 

@@ -12,6 +12,7 @@
 //   newton_tail      reference/bezierTriangle.cpp:132-195
 //   fresnel_t        no reference counterpart: the transmittance of a refraction (DESIGN.md (a), ray power)
 //   att              no reference counterpart: the Beer-Lambert term of one leg (DESIGN.md (a), absorption)
+//   coat_t           no reference counterpart: the transmittance of a coated surface (DESIGN.md (a), surface coatings)
 __device__ __forceinline__ f3 add(f3 a, f3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
 __device__ __forceinline__ f3 sub(f3 a, f3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
 __device__ __forceinline__ f3 scale(f3 a, float s) { return mk(a.x * s, a.y * s, a.z * s); }
@@ -64,6 +65,32 @@ __device__ __forceinline__ float att(float x) {
   p = p + 1.0f;
   const float r = p * bits_f32((127u - (uint32_t)(int32_t)k) << 23);
   return live ? r : 0.0f;
+}
+
+// Transmittance of a coated surface (DESIGN.md (a), surface coatings; include/bzr.h bzr_coating): the row holds the
+// reflectance at the gap-side cosines i / 128, and the lookup is defined by its operations like att.  coat_cell: the
+// cell i = min((int)(128 mu'), 127) and the fraction f = 128 mu' - i of mu' = min(mu, 1), both exact (a scaling by a
+// power of two, an integer below 2^7, a difference of two floats within a factor of two or with i = 0); the integer
+// clamps keep a NaN or a negative mu inside the row.  coat_mix: R = r0 + f (r1 - r0), each operation rounded once, and
+// T = 1 - R.  With both entries in [0, 1] so are R and T.
+__device__ __forceinline__ int coat_cell(float mu, float &f) {
+  const float x = fminf(mu, 1.0f) * 128.0f;
+  int i = (int)x;
+  i = i < 127 ? i : 127;
+  i = i > 0 ? i : 0;
+  f = x - (float)i;
+  return i;
+}
+__device__ __forceinline__ float coat_mix(float r0, float r1, float f) {
+  const float dr = r1 - r0;
+  const float p = f * dr;
+  const float r = r0 + p;
+  return 1.0f - r;
+}
+__device__ __forceinline__ float coat_t(const float *row, float mu) {
+  float f;
+  const int i = coat_cell(mu, f);
+  return coat_mix(row[i], row[i + 1], f);
 }
 
 template <typename P>

@@ -444,6 +444,46 @@ __device__ __forceinline__ uint32_t bidir_eta_t(const Hit &h, float eta, f3 s, f
   if (drawn) gain = 1.0f;
   return st;
 }
+// bidir_eta_t on coated surfaces (kModeCoat; include/bzr.h bzr_coating): T is chosen per lane between fresnel_t and
+// coat_t(row, mu), `coated` saying which and `row` being the lane's row of the table (always inside the table's part of
+// the context's buffer, whatever the hit is).  T matters to the lanes that `pays`: `live` (the caller's: the lane is in
+// this round and its channel in the table), a hit on the expected side, s2 < 0.99 -- they draw against it or multiply
+// it in.  Both forms are skipped by a wave vote, not per lane: fresnel_t's two divisions and square root when no
+// paying lane meets bare glass, the table's gather when none meets a coating.  A lane that does not look its T up
+// reads entry 0 and 1 of its row and drops them.  (A sibling again: bidir_eta_t's instantiations keep their code.)
+__device__ __forceinline__ uint32_t coat_eta_t(const Hit &h, float eta, f3 s, f3 d, uint32_t expected, bool live,
+                                               bool may_reflect, bool may_draw, float u, bool coated,
+                                               const float *__restrict__ row, f3 &o_s, f3 &o_d, float &gain) {
+  const float s2 = eta * eta * (1.0f - h.cs * h.cs);
+  const bool open = expected == BZR_RR_INSIDE;
+  const bool side = open ? h.cs < 0.0f : h.cs >= 0.0f;
+  const bool met = h.what == kIntersect && side;
+  const bool facing = may_reflect && met;
+  const bool drawn = facing && may_draw && s2 < 0.99f;
+  const bool pays = live && met && s2 < 0.99f;
+  const bool looks = pays && coated;
+  float t = 1.0f;
+  if (__any(pays && !coated)) t = fresnel_t(eta, h.cs, s2);
+  if (__any(looks)) {
+    float f;
+    int i = coat_cell(open ? fabsf(h.cs) : sqrt_rn(1.0f - s2), f);
+    i = looks ? i : 0;
+    const float tc = coat_mix(row[i], row[i + 1], f);
+    if (looks) t = tc;
+  }
+  bool mirror = facing && s2 >= 1.0f;
+  if (drawn) mirror = u >= t;
+  if (mirror) {
+    const float k = 2.0f * h.cs;
+    o_d = normalized(sub(d, scale(h.normal, k)));
+    o_s = h.point;
+    return kReflected;
+  }
+  float unused;
+  const uint32_t st = refract_eta_t<false>(h, eta, s, d, expected, o_s, o_d, unused);
+  gain = drawn ? 1.0f : t;
+  return st;
+}
 // The walk's side rule: does the surface a glass segment met face forward along the chain's axis `a`?  One dot product
 // in binary32, the last two products summed first (no contraction: the build's -ffp-contract=off).
 __device__ __forceinline__ bool bidir_back(f3 n, f3 a) { return n.x * a.x + (n.y * a.y + n.z * a.z) >= 0.0f; }
@@ -655,6 +695,10 @@ constexpr uint32_t kSlotWords = 12;  // t, point, cos, bary, normal, source patc
 // both through its gap_table pointer: with a pointer of their own in TraceJob the two non-counting k_trace<kModeAbsorb>
 // came out with 36 B of scratch reserved (never accessed), in every order of the tail that was tried (DESIGN (a)).
 constexpr uint32_t kGapPart = (kMaxLenses + 1u) * BZR_MAX_CHANNELS, kAbsorbPart = kMaxLenses * BZR_MAX_CHANNELS;
+// kModeCoat's table lies behind those, kCoatPart floats from the gap table: rows of BZR_COAT_SAMPLES floats, row
+// (2 l + side) nchan + c for surface (l, side) and channel c; kCoatFloats is the worst case, 16 x 64 x 129 (528 KB).
+constexpr uint32_t kCoatPart = kGapPart + 2u * kAbsorbPart;
+constexpr uint32_t kCoatFloats = 2u * kMaxLenses * BZR_MAX_CHANNELS * BZR_COAT_SAMPLES;
 // kModeAbsorb: kModeMedia with Beer-Lambert absorption -- every leg that ends in a refraction or a reflection
 // multiplies the weight by att(a len) (leg_attenuation), a = gap_absorb[l][channel[i]] in front of lens l and
 // glass_absorb[l][channel[i]] inside it, ahead of the Fresnel gain; a reflection now touches the weight.  A mode of its
@@ -671,12 +715,19 @@ constexpr uint32_t kGapPart = (kMaxLenses + 1u) * BZR_MAX_CHANNELS, kAbsorbPart 
 // three job words, the chain's axis, share kModeRefract's `expected` and `expected_all` slots of TraceJob, as ghost_base
 // shares `hits`: TraceJob keeps its size and the older kernels their code.  A mode of its own: the other ten compile to
 // the code they had.
+// kModeCoat: kModeBidir with tabulated reflectances (include/bzr.h bzr_coating) -- the walk, the schedule and the words
+// are kModeBidir's; the step is coat_eta_t, which takes T per lane from fresnel_t or from the surface's row in the
+// context's buffer (kCoatPart).  Its one job word, the mask of coated surfaces, rides in the high half of max_bounces
+// (the budget is at most BZR_MAX_BOUNCES): TraceJob keeps its size and k_chain_scan its arguments.  A mode of its own:
+// the other eleven compile to the code they had.
 enum OutMode {
   kModeHits = 0, kModeRefract = 1, kModeStage = 2, kModePower = 3, kModeSpectral = 4, kModeTir = 5, kModeOpl = 6,
-  kModeMedia = 7, kModeAbsorb = 8, kModeGhost = 9, kModeBidir = 10
+  kModeMedia = 7, kModeAbsorb = 8, kModeGhost = 9, kModeBidir = 10,
+  kModeCoat = 11
 };
 constexpr bool has_ghost(int mode) { return mode == kModeGhost; }
-constexpr bool has_bidir(int mode) { return mode == kModeBidir; }
+constexpr bool has_coat(int mode) { return mode == kModeCoat; }
+constexpr bool has_bidir(int mode) { return mode == kModeBidir || has_coat(mode); }
 constexpr bool has_absorb(int mode) { return mode == kModeAbsorb || has_ghost(mode) || has_bidir(mode); }
 constexpr bool has_media(int mode) { return mode == kModeMedia || has_absorb(mode); }
 constexpr bool has_opl(int mode) { return mode == kModeOpl || has_media(mode); }
@@ -2093,6 +2144,8 @@ template <>
 struct TraceKeep<kModeBidir> : TraceKeep<kModeAbsorb> {
   uint32_t state[64];
 };
+template <>
+struct TraceKeep<kModeCoat> : TraceKeep<kModeBidir> {};  // kModeCoat keeps what kModeBidir keeps: the table is read
 // The bundle walk's set of leaf slots already queued in this wave-segment (bundle_batch `seen`), one bit per
 // slot: the refract and chain kernels walk the trees with split leaf boxes (MeshView swide).  The intersect
 // kernel's 6.7 KB per wave leave no room for it (24 waves x 7.7 KB > 160 KB), and the power, spectral and TIR
@@ -2600,12 +2653,14 @@ struct TraceJob {
   uint32_t lossless;               // kModeSpectral: the weights stay as they are (the gain counts as 1)
   uint32_t *bounces;               // kModeTir, optional [n]: the rays' reflections (channel may be null: channel 0)
   uint32_t max_bounces;            // kModeTir: reflections allowed per ray and lens (<= BZR_MAX_BOUNCES)
+                                   // kModeCoat: and, in bits 16-31, the mask of coated surfaces (bit 2 l + side)
   float *opl;                      // kModeOpl [n]: the traced rays' optical path length (may alias opl_in)
   const float *opl_in;             // kModeOpl [n]: the path the rays start with, or null -> 0
   float *glass;                    // kModeOpl, optional [n]: the rays' geometric length inside glass
   const float *gap_table;          // kModeMedia [count + 1][nchan]: the index in front of lens l, row count behind the last
                                    // kModeAbsorb: and, kGapPart floats behind it, glass_absorb [count][nchan], and
                                    // kAbsorbPart floats behind that gap_absorb [count][nchan] (the context's buffer)
+                                   // kModeCoat: and, kCoatPart floats behind it, the coating table's rows
 };
 
 // kTraceWpe: amdgpu_waves_per_eu lower bound for k_trace.  The chain kernel needs 72 VGPRs
@@ -2792,8 +2847,19 @@ __global__ __launch_bounds__(kTraceBlock) BZR_TRACE_ATTR void k_trace(LensSet le
       const float eta = div_rn(gl ? ri : ng, gl ? ng : ri);
       f3 os, od;
       float gain = 1.0f;
-      uint32_t r = bidir_eta_t<true>(h, eta, s, d, gl ? uint32_t(BZR_RR_OUTSIDE) : uint32_t(BZR_RR_INSIDE),
-                                     in_table && (cnt >> 16) < job.max_bounces, !job.lossless, u, os, od, gain);
+      uint32_t r;
+      if constexpr (has_coat(kMode)) {
+        // (the surface's number 2 l + side, its mask bit and the lane's row: l < count, c < nchan, so the row lies in
+        // the table's part of the buffer for every lane, hit or not)
+        const uint32_t sf = 2u * l + (back ? 1u : 0u);
+        r = coat_eta_t(h, eta, s, d, gl ? uint32_t(BZR_RR_OUTSIDE) : uint32_t(BZR_RR_INSIDE), act && in_table,
+                       in_table && (cnt >> 16) < (job.max_bounces & 0xFFFFu), !job.lossless, u,
+                       ((job.max_bounces >> (16u + sf)) & 1u) != 0u,
+                       job.gap_table + kCoatPart + (sf * job.nchan + c) * uint32_t(BZR_COAT_SAMPLES), os, od, gain);
+      } else {
+        r = bidir_eta_t<true>(h, eta, s, d, gl ? uint32_t(BZR_RR_OUTSIDE) : uint32_t(BZR_RR_INSIDE),
+                              in_table && (cnt >> 16) < job.max_bounces, !job.lossless, u, os, od, gain);
+      }
       if (!in_table) r = BZR_RR_NONE;
       if (job.lossless) gain = 1.0f;
       if (act) {
@@ -3083,7 +3149,7 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
                                                        const float *__restrict__ gap_absorb, uint64_t ghost_at,
                                                        float axis_x, float axis_y, float axis_z) {
   constexpr bool kPower = kScan != 0, kSpectral = kScan >= 2, kTir = kScan >= 3, kOpl = kScan >= 4, kMedia = kScan >= 5;
-  constexpr bool kAbsorb = kScan >= 6, kGhost = kScan == 7, kBidir = kScan == 8;
+  constexpr bool kAbsorb = kScan >= 6, kGhost = kScan == 7, kBidir = kScan == 8 || kScan == 9, kCoat = kScan == 9;
   uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   f3 s, d;
@@ -3115,9 +3181,19 @@ __global__ __launch_bounds__(kBlock) void k_chain_scan(LensSet lenses, const flo
       const float ng = gap_table[gi * nchan + ch];
       f3 os, od;
       float gain = 1.0f;
-      uint32_t r = bidir_eta_t<true>(h, div_rn(gl ? ri : ng, gl ? ng : ri), s, d, gl ? BZR_RR_OUTSIDE : BZR_RR_INSIDE,
-                                     in_table && bounces < max_bounces, true, ghost_uniform(ghost_at, i, 256u + seg), os,
-                                     od, gain);
+      uint32_t r;
+      if constexpr (kCoat) {
+        // (the mask rides in max_bounces' high half and the table lies behind gap_absorb's part, as in k_trace)
+        const uint32_t sf = 2u * l + (back ? 1u : 0u);
+        r = coat_eta_t(h, div_rn(gl ? ri : ng, gl ? ng : ri), s, d, gl ? BZR_RR_OUTSIDE : BZR_RR_INSIDE, in_table,
+                       in_table && bounces < (max_bounces & 0xFFFFu), true, ghost_uniform(ghost_at, i, 256u + seg),
+                       ((max_bounces >> (16u + sf)) & 1u) != 0u,
+                       gap_absorb + kAbsorbPart + (sf * nchan + ch) * uint32_t(BZR_COAT_SAMPLES), os, od, gain);
+      } else {
+        r = bidir_eta_t<true>(h, div_rn(gl ? ri : ng, gl ? ng : ri), s, d, gl ? BZR_RR_OUTSIDE : BZR_RR_INSIDE,
+                              in_table && bounces < max_bounces, true, ghost_uniform(ghost_at, i, 256u + seg), os,
+                              od, gain);
+      }
       if (!in_table) r = BZR_RR_NONE;
       ++seg;
       if (r != BZR_RR_NONE) {
@@ -3594,9 +3670,12 @@ constexpr size_t kRiTableFloats = (size_t)kMaxLenses * kMaxChannels, kGapTableFl
 // (and kModeAbsorb's two tables [nlens][nchan] behind those: the glass part, then the gap part)
 constexpr size_t kAbsorbTableFloats = kAbsorbPart;
 constexpr size_t kGlassAbsorbAt = kRiTableFloats + kGapTableFloats, kGapAbsorbAt = kGlassAbsorbAt + kAbsorbTableFloats;
+// (and kModeCoat's rows behind those)
+constexpr size_t kCoatAt = kGapAbsorbAt + kAbsorbTableFloats;
+static_assert(kCoatAt == kRiTableFloats + kCoatPart, "the kernels reach the coating's rows through gap_table");
 bzr_status upload_ri_table(bzr_ctx *ctx, const float *table, uint32_t nlens, uint32_t nchan) {
   const size_t count = (size_t)nlens * nchan;
-  if (!ctx->ri_table) BZR_HIP(hipMalloc(&ctx->ri_table, (kGapAbsorbAt + kAbsorbTableFloats) * sizeof(float)));
+  if (!ctx->ri_table) BZR_HIP(hipMalloc(&ctx->ri_table, (kCoatAt + kCoatFloats) * sizeof(float)));
   if (ctx->ri_table_host.size() == count && std::memcmp(ctx->ri_table_host.data(), table, count * sizeof(float)) == 0)
     return BZR_OK;
   BZR_HIP(hipStreamSynchronize(ctx->stream));
@@ -3633,6 +3712,52 @@ bzr_status upload_absorb_table(bzr_ctx *ctx, const float *table, uint32_t nlens,
   host.clear();
   BZR_HIP(hipMemcpy(ctx->ri_table + at, table, count * sizeof(float), hipMemcpyHostToDevice));
   host.assign(table, table + count);
+  return BZR_OK;
+}
+// A coating's checks (include/bzr.h bzr_coating): the mask's bits below 2 nlens, a table where the mask is not zero,
+// every entry of a masked row finite and in [0, 1].  Rows of unmasked surfaces are not read.
+bzr_status check_coating(const bzr_coating *coat, uint32_t nlens, uint32_t nchan) {
+  if (!coat || coat->mask == 0u) return BZR_OK;
+  if (nlens < 16u && (coat->mask >> (2u * nlens)) != 0u)
+    return set_error(BZR_ERR_INVALID_ARGUMENT, "coating mask names a surface at or above 2 nlens");
+  if (!coat->table) return set_error(BZR_ERR_INVALID_ARGUMENT, "coating mask without a table");
+  const size_t per = (size_t)nchan * BZR_COAT_SAMPLES;
+  for (uint32_t sf = 0; sf < 2u * nlens; ++sf) {
+    if (!((coat->mask >> sf) & 1u)) continue;
+    for (size_t k = 0; k < per; ++k) {
+      const float v = coat->table[sf * per + k];
+      if (!(v >= 0.0f) || !(v <= 1.0f))
+        return set_error(BZR_ERR_INVALID_ARGUMENT, "coating table entries must be finite and in [0, 1]");
+    }
+  }
+  return BZR_OK;
+}
+// kModeCoat's rows behind the absorption parts, under upload_absorb_table's rule: the context keeps the mask, the shape
+// and the masked rows of what the device holds (coat_key, coat_host: the rows packed in surface order), and the device
+// copy is rewritten only when one of them differs.  A masked row is then always one the device has received -- a row of
+// zeros too, which an image with zeros for the unmasked rows could not tell from a row never sent.  Only the masked
+// rows are copied.  A call without coated surfaces touches nothing.
+bzr_status upload_coat_table(bzr_ctx *ctx, const bzr_coating *coat, uint32_t nlens, uint32_t nchan) {
+  if (!coat || coat->mask == 0u) return BZR_OK;
+  const size_t per = (size_t)nchan * BZR_COAT_SAMPLES;
+  const uint64_t key = ((uint64_t)coat->mask << 32) | ((uint64_t)nlens << 16) | nchan;
+  std::vector<float> rows;
+  for (uint32_t sf = 0; sf < 2u * nlens; ++sf)
+    if ((coat->mask >> sf) & 1u) rows.insert(rows.end(), coat->table + sf * per, coat->table + (sf + 1u) * per);
+  if (ctx->coat_key == key && ctx->coat_host.size() == rows.size() &&
+      std::memcmp(ctx->coat_host.data(), rows.data(), rows.size() * sizeof(float)) == 0)
+    return BZR_OK;
+  BZR_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->coat_key = 0;
+  ctx->coat_host.clear();
+  size_t at = 0;
+  for (uint32_t sf = 0; sf < 2u * nlens; ++sf)
+    if ((coat->mask >> sf) & 1u) {
+      BZR_HIP(hipMemcpy(ctx->ri_table + kCoatAt + sf * per, rows.data() + at, per * sizeof(float), hipMemcpyHostToDevice));
+      at += per;
+    }
+  ctx->coat_host = std::move(rows);
+  ctx->coat_key = key;
   return BZR_OK;
 }
 // Every used entry of an absorption table finite and not below zero (a null table is all zero).
@@ -4285,7 +4410,7 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
                               uint32_t *out_bounces = nullptr, const float *opl_in = nullptr, float *out_opl = nullptr,
                               float *out_glass = nullptr, const float *gap = nullptr, const float *glass_abs = nullptr,
                               const float *gap_abs = nullptr, uint64_t ghost_seed = 0, uint64_t first_ray = 0,
-                              const float *axis = nullptr) {
+                              const float *axis = nullptr, const bzr_coating *coat = nullptr) {
   constexpr bool kPower = has_power(kMode), kSpectral = has_channels(kMode), kTir = has_tir(kMode);
   constexpr bool kOpl = has_opl(kMode), kMedia = has_media(kMode), kAbsorb = has_absorb(kMode);
   if (bzr_status s = check_flags(flags, true)) return s;
@@ -4326,6 +4451,10 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
     if (bzr_status s = upload_absorb_table(ctx, glass_abs, nlens, nchan, kGlassAbsorbAt, ctx->glass_absorb_host)) return s;
     if (bzr_status s = upload_absorb_table(ctx, gap_abs, nlens, nchan, kGapAbsorbAt, ctx->gap_absorb_host)) return s;
   }
+  if (has_coat(kMode)) {  // the rows, and the mask into the high half of the kernels' max_bounces word
+    if (bzr_status s = upload_coat_table(ctx, coat, nlens, nchan)) return s;
+    max_bounces |= (coat ? coat->mask : 0u) << 16;
+  }
   // (kModeBidir has no staged form: its entry point has refused the explicit flag, the automatic choice is fused)
   const bool staged = !has_bidir(kMode) && !use_scan(flags) && use_staged(flags, n, max_patches(set));
   float *r = nullptr, *tmp = nullptr;  // tmp, host + AoS: the records on the device, in and out
@@ -4361,7 +4490,7 @@ static bzr_status trace_chain(bzr_ctx *ctx, const bzr_mesh *const *lenses, const
   }
   if (use_scan(flags)) {
     launch(ctx, BZR_KERNEL_CHAIN_SCAN,
-           k_chain_scan<has_bidir(kMode) ? 8 : has_ghost(kMode) ? 7 : kAbsorb ? 6 : kMedia ? 5 : kOpl ? 4 : (kTir ? 3 : (kSpectral ? 2 : (kPower ? 1 : 0)))>,
+           k_chain_scan<has_coat(kMode) ? 9 : has_bidir(kMode) ? 8 : has_ghost(kMode) ? 7 : kAbsorb ? 6 : kMedia ? 5 : kOpl ? 4 : (kTir ? 3 : (kSpectral ? 2 : (kPower ? 1 : 0)))>,
            dim3(grid_for(n)), set, d_rays, n, d_out, d_st, d_seg, d_win, d_w, d_ch, (const float *)ctx->ri_table, nchan, d_bnc,
            max_bounces, d_oin, d_opl, d_glass, kMedia ? (const float *)ctx->ri_table + kRiTableFloats : nullptr,
            kAbsorb ? (const float *)ctx->ri_table + kGlassAbsorbAt : nullptr,
@@ -4546,6 +4675,30 @@ extern "C" bzr_status bzr_trace_chain_bidir(bzr_ctx *ctx, const bzr_mesh *const 
   return trace_chain<kModeBidir>(ctx, lenses, ri_table, nlens, rays, weight_in, n, out_rays, out_weight, out_status,
                                  out_segments, flags, channel, nchan, max_bounces, out_bounces, opl_in, out_opl, out_glass,
                                  gap_table, glass_absorb, gap_absorb, ghost_seed, first_ray, axis);
+}
+
+extern "C" bzr_status bzr_trace_chain_coated(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                             const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                             uint32_t nlens, uint32_t nchan, const float *rays, const uint8_t *channel,
+                                             const float *weight_in, const float *opl_in, uint32_t n,
+                                             uint32_t max_bounces, uint64_t ghost_seed, uint64_t first_ray,
+                                             const float axis[3], const bzr_coating *coat, float *out_rays,
+                                             float *out_weight, uint32_t *out_status, uint32_t *out_segments,
+                                             uint32_t *out_bounces, float *out_opl, float *out_glass, uint32_t flags) {
+  // (bzr_trace_chain_bidir's checks, in its order, then the coating's)
+  if (!out_opl) return set_error(BZR_ERR_INVALID_ARGUMENT, "null out_opl");
+  if (max_bounces > BZR_MAX_BOUNCES) return set_error(BZR_ERR_INVALID_ARGUMENT, "max_bounces must be 0..8");
+  if (nlens >= 1 && nlens <= kMaxLenses && nchan >= 1 && nchan <= kMaxChannels) {
+    if (bzr_status s = check_absorb_table(glass_absorb, nlens, nchan, "glass_absorb entries must be finite and >= 0")) return s;
+    if (bzr_status s = check_absorb_table(gap_absorb, nlens, nchan, "gap_absorb entries must be finite and >= 0")) return s;
+  }
+  if (bzr_status s = check_axis(axis)) return s;
+  if (bzr_status s = check_bidir_flags(flags)) return s;
+  if (nlens >= 1 && nlens <= kMaxLenses && nchan >= 1 && nchan <= kMaxChannels)
+    if (bzr_status s = check_coating(coat, nlens, nchan)) return s;
+  return trace_chain<kModeCoat>(ctx, lenses, ri_table, nlens, rays, weight_in, n, out_rays, out_weight, out_status,
+                                out_segments, flags, channel, nchan, max_bounces, out_bounces, opl_in, out_opl, out_glass,
+                                gap_table, glass_absorb, gap_absorb, ghost_seed, first_ray, axis, coat);
 }
 
 // ------------------------------------------------------------ test hook: normalized()
@@ -5278,6 +5431,8 @@ struct IllumTir {
   bool bidir = false;
   float axis[3] = {0.0f, 0.0f, 0.0f};
   uint64_t *back_count = nullptr, *back_power = nullptr;
+  // bzr_illuminate_coated: the chain is kModeCoat's over this coating (checked; null or mask 0: kModeBidir's)
+  const bzr_coating *coat = nullptr;
 };
 static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri, uint32_t nlens,
                              const bzr_emitter *em, uint64_t total_rays, const bzr_target *tg, const bzr_radiometry *rad,
@@ -5339,6 +5494,7 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
       return s;
     if (bzr_status s = upload_absorb_table(ctx, tir->gap_absorb, nlens, nchan, kGapAbsorbAt, ctx->gap_absorb_host))
       return s;
+    if (bzr_status s = upload_coat_table(ctx, tir->coat, nlens, nchan)) return s;
   }
   // target plane (normal = axis_u x axis_v normalised, constant = n . origin) and cell sizes, in the
   // oracle's operation order
@@ -5481,7 +5637,12 @@ static bzr_status illuminate(bzr_ctx *ctx, const bzr_mesh *const *lenses, const 
       job.axis_xy[0] = tir->axis[0];
       job.axis_xy[1] = tir->axis[1];
       job.axis_z = tir->axis[2];
-      if (bzr_status s = run_fused<kModeBidir>(ctx, set, job, flags)) return s;
+      // (a lossless call draws nothing and pays no T: the coating is ignored, the chain is kModeBidir's)
+      const uint32_t coat_mask = (tir->coat && !job.lossless) ? tir->coat->mask : 0u;
+      if (coat_mask != 0u) {
+        job.max_bounces |= coat_mask << 16;
+        if (bzr_status s = run_fused<kModeCoat>(ctx, set, job, flags)) return s;
+      } else if (bzr_status s = run_fused<kModeBidir>(ctx, set, job, flags)) return s;
       hipLaunchKernelGGL(k_back_rows, dim3(grid_for(m)), dim3(kBlock), 0, ctx->stream, m, (const uint32_t *)d_st,
                          (const uint32_t *)d_seg, (const uint32_t *)d_bnc, (const float *)d_w, (const uint8_t *)d_ch,
                          d_bcount, d_bpower);
@@ -5705,6 +5866,47 @@ extern "C" bzr_status bzr_illuminate_bidir(bzr_ctx *ctx, const bzr_mesh *const *
   tir.axis[0] = axis[0], tir.axis[1] = axis[1], tir.axis[2] = axis[2];
   tir.back_count = back_count;
   tir.back_power = back_power_q32;
+  return illuminate(ctx, lenses, ri_table, nlens, em, total_rays, tg, rad, flux_q32, hist, stats, power_q32, flags, true,
+                    nchan, &tir);
+}
+
+// bzr_illuminate_bidir over the coated chain.
+extern "C" bzr_status bzr_illuminate_coated(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                            const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                            uint32_t nlens, uint32_t nchan, const bzr_emitter *em, uint64_t total_rays,
+                                            const bzr_target *tg, const bzr_radiometry *rad, uint32_t max_bounces,
+                                            uint64_t ghost_seed, const float axis[3], const bzr_coating *coat,
+                                            uint64_t *flux_q32, uint32_t *hist, uint64_t *reflected_flux_q32,
+                                            uint32_t *reflected_hist, uint64_t *stats, uint64_t *power_q32,
+                                            uint64_t *ledger_count, uint64_t *ledger_power_q32, uint64_t *back_count,
+                                            uint64_t *back_power_q32, uint32_t flags, const bzr_farfield *far,
+                                            uint64_t *far_flux_q32, uint32_t *far_hist, uint64_t *far_reflected_flux_q32,
+                                            uint64_t *far_stats, uint64_t *far_power_q32) {
+  if (!rad) return set_error(BZR_ERR_INVALID_ARGUMENT, "null radiometry");
+  if (!far && (far_flux_q32 || far_hist || far_reflected_flux_q32 || far_stats || far_power_q32))
+    return set_error(BZR_ERR_INVALID_ARGUMENT, "far outputs given without a far-field frame");
+  if (!far && !tg) return set_error(BZR_ERR_INVALID_ARGUMENT, "neither a target nor a far-field frame");
+  if (bzr_status s = check_axis(axis)) return s;
+  if (bzr_status s = check_bidir_flags(flags)) return s;
+  if (nlens >= 1 && nlens <= kMaxLenses && nchan >= 1 && nchan <= kMaxChannels)
+    if (bzr_status s = check_coating(coat, nlens, nchan)) return s;
+  if (far) {
+    FarFrame checked{};
+    if (bzr_status s = far_frame(far, nchan, checked)) return s;
+  }
+  const IllumFar ifar{far, far_flux_q32, far_hist, far_reflected_flux_q32, far_stats, far_power_q32};
+  IllumTir tir{max_bounces, reflected_flux_q32, reflected_hist, ledger_count, ledger_power_q32};
+  tir.media = true;
+  tir.gap = gap_table;
+  tir.glass_absorb = glass_absorb;
+  tir.gap_absorb = gap_absorb;
+  tir.far = far ? &ifar : nullptr;
+  tir.ghost_seed = ghost_seed;
+  tir.bidir = true;
+  tir.axis[0] = axis[0], tir.axis[1] = axis[1], tir.axis[2] = axis[2];
+  tir.back_count = back_count;
+  tir.back_power = back_power_q32;
+  tir.coat = coat;
   return illuminate(ctx, lenses, ri_table, nlens, em, total_rays, tg, rad, flux_q32, hist, stats, power_q32, flags, true,
                     nchan, &tir);
 }

@@ -280,6 +280,42 @@ void traceChainBidir(std::vector<BezierLens const *> const &lenses, std::vector<
   }
 }
 
+void traceChainCoated(std::vector<BezierLens const *> const &lenses, std::vector<float> const &riTable,
+                      std::vector<float> const &gapTable, std::vector<float> const &glassAbsorb,
+                      std::vector<float> const &gapAbsorb, Ray const *rays, uint8_t const *channels, float const *weights,
+                      float const *opl, std::size_t n, uint32_t maxBounces, uint64_t ghostSeed, uint64_t firstRay,
+                      float const (&axis)[3], std::vector<float> const &coatTable, uint32_t coatMask, Ray *outRays,
+                      float *outWeights, RefractionResult *outStatus, float *outOpl, float *outGlass,
+                      uint32_t *outSegments, uint32_t *outBounces, Context *ctx) {
+  if (lenses.empty() || riTable.size() % lenses.size()) throw std::invalid_argument("riTable must be [lenses][nchan]");
+  const uint32_t nchan = static_cast<uint32_t>(riTable.size() / lenses.size());
+  if (!gapTable.empty() && gapTable.size() != (lenses.size() + 1) * nchan)
+    throw std::invalid_argument("gapTable must be empty or [lenses + 1][nchan]");
+  if (!glassAbsorb.empty() && glassAbsorb.size() != riTable.size())
+    throw std::invalid_argument("glassAbsorb must be empty or [lenses][nchan]");
+  if (!gapAbsorb.empty() && gapAbsorb.size() != riTable.size())
+    throw std::invalid_argument("gapAbsorb must be empty or [lenses][nchan]");
+  if (!coatTable.empty() && coatTable.size() != 2 * riTable.size() * BZR_COAT_SAMPLES)
+    throw std::invalid_argument("coatTable must be empty or [2 lenses][nchan][BZR_COAT_SAMPLES]");
+  Context &c = ctx ? *ctx : defaultContext();
+  std::vector<bzr_mesh const *> meshes;
+  for (auto const *l : lenses) meshes.push_back(l->getMesh().device(c));
+  const bzr_coating coat{coatTable.empty() ? nullptr : coatTable.data(), coatMask};
+  std::lock_guard<std::mutex> hold(c.lock());
+  for (std::size_t off = 0; off < n; off += kMaxBatch) {  // (each batch draws with its rays' own numbers)
+    const std::size_t m = std::min(kMaxBatch, n - off);
+    check(bzr_trace_chain_coated(c.get(), meshes.data(), riTable.data(), gapTable.empty() ? nullptr : gapTable.data(),
+                                 glassAbsorb.empty() ? nullptr : glassAbsorb.data(),
+                                 gapAbsorb.empty() ? nullptr : gapAbsorb.data(), static_cast<uint32_t>(meshes.size()),
+                                 nchan, records(rays + off), channels ? channels + off : nullptr,
+                                 weights ? weights + off : nullptr, opl ? opl + off : nullptr, static_cast<uint32_t>(m),
+                                 maxBounces, ghostSeed, firstRay + off, axis, &coat, records(outRays + off),
+                                 outWeights + off, words(outStatus + off), outSegments ? outSegments + off : nullptr,
+                                 outBounces ? outBounces + off : nullptr, outOpl ? outOpl + off : nullptr,
+                                 outGlass ? outGlass + off : nullptr, BZR_HOST_PTRS | BZR_RAYS_AOS));
+  }
+}
+
 void farfieldBin(bzr_farfield const &far, Ray const *rays, float const *weights, RefractionResult const *status,
                  uint8_t const *channels, std::size_t n, uint32_t nchan, uint64_t *farFlux, uint32_t *farHist,
                  uint64_t *farStats, uint64_t *farPower, Context *ctx) {

@@ -296,6 +296,118 @@ bzr_status bzr_bidir_uniform(uint64_t seed, uint64_t ray, uint32_t segment, floa
   return BZR_OK;
 }
 
+// ---- surface coatings (include/bzr.h bzr_coating) ----
+// The lookup's host twin: patch_math_body.inc coat_t, the text the kernels compile.
+bzr_status bzr_coat_transmittance(const float *row, float mu, float *t) {
+  if (!row || !t) return bad("null argument");
+  if (!(mu >= 0.0f)) return bad("mu must be >= 0");
+  *t = bzr_host::coat_transmittance(row, mu);
+  return BZR_OK;
+}
+
+// include/bzr_debug.h: the same lookup over n cosines
+int32_t bzr_debug_coat_transmittance(const float *row, const float *mu, uint32_t n, float *out) {
+  if ((!row || !mu || !out) && n) return bad("null argument");
+  for (uint32_t i = 0; i < n; ++i)
+    if (!(mu[i] >= 0.0f)) return bad("mu must be >= 0");
+  for (uint32_t i = 0; i < n; ++i) out[i] = bzr_host::coat_transmittance(row, mu[i]);
+  return BZR_OK;
+}
+
+// One row by the characteristic-matrix method in binary64.  Per polarisation a medium j has the admittance
+// y_j = n_j cos_j (s) or n_j / cos_j (p), cos_j = sqrt(1 - (n_gap sin / n_j)^2) a complex root with a non-negative
+// imaginary part (evanescent beyond the critical angle); a layer's matrix is [[cos d, -i sin d / y], [-i y sin d, cos d]]
+// with d = 2 pi n_j t_j cos_j / lambda; (B, C) = M_1 ... M_k (1, y_glass), r = (y_gap B - C) / (y_gap B + C),
+// R = |r|^2.  Every value is computed before the first is written.
+namespace {
+struct Cx {
+  double re, im;
+};
+inline Cx operator+(Cx a, Cx b) { return {a.re + b.re, a.im + b.im}; }
+inline Cx operator-(Cx a, Cx b) { return {a.re - b.re, a.im - b.im}; }
+inline Cx operator*(Cx a, Cx b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+inline Cx operator/(Cx a, Cx b) {
+  const double z = b.re * b.re + b.im * b.im;
+  return {(a.re * b.re + a.im * b.im) / z, (a.im * b.re - a.re * b.im) / z};
+}
+// sqrt of a real number: on the positive real or the positive imaginary axis
+inline Cx root(double x) { return x >= 0.0 ? Cx{std::sqrt(x), 0.0} : Cx{0.0, std::sqrt(-x)}; }
+// cos z and sin z, both divided by e^|Im z|: a layer's matrix may carry any common factor, (B, C) enter r only through
+// their ratio, and the scaled pair stays of order 1 where cosh and sinh of a thick evanescent layer would overflow
+inline void cx_cos_sin_scaled(Cx z, Cx &c, Cx &s) {
+  const double e = std::exp(-2.0 * std::fabs(z.im));
+  const double ch = 0.5 * (1.0 + e), sh = (z.im < 0.0 ? -0.5 : 0.5) * (1.0 - e);
+  c = {std::cos(z.re) * ch, -std::sin(z.re) * sh};
+  s = {std::sin(z.re) * ch, std::cos(z.re) * sh};
+}
+}  // namespace
+
+bzr_status bzr_coating_reflectance(double n_gap, double n_glass, const double *layer_index,
+                                   const double *layer_thickness_um, uint32_t nlayers, double wavelength_um,
+                                   float *out_row) {
+  constexpr uint32_t kMaxLayers = 8;
+  if (!out_row) return bad("null out_row");
+  if (nlayers > kMaxLayers) return bad("nlayers must be 0..8");
+  if (nlayers && (!layer_index || !layer_thickness_um)) return bad("null layer arrays");
+  if (!std::isfinite(n_gap) || !(n_gap > 0.0) || !std::isfinite(n_glass) || !(n_glass > 0.0))
+    return bad("indices must be finite and positive");
+  if (!std::isfinite(wavelength_um) || !(wavelength_um > 0.0)) return bad("wavelength must be finite and positive");
+  for (uint32_t j = 0; j < nlayers; ++j) {
+    if (!std::isfinite(layer_index[j]) || !(layer_index[j] > 0.0)) return bad("layer indices must be finite and positive");
+    if (!std::isfinite(layer_thickness_um[j]) || !(layer_thickness_um[j] > 0.0))
+      return bad("layer thicknesses must be finite and positive");
+  }
+  float row[BZR_COAT_SAMPLES];
+  row[0] = 1.0f;  // (mu = 0: grazing, by definition)
+  const double kTwoPi = 6.283185307179586476925286766559;
+  for (uint32_t i = 1; i < BZR_COAT_SAMPLES; ++i) {
+    const double mu = (double)i / 128.0;
+    const double q = n_gap * n_gap * (1.0 - mu * mu);  // (n sin)^2, Snell's invariant
+    const double cg2 = 1.0 - q / (n_glass * n_glass);
+    if (!(cg2 > 0.0)) {  // the glass is at or beyond its critical angle: a lossless stack sends everything back
+      row[i] = 1.0f;
+      continue;
+    }
+    const Cx cg = root(cg2);
+    double rsum = 0.0;
+    for (int pol = 0; pol < 2; ++pol) {
+      const Cx y0 = pol ? Cx{n_gap / mu, 0.0} : Cx{n_gap * mu, 0.0};
+      const Cx ys = pol ? Cx{n_glass, 0.0} / cg : Cx{n_glass, 0.0} * cg;
+      Cx b{1.0, 0.0}, c = ys;
+      for (uint32_t k = nlayers; k-- > 0;) {  // from the glass outwards: (B, C) <- M_k (B, C)
+        const double nj = layer_index[k];
+        const Cx cj = root(1.0 - q / (nj * nj));
+        const double kd = kTwoPi * nj * layer_thickness_um[k] / wavelength_um;
+        const Cx mi{0.0, -1.0};
+        Cx nb, nc;
+        if (cj.re == 0.0 && cj.im == 0.0) {
+          // the layer exactly at its critical angle: the matrix's limit for cos_j -> 0.  s (y = n cos_j):
+          // sin(kd cos_j) / y -> kd / n and y sin -> 0, [[1, -i kd / n], [0, 1]]; p (y = n / cos_j): sin / y -> 0 and
+          // y sin -> n kd, [[1, 0], [-i n kd, 1]]
+          nb = b + mi * Cx{pol ? 0.0 : kd / nj, 0.0} * c;
+          nc = mi * Cx{pol ? nj * kd : 0.0, 0.0} * b + c;
+        } else {
+          const Cx yj = pol ? Cx{nj, 0.0} / cj : Cx{nj, 0.0} * cj;
+          Cx cd, sd;
+          cx_cos_sin_scaled(Cx{kd, 0.0} * cj, cd, sd);
+          nb = cd * b + (mi * sd / yj) * c;
+          nc = (mi * yj * sd) * b + cd * c;
+        }
+        b = nb;
+        c = nc;
+      }
+      const Cx r = (y0 * b - c) / (y0 * b + c);
+      rsum += r.re * r.re + r.im * r.im;
+    }
+    double rr = 0.5 * rsum;
+    if (!std::isfinite(rr)) return bad("reflectance is not finite");
+    if (rr > 1.0) rr = 1.0;  // (an evanescent stack gives 1 up to rounding)
+    row[i] = static_cast<float>(rr);
+  }
+  std::memcpy(out_row, row, sizeof row);
+  return BZR_OK;
+}
+
 // ---- far field (include/bzr.h bzr_farfield) ----
 // The frame's checks and what every user derives from it, stated once: the pole n = axis_u x axis_v normalised as
 // illuminate() normalises the target's normal, S = R + R and the cell sizes.  out[13]: n, axis_u, axis_v, R, S, cu,

@@ -13,6 +13,7 @@
 //   lensRefract     BezierLens::refract         reference/bezierLens.cpp:4-34
 //   lensRefractPower  the same with the refraction's Fresnel transmittance (patch_math_body.inc fresnel_t)
 //   attenuation     the chain's Beer-Lambert term (patch_math_body.inc att), for bzr_debug_attenuation
+//   coat_transmittance  the coated surface's lookup (patch_math_body.inc coat_t), for bzr_coat_transmittance
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -178,6 +179,9 @@ void fresnel_pairs(const float *eta, const float *cs, uint32_t n, float *t_out) 
 void attenuation(const float *x, uint32_t n, float *out) {
   for (uint32_t i = 0; i < n; ++i) out[i] = att(x[i]);
 }
+
+// bzr_coat_transmittance: the shared lookup text (patch_math_body.inc coat_t).
+float coat_transmittance(const float *row, float mu) { return coat_t(row, mu); }
 
 // newton_tail's hook answering "not needed" (bzr_debug_newton_short)
 struct NormalNever {

@@ -15,6 +15,8 @@ void newton_short_pair(const float *record, const float ray[6], bool limitNone, 
 void fresnel_pairs(const float *eta, const float *cs, uint32_t n, float *t_out);
 // The Beer-Lambert term att(x[i]) of n values (bzr_debug_attenuation with a null context).
 void attenuation(const float *x, uint32_t n, float *out);
+// The coated surface's transmittance coat_t(row, mu), row [BZR_COAT_SAMPLES] (bzr_coat_transmittance).
+float coat_transmittance(const float *row, float mu);
 }  // namespace bzr_host
 
 namespace bzr {

@@ -486,6 +486,70 @@ bzr_status bzr_trace_chain_bidir(bzr_ctx *ctx, const bzr_mesh *const *lenses, co
  * 0.  A segment above the bound (BZR_MAX_BOUNCES + 1)(2 * 8 + 1) = 153, or a NULL u, return BZR_ERR_INVALID_ARGUMENT
  * with nothing written. */
 bzr_status bzr_bidir_uniform(uint64_t seed, uint64_t ray, uint32_t segment, float *u);
+/* ---- surface coatings: tabulated reflectance in the bidirectional chain ----
+ * Every surface above is bare glass: T = fresnel_t(eta, cs, s2).  A coating replaces that T, per surface and per
+ * channel, by a table of the unpolarised power reflectance R against the cosine of incidence.
+ * Surface numbering.  A surface is (l, side), side = back ? 1 : 0, where back is bzr_trace_chain_bidir's side rule
+ * applied to the winning hit's normal n: n0 a0 + (n1 a1 + n2 a2) >= 0.  Here it is evaluated in open segments too, not
+ * only in glass segments.  In both kinds of segment the normal of a hit that the step accepts points out of the glass,
+ * so the rule names the same physical surface from either side: side 0 is the front of lens l, side 1 its back.
+ * The row.  table[2 l + side][c][i] is R of that surface for channel c at the gap-side cosine mu_i = i / 128: the cosine
+ * of the ray's angle to the normal in the medium outside the glass.  For a lossless stack R is the same from both sides
+ * at Snell-linked angles, so one row serves both directions; the gap-side cosine is the smooth parametrisation (the
+ * glass-side one has a square-root singularity at the critical angle).
+ * The step.  On a surface whose mask bit is set, in an open segment whose winning hit has cs < 0 or a glass segment
+ * whose hit has cs >= 0, with s2 < 0.99, T = coat_t(row, mu) stands where T = fresnel_t(eta, cs, s2) stood:
+ *   mu = open segment ? |cs| : sqrt_rn(1 - s2)        (the c2 Snell's step has; s2 = eta eta (1 - cs cs))
+ *   mu = min(mu, 1.0f)
+ *   x  = mu * 128.0f                                   (exact)
+ *   i  = min((int)x, 127)       f = x - (float)i       (exact)
+ *   d  = row[i + 1] - row[i]    p = f * d              R = row[i] + p
+ *   T  = 1.0f - R
+ * in IEEE binary32 without contraction, exact under BZR_MODE_FAST too: it belongs to the chain step like fresnel_t.
+ * With every entry in [0, 1], R and T stay in [0, 1] without a clamp: row[i] + fl(f d) lies between the two entries up
+ * to one rounding, and 0 and 1 are representable.  T is used exactly where bzr_trace_chain_bidir uses it: as the
+ * roulette's threshold (u >= T mirrors, u < T refracts with w = w A) and in the budget-spent step w = (w A) T.
+ * Unchanged on every surface: total reflection (s2 >= 1) and the band 0.99 <= s2 < 1; the draw
+ * G(ghost_seed, j, 256 + q - 1); the mirror step, the legs, A, the states and the termination bound.
+ * Mask and validation.  A surface whose mask bit is clear uses fresnel_t exactly as before; rows of unmasked surfaces
+ * are neither read nor validated.  With coat == NULL or mask == 0 every output is bzr_trace_chain_bidir's bit for bit,
+ * in both modes, fused and on the brute-force scan.  A mask bit at or above 2 nlens, a non-zero mask with a NULL table,
+ * an entry of a masked row that is not finite or lies outside [0, 1], and an explicit BZR_PIPELINE_STAGED return
+ * BZR_ERR_INVALID_ARGUMENT before any output is touched.
+ * Consequences.  A row of zeros is a perfect anti-reflection coating: no draw ever mirrors there, and the budget-spent
+ * step keeps the weight.  A row of ones is a mirror: a ray with budget left always reflects there, and a ray whose
+ * budget is spent refracts with weight exactly 0.
+ * Out of scope: a coating that absorbs (R + T < 1: metals, absorbing filters), polarisation, and the coating's phase
+ * in out_opl. */
+#define BZR_COAT_SAMPLES 129
+typedef struct bzr_coating {
+  const float *table;   /* [2 nlens][nchan][BZR_COAT_SAMPLES], row-major float32, host memory like ri_table */
+  uint32_t mask;        /* bit 2 l + side: surface (l, side) is coated; side 0 = front, 1 = back */
+} bzr_coating;
+/* bzr_trace_chain_bidir's arguments with `coat` behind axis (NULL: no surface is coated).  Fused, or BZR_ACCEL_NONE for
+ * the brute-force scan; at max_bounces = 0 it is the plain coated forward chain. */
+bzr_status bzr_trace_chain_coated(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                  const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                  uint32_t nlens, uint32_t nchan, const float *rays_soa, const uint8_t *channel,
+                                  const float *weight_in, const float *opl_in, uint32_t n, uint32_t max_bounces,
+                                  uint64_t ghost_seed, uint64_t first_ray, const float axis[3], const bzr_coating *coat,
+                                  float *out_rays_soa, float *out_weight, uint32_t *out_status, uint32_t *out_segments,
+                                  uint32_t *out_bounces, float *out_opl, float *out_glass, uint32_t flags);
+/* The lookup's host twin (no context, no device), compiled from the text the kernels compile: *t = coat_t(row, mu).
+ * A NULL pointer or a mu that is not >= 0 returns BZR_ERR_INVALID_ARGUMENT with nothing written. */
+bzr_status bzr_coat_transmittance(const float row[BZR_COAT_SAMPLES], float mu, float *t);
+/* One row on the host (no context, no device): the unpolarised reflectance (R_s + R_p) / 2 of a lossless dielectric
+ * stack between a gap of index n_gap and glass of index n_glass by the characteristic-matrix method, evaluated in
+ * binary64 at mu_i = i / 128 and rounded once to float.  Layers are listed from the gap side to the glass, thicknesses
+ * and the wavelength in micrometres; nlayers = 0 is the bare Fresnel surface.  Cosines are complex: an evanescent
+ * layer frustrates the reflection (however thick: its matrix is scaled, so cosh and sinh do not overflow, and R tends
+ * to 1), a layer exactly at its critical angle takes its matrix's limit, and glass at or beyond its critical angle
+ * gives R = 1 exactly.  out_row[0] = 1 by
+ * definition (mu = 0 divides by zero in p).  Indices or thicknesses that are not finite and positive, a wavelength
+ * that is not, nlayers above 8 and NULL pointers return BZR_ERR_INVALID_ARGUMENT with out_row untouched. */
+bzr_status bzr_coating_reflectance(double n_gap, double n_glass, const double *layer_index,
+                                   const double *layer_thickness_um, uint32_t nlayers, double wavelength_um,
+                                   float out_row[BZR_COAT_SAMPLES]);
 /* Absorption coefficients from a glass catalogue's internal transmittance, on the host (no context, no device):
  * out_a[i] = -ln(internal_transmittance[i]) / thickness, evaluated in binary64 and rounded once to float, per unit of
  * the length `thickness` is given in.  A transmittance outside (0, 1], a thickness that is not finite and positive or
@@ -834,6 +898,22 @@ bzr_status bzr_illuminate_bidir(bzr_ctx *ctx, const bzr_mesh *const *lenses, con
                                 uint64_t *back_count, uint64_t *back_power_q32, uint32_t flags,
                                 const bzr_farfield *far, uint64_t *far_flux_q32, uint32_t *far_hist,
                                 uint64_t *far_reflected_flux_q32, uint64_t *far_stats, uint64_t *far_power_q32);
+/* bzr_illuminate_bidir over the chain of bzr_trace_chain_coated: `coat` follows axis (checked as there); the same
+ * outputs, ledger and BACK rows.  With rad->surface == BZR_SURFACE_LOSSLESS the coating is ignored (no draw, no T): the
+ * call is bzr_illuminate_bidir's lossless call bit for bit.  With coat == NULL or mask == 0 it is bzr_illuminate_bidir
+ * bit for bit. */
+bzr_status bzr_illuminate_coated(bzr_ctx *ctx, const bzr_mesh *const *lenses, const float *ri_table,
+                                 const float *gap_table, const float *glass_absorb, const float *gap_absorb,
+                                 uint32_t nlens, uint32_t nchan, const bzr_emitter *em, uint64_t total_rays,
+                                 const bzr_target *target, const bzr_radiometry *rad, uint32_t max_bounces,
+                                 uint64_t ghost_seed, const float axis[3], const bzr_coating *coat,
+                                 uint64_t *flux_q32, uint32_t *hist,
+                                 uint64_t *reflected_flux_q32, uint32_t *reflected_hist,
+                                 uint64_t *stats, uint64_t *power_q32,
+                                 uint64_t *ledger_count, uint64_t *ledger_power_q32,
+                                 uint64_t *back_count, uint64_t *back_power_q32, uint32_t flags,
+                                 const bzr_farfield *far, uint64_t *far_flux_q32, uint32_t *far_hist,
+                                 uint64_t *far_reflected_flux_q32, uint64_t *far_stats, uint64_t *far_power_q32);
 /* Host helpers (no device).  bzr_farfield_cell: the cell rule above on the host, the device's twin: *cell is the
  * cell of direction d, or -1 where d is not binned (maps of 2^31 cells or more are refused).
  * bzr_farfield_directions: each cell centre in binary64, cell-major: dir_xyz [cells][3] the unit direction,

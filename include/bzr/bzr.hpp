@@ -514,6 +514,18 @@ void traceChainBidir(std::vector<BezierLens const *> const &lenses, std::vector<
                      float const (&axis)[3], Ray *outRays, float *outWeights, RefractionResult *outStatus, float *outOpl,
                      float *outGlass = nullptr, uint32_t *outSegments = nullptr, uint32_t *outBounces = nullptr,
                      Context *ctx = nullptr);
+// The coated chain (bzr_trace_chain_coated): traceChainBidir's arguments with the coating behind axis -- coatTable
+// [2 lenses][nchan][BZR_COAT_SAMPLES] reflectances (empty: no table) and coatMask, bit 2 l + side per coated surface
+// (side 0 the front of lens l, 1 its back).  With coatMask == 0 it is traceChainBidir bit for bit.  Throws what
+// traceChainBidir throws, and for a table of another size, a mask bit beyond the surfaces, a mask without a table and
+// an entry of a masked row outside [0, 1].
+void traceChainCoated(std::vector<BezierLens const *> const &lenses, std::vector<float> const &riTable,
+                      std::vector<float> const &gapTable, std::vector<float> const &glassAbsorb,
+                      std::vector<float> const &gapAbsorb, Ray const *rays, uint8_t const *channels, float const *weights,
+                      float const *opl, std::size_t n, uint32_t maxBounces, uint64_t ghostSeed, uint64_t firstRay,
+                      float const (&axis)[3], std::vector<float> const &coatTable, uint32_t coatMask, Ray *outRays,
+                      float *outWeights, RefractionResult *outStatus, float *outOpl, float *outGlass = nullptr,
+                      uint32_t *outSegments = nullptr, uint32_t *outBounces = nullptr, Context *ctx = nullptr);
 // Bins a traced batch by direction into a far-field map (bzr_farfield_bin): rays [n] as the traceChain* calls return
 // them (only the directions are read), weights, status and channels [n] each may be null (1.0f; every ray is seen,
 // otherwise only cOutside rays; channel 0).  farFlux / farHist [nchan][bins_v][bins_u] accumulate (one may be null);

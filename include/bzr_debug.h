@@ -131,6 +131,10 @@ int32_t bzr_debug_fresnel(const float *eta, const float *cs, uint32_t n, float *
  * the text evaluates it (no device); otherwise ctx is a bzr_ctx* (bzr.h) and one small kernel on its device does,
  * synchronously.  The two agree bit for bit.  Returns 0 on success. */
 int32_t bzr_debug_attenuation(void *ctx, const float *x, uint32_t n, float *out);
+/* bzr_coat_transmittance (bzr.h) over n cosines at once: out[i] = coat_t(row, mu[i]), row [BZR_COAT_SAMPLES], the same
+ * compilation of patch_math_body.inc coat_t.  A NULL pointer with n > 0, or a mu[i] that is not >= 0, returns
+ * BZR_ERR_INVALID_ARGUMENT with nothing written.  No device.  Returns 0 on success. */
+int32_t bzr_debug_coat_transmittance(const float *row, const float *mu, uint32_t n, float *out);
 /* A/B hook of k_land_far's wave combine (bzr_farfield_bin, bzr_illuminate_farfield): the following calls on this
  * context run at most `rounds` leader-election rounds per wave before the lanes left over issue their own atomics
  * (0: plain per-lane atomics, 64: unbounded); a negative value restores the default.  The maps' bits do not depend
